@@ -9,11 +9,15 @@ step   : one complete `irls` solve of that graph from its `init_mst` initialisat
          restored on the device before every step; the restore is inside the timed region).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--p-loop P] [--views n] [--edges m]
+                    [--dump-outputs DIR] [--full]
 
 For N > 1 the driver launches one process per GPU through torch.distributed.run; rank 0 prints
-ONE JSON line. The line also carries `roofline` (dominant kernel + the edge-residual kernel the
-north star names, HIP-event timed on the handle's stream) and `cpu_baseline` (the CPU oracle --
-a port, not Eigen+SuiteSparse, which cannot be built in this image -- on a bounded sample).
+ONE JSON line. A plain run sets up, warms up, times the K steps and prints the headline line
+(`ms_per_step` = milliseconds per timed step). --dump-outputs DIR writes what the last timed step
+computed (rotations, weights, score trace) as DIR/<name>.npy. With --full the line also carries
+`roofline` (dominant kernel + the edge-residual kernel the north star names, HIP-event timed on
+the handle's stream), the `also_*` legs, the sharded run's phase timing and its check against one
+GPU, and `cpu_baseline` (the CPU oracle -- a port, not Eigen+SuiteSparse -- on a bounded sample).
 """
 import argparse
 import json
@@ -469,6 +473,45 @@ def host_throttled_usec():
     return None
 
 
+def step_outputs(G, D, res, dist, Q0):
+    """What a caller of `irls` receives from the last step: the rotations (rows [x, y, z, w]), the edge weights and the
+    score trace. A sharded handle knows the rows and edges of its own shards: the ranks' parts are merged on every rank,
+    and the fixed views, which no shard writes back, keep the rotations they were given."""
+    if D is None:
+        return {"rotations": G.get_rotations(), "weights": G.get_weights(), "scores": res["scores"]}
+    Q = D.get_rotations(into=np.full((D.n_total, 4), np.nan))
+    w = D.get_weights()
+    parts = [None] * dist.get_world_size()
+    dist.all_gather_object(parts, (Q, w))
+    for Qr, wr in parts:   # a cross-shard edge lives on both of its shards, computed identically
+        Q = np.where(np.isnan(Q), Qr, Q)
+        w = np.where(np.isnan(w), wr, w)
+    Q[:D.f] = Q0[:D.f]
+    return {"rotations": Q, "weights": w, "scores": res["scores"]}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Writes every array as d/<name>.npy in float64. If they would exceed `limit` bytes in all, every array keeps the same
+    fraction of its rows, a sorted sample drawn with a fixed seed, and d/<name>_rows.npy holds the row indices (float64)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    need = sum(a.nbytes for a in arrays.values())
+    # a sampled row costs its own bytes plus 8 for its index; 64 KiB kept back for the .npy headers
+    frac = 1.0 if need <= limit else (limit - (64 << 10)) / sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(seed).choice(len(a), int(len(a) * frac), replace=False))
+            a = a[rows]
+            np.save(os.path.join(d, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(d, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def main():
     thr0 = host_throttled_usec()
     ap = argparse.ArgumentParser()
@@ -496,8 +539,15 @@ def main():
                     help="N > 1 only: if the library's RCCL communicator cannot be formed, run the same sharded solver over "
                          "the host-staged wire (torch.distributed/gloo) instead of FAILING. Without this flag a multi-GPU "
                          "run either measures RCCL over xGMI or exits non-zero -- it can never silently measure gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: kernel rooflines, rocprofv3 passes, the other sizes and solvers, the CPU "
+                         "baselines and, for N > 1, the phase timing and the check against one GPU (--no-* trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rotations, weights, score trace) as DIR/<name>.npy")
     ap.add_argument("--cpu-only", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_only:
         return cpu_baselines_main(json.loads(args.cpu_only))
 
@@ -617,27 +667,34 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     dstats = D.stats() if D is not None else None
+    dumped = None
+    if args.dump_outputs:   # what the last timed step left, before anything else runs on the handle
+        outputs = step_outputs(G, D, res, dist, Q0)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, outputs)
+        del outputs
     if D is not None:
         dinfo = D.info()   # wire actually used + ranks of the RCCL communicator as RCCL counts them
-        # where an iteration goes, phase by phase (irotavg_dist_timing): a few UNTIMED solves with the phase clock on --
-        # the stream is drained at every phase boundary, so the phases are to be read against each other
-        D.timing(True)
-        for _ in range(3):
-            step()
-        dphases = D.timing(False)
-        tp = torch.tensor([dphases["us_per_iteration"][k] for k in capi.DistGraph.TIMING_PHASES], dtype=torch.float64,
-                          device="cpu" if share else "cuda")
-        dist.all_reduce(tp, op=dist.ReduceOp.MAX)   # the slowest rank's phases
-        dphases["us_per_iteration_max_over_ranks"] = {k: float(tp[i].item()) for i, k in enumerate(capi.DistGraph.TIMING_PHASES)}
+        if args.full:
+            # where an iteration goes, phase by phase (irotavg_dist_timing): a few UNTIMED solves with the phase clock on --
+            # the stream is drained at every phase boundary, so the phases are to be read against each other
+            D.timing(True)
+            for _ in range(3):
+                step()
+            dphases = D.timing(False)
+            tp = torch.tensor([dphases["us_per_iteration"][k] for k in capi.DistGraph.TIMING_PHASES], dtype=torch.float64,
+                              device="cpu" if share else "cuda")
+            dist.all_reduce(tp, op=dist.ReduceOp.MAX)   # the slowest rank's phases
+            dphases["us_per_iteration_max_over_ranks"] = {k: float(tp[i].item()) for i, k in enumerate(capi.DistGraph.TIMING_PHASES)}
         D.close()
-        if rank == 0:   # kernel rooflines are measured on a single-GPU handle of the same graph
+        if rank == 0 and args.full:   # kernel rooflines are measured on a single-GPU handle of the same graph
             G = capi.Graph(S["I"], S["QQ"], S["n"], 1, pcg_rtol=args.rtol, device=dev)
             G.set_rotations(Q0)
             res_single = G.irls(4, SIG, 100, 1e-3)   # ... and the sharded run is held against it (dist.matches_single_gpu)
 
     if rank == 0:
         iters = res["iters"]
-        st = G.stats()
+        st = G.stats() if G is not None else {}
         if dstats is not None:
             st = dict(st, pcg_iters=dstats["pcg_iters"], pcg_solves=dstats["pcg_solves"])
         value = S["m"] * iters * args.steps / dt
@@ -670,9 +727,11 @@ def main():
                            "idle clocks; the first solves of a process run ~8 %% slower); every step repeats the "
                            "identical solve (on the PCG path the predictive poll schedule and the cached coarse inverse "
                            "are then warm; the direct solver keeps nothing between solves) -- not a first-call figure "
-                           "(that is also_one_shot_host_buffers)" % args.ramp,
+                           "(that is --full's also_one_shot_host_buffers)" % args.ramp,
         }
         line["build"] = build_record
+        if dumped is not None:
+            line["outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if dstats is not None:
             line["config"]["dist"] = dinfo
             # the first multi-GPU run diagnoses itself: the wire that carried it, RCCL's own count of the communicator,
@@ -681,6 +740,12 @@ def main():
                 "wire": dinfo["wire"], "halo": dinfo["halo"], "ncclCommCount": dinfo["rccl_comm_ranks"], "world": world,
                 "hosted_allowed": bool(args.allow_hosted),
                 "valid_scaling_measurement": bool(dinfo["wire"] == "rccl" and dinfo["rccl_comm_ranks"] == world and not share),
+                "sharded_solver": "direct" if dinfo.get("direct_block") else "pcg",
+                "closures": dinfo.get("closures", 0),
+                "expected": expected_scaling(args, world),
+            }
+        if dstats is not None and args.full:
+            line["dist"].update({
                 # the sharded result against the same graph on ONE GPU of this node (rank 0's handle): a wrong exchange on
                 # a wire that no test could exercise shows here, not in a plausible-looking throughput
                 "matches_single_gpu": bool(res["iters"] == res_single["iters"] and
@@ -689,17 +754,19 @@ def main():
                 "max_rel_score_diff": float(np.max(np.abs(np.asarray(res["scores"][:min(res["iters"], res_single["iters"])]) -
                                                           np.asarray(res_single["scores"][:min(res["iters"], res_single["iters"])])) /
                                                    np.maximum(np.abs(np.asarray(res_single["scores"][:min(res["iters"], res_single["iters"])])), 1e-300))),
-                "sharded_solver": "direct" if dinfo.get("direct_block") else "pcg",
-                "closures": dinfo.get("closures", 0),
                 "phases_us_per_iteration": dphases["us_per_iteration_max_over_ranks"],
                 "phases_us_per_iteration_rank0": dphases["us_per_iteration"],
                 "phases_iterations": dphases["iterations"],
                 "phases_note": "3 untimed solves with irotavg_dist_timing on (stream drained at every phase boundary: read the "
                                "phases against each other, their sum exceeds the undisturbed iteration); max over ranks",
-                "expected": expected_scaling(args, world),
-            }
-        if args.no_kernels:
-            G.close()
+            })
+        if args.no_kernels or not args.full:
+            # a plain run: the headline and nothing that needs runs of its own
+            if G is not None:
+                G.close()
+            thr1 = host_throttled_usec()
+            line["host_throttled_usec"] = None if thr0 is None or thr1 is None else thr1 - thr0
+            line["host_throttled_usec_timed_region"] = None if thr_a is None or thr_b is None else thr_b - thr_a
             print(json.dumps(line), flush=True)
             if dist is not None:
                 dist.barrier()

@@ -71,7 +71,7 @@ def test_two_processes_rccl_on_one_device():
     assert "DIST_WORKER_OK" in r.stdout
 
 
-def test_bench_runs_with_two_ranks():
+def test_bench_runs_with_two_ranks(tmp_path):
     """bench.py's own N > 1 branch (sharding, timing protocol, max over ranks, the JSON line), two ranks
     sharing the box's one GPU (IROTAVG_BENCH_SHARE_GPU=1). RCCL refuses two ranks on one device, so this
     exercises both answers to "the library's communicator cannot be formed": the refusal (default) and, with
@@ -95,7 +95,9 @@ def test_bench_runs_with_two_ranks():
     assert refused["value"] is None and "refusing" in refused["error"] and refused["dist"]["wire"] == "none"
     # (2) with it: the same sharded solver over the host-staged wire, and the line says so in machine-readable form
     cmd[cmd.index("29617")] = "29618"
-    r = subprocess.run(cmd + ["--allow-hosted"], capture_output=True, text=True, timeout=420, env=env, cwd=ROOT)
+    # (--full: the phase timing and the check against one GPU are not part of a plain run)
+    r = subprocess.run(cmd + ["--allow-hosted", "--full", "--dump-outputs", str(tmp_path / "two")], capture_output=True,
+                       text=True, timeout=420, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
     two = json.loads(lines[0])
@@ -111,11 +113,16 @@ def test_bench_runs_with_two_ranks():
     assert ph["local_reductions"] > 0 and ph["gather_of_separators"] > 0 and ph["halo_of_the_step"] > 0
     assert ph["closure_sum"] == 0.0                           # no closures in this graph
     assert "ms_per_step_by_gpus" in d["expected"] or d["expected"]["workload"] is None
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common,
-                         capture_output=True, text=True, timeout=420, cwd=ROOT)
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs",
+                          str(tmp_path / "one")] + common, capture_output=True, text=True, timeout=420, cwd=ROOT)
     one = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][0])
     assert two["n_gpus"] == 2 and two["scaling"] == "strong" and two["value"] > 0
     assert two["iters_to_converge"] == one["iters_to_converge"]
     assert "2 contiguous ranges" in two["config"]["parallelism"]
     np_ = __import__("numpy")
     np_.testing.assert_allclose(two["final_scores"], one["final_scores"], rtol=1e-6)
+    # the dumped outputs of the last step: the ranks' shards merged into the arrays one GPU returns
+    for name, tol in (("rotations", dict(rtol=0, atol=1e-8)), ("weights", dict(rtol=1e-6, atol=1e-12))):
+        a2, a1 = np_.load(tmp_path / "two" / (name + ".npy")), np_.load(tmp_path / "one" / (name + ".npy"))
+        assert a2.shape == a1.shape and not np_.isnan(a2).any(), name
+        np_.testing.assert_allclose(a2, a1, err_msg=name, **tol)

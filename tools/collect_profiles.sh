@@ -6,12 +6,12 @@ set -u
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/final
 mkdir -p $OUT
-timeout 900 python bench.py > $OUT/bench_final.json 2> $OUT/bench_final.err
+timeout 900 python bench.py --full > $OUT/bench_final.json 2> $OUT/bench_final.err
 cp -r gpurun_out/bench_profile $OUT/bench_profile 2>/dev/null
-timeout 400 python bench.py --views 1000000 --edges 20000000 --steps 20 --warmup 2 --ramp 5 --no-pmc > $OUT/bench_1M20M.json 2> $OUT/bench_1M20M.err
-timeout 300 python bench.py --views 10000 --edges 150000 --no-pmc > $OUT/bench_10k150k.json 2> $OUT/bench_10k.err
-timeout 300 python bench.py --views 10000 --edges 150000 --p-loop 0.02 --steps 50 --no-pmc > $OUT/bench_10k150k_loop02.json 2>> $OUT/bench_10k.err
-timeout 600 python bench.py --p-loop 0.02 --steps 20 > $OUT/bench_loop02.json 2> $OUT/bench_loop02.err
+timeout 400 python bench.py --full --views 1000000 --edges 20000000 --steps 20 --warmup 2 --ramp 5 --no-pmc > $OUT/bench_1M20M.json 2> $OUT/bench_1M20M.err
+timeout 300 python bench.py --full --views 10000 --edges 150000 --no-pmc > $OUT/bench_10k150k.json 2> $OUT/bench_10k.err
+timeout 300 python bench.py --full --views 10000 --edges 150000 --p-loop 0.02 --steps 50 --no-pmc > $OUT/bench_10k150k_loop02.json 2>> $OUT/bench_10k.err
+timeout 600 python bench.py --full --p-loop 0.02 --steps 20 > $OUT/bench_loop02.json 2> $OUT/bench_loop02.err
 cp -r gpurun_out/bench_profile $OUT/bench_profile_loop02 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/l1band -o l -- python $GRAFT_REPO_ROOT/tools/prof_case.py --what l1ra --reps 7 > $GRAFT_REPO_ROOT/$OUT/l1band.log 2>&1

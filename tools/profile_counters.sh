@@ -9,8 +9,8 @@ R=$PWD
 export TMPDIR=/tmp
 mkdir -p "$OUT"
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/trace" -o t -- python "$R/bench.py" --steps 3 --warmup 1 --no-cpu --no-extra "$@" > "$R/$OUT/trace.log" 2>&1
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$R/$OUT/fetch" -o f -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu --no-extra "$@" > "$R/$OUT/fetch.log" 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$R/$OUT/write" -o w -- python "$R/bench.py" --steps 2 --warmup 1 --no-cpu --no-extra "$@" > "$R/$OUT/write.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/trace" -o t -- python "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu --no-extra "$@" > "$R/$OUT/trace.log" 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$R/$OUT/fetch" -o f -- python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu --no-extra "$@" > "$R/$OUT/fetch.log" 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$R/$OUT/write" -o w -- python "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu --no-extra "$@" > "$R/$OUT/write.log" 2>&1
 cd "$R"
 ls -R "$OUT" | head -30
