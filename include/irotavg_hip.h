@@ -38,6 +38,7 @@ extern "C" {
 #define IROTAVG_ERR_NOT_CONVERGED (-8) /* inner PCG hit its iteration cap -- after irls has re-inverted a re-used
                                           coarse inverse and, on a single level of <= 1024 views, tried the dense
                                           Cholesky solve; the iterate reached so far is left in place */
+#define IROTAVG_ERR_UNSUPPORTED (-9)  /* the query is not available on this kind of handle (irotavg_graph_rotation_variance) */
 
 /* ral/l1_irls.hpp:56-57 -- the integer values are ABI */
 enum irotavg_cost {
@@ -258,6 +259,31 @@ int irotavg_graph_direct_info(irotavg_graph *g, int64_t *info, int cap);
  * irotavg_stats.last_relres. IROTAVG_ERR_BAD_ARG if the handle's systems do not run through the direct solver or none
  * has been solved yet. */
 int irotavg_graph_direct_residual(irotavg_graph *g, double *relres);
+
+/* Uncertainty of the IRLS solution (docs/rotation_variance.md). M = A' diag(d^2) A with A = irotavg_make_A's
+ * incidence (m x nu, nu = n_total - f) and d = the handle's current weights (irotavg_graph_get_weights), Sigma = M^-1:
+ *   var[v]      = Sigma_{v-f, v-f} for a free view v, 0 for a fixed one (n_total entries; NULL: not asked for);
+ *   pair_var[t] = u' Sigma u, u = e_i - e_j over the free ones of (pairs[2t], pairs[2t+1]) (0 for two fixed views, i == j);
+ *   scale       = s^2 = sum_k d_k^2 |r_k|^2 / (3 (m_A - nu)) over the m_A edges with a nonzero row of A, r_k the edge
+ *                 residuals of the current rotations (NaN when m_A <= nu). Covariance of view v's rotation vector under
+ *                 the reference's linearisation: s^2 var[v] I_3; of log(R_j R_i') for a pair: s^2 pair_var I_3.
+ * One factorisation serves both outputs. Routes: nu <= 2048 -- a dense inverse; the banded direct solver's handles
+ * (stats.band_block > 0) -- block-tridiagonal selected inversion + Woodbury correction for the loop closures; any other
+ * (multigrid-PCG) handle: pairs only (var == NULL), three pairs per solve of the handle's own PCG to pcg_rtol; var != NULL
+ * there gives IROTAVG_ERR_UNSUPPORTED. Read-only: rotations, weights, residuals, stats and every later result of the
+ * handle are as if the call had not run. Deterministic (bitwise). A singular M (a view that no weighted edge ties to a
+ * fixed one: a pivot not above 1e-13 x its row's diagonal in M, or a PCG breakdown) gives IROTAVG_ERR_SOLVER (or the
+ * PCG's IROTAVG_ERR_NOT_CONVERGED); outputs are written only on success. Out-of-range ids / npairs < 0:
+ * IROTAVG_ERR_BAD_ARG before any device work. */
+int irotavg_graph_rotation_variance(irotavg_graph *g, double *var /* n_total, or NULL */, int64_t npairs,
+                                    const int32_t *pairs /* 2*npairs view ids */, double *pair_var /* npairs */,
+                                    double *scale /* may be NULL */);
+/* The same query without a handle (e.g. after irotavg_irls in src/ViewGraph.cpp:1400-1417): Q and weights are what
+ * irls returned. Goes through the one-shot calls' kept handle (irotavg_oneshot_cache), so a call after irotavg_irls on
+ * the same I, QQ does not rebuild. */
+int irotavg_rotation_variance(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq,
+                              const double *Q, int64_t ldq, const double *weights, double *var, int64_t npairs,
+                              const int32_t *pairs, double *pair_var, double *scale);
 
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash

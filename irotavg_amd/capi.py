@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libirotavg_hip.so")
 OK = 0
 ERR_BAD_ARG, ERR_NOT_SPANNING, ERR_SOLVER, ERR_UNKNOWN_COST = -1, -2, -3, -4
 ERR_NOMEM, ERR_HIP, ERR_NO_DEVICE, ERR_NOT_CONVERGED = -5, -6, -7, -8
+ERR_UNSUPPORTED = -9
 
 # symbols declared in include/irotavg_hip.h (kept in sync by tests/test_abi.py)
 SYMBOLS = [
@@ -40,6 +41,7 @@ SYMBOLS = [
     "irotavg_window_solve", "irotavg_window_solve_kernel", "irotavg_trim_memory", "irotavg_rmat2quat", "irotavg_quat2rmat", "irotavg_viewgraph_save_poses",
     "irotavg_oneshot_cache", "irotavg_oneshot_cache_clear", "irotavg_oneshot_cache_stats",
     "irotavg_dist_timing",
+    "irotavg_graph_rotation_variance", "irotavg_rotation_variance",
 ]
 
 
@@ -136,6 +138,9 @@ def lib():
     L.irotavg_graph_fingerprint.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.irotavg_graph_direct_info.argtypes = [vp, _i64p, C.c_int]
     L.irotavg_graph_direct_residual.argtypes = [vp, _dp]
+    L.irotavg_graph_rotation_variance.argtypes = [vp, _dp, C.c_int64, _ip, _dp, _dp]
+    L.irotavg_rotation_variance.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
+                                            _dp, C.c_int64, _ip, _dp, _dp]
     L.irotavg_viewgraph_create.argtypes = [C.POINTER(vp), C.POINTER(Options)]
     L.irotavg_viewgraph_destroy.argtypes = [vp]
     L.irotavg_viewgraph_destroy.restype = None
@@ -380,6 +385,12 @@ class Graph:
         check(lib().irotavg_graph_direct_residual(self._h, _d(out)), "direct_residual")
         return out
 
+    def rotation_variance(self, pairs=None, marginals=True, allow_rc=()):
+        """irotavg_graph_rotation_variance: dict(rc, var (n_total, or None), pair_var (npairs), scale). The covariance
+        of view v's rotation vector is scale * var[v] * I_3, of log(R_j R_i') for a pair scale * pair_var * I_3."""
+        return _variance_call(lambda *a: lib().irotavg_graph_rotation_variance(self._h, *a), self.n_total, pairs,
+                              marginals, allow_rc, "irotavg_graph_rotation_variance")
+
     def fingerprint(self):
         """Hashes of every structural array + the kernel-choosing scalars (irotavg_graph_fingerprint)."""
         out = (C.c_uint64 * 512)()
@@ -392,6 +403,30 @@ class Graph:
         ms = C.c_double(0)
         check(lib().irotavg_graph_time_kernel(self._h, which, reps, C.byref(ms)), "time_kernel")
         return ms.value
+
+
+def _variance_call(call, n_total, pairs, marginals, allow_rc, where):
+    P = np.zeros((0, 2), dtype=np.int32) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    var = np.full(n_total, np.nan) if marginals else None
+    pv = np.full(max(len(P), 1), np.nan)
+    scale = C.c_double(np.nan)
+    rc = call(_d(var) if marginals else None, len(P), _i(P) if len(P) else None, _d(pv), C.byref(scale))
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, where)
+    return dict(rc=rc, var=var, pair_var=pv[:len(P)], scale=scale.value)
+
+
+def rotation_variance(I, QQ, Q, weights, f, pairs=None, marginals=True, allow_rc=()):
+    """irotavg_rotation_variance: the query without a handle (through the kept one-shot handle), from the rotations and
+    weights irls returned."""
+    I = edges(I)
+    QQ = fmat(QQ)
+    Q = fmat(Q)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    n_total = Q.shape[0]
+    return _variance_call(lambda *a: lib().irotavg_rotation_variance(len(I), n_total, int(f), _i(I), _d(QQ),
+                                                                     QQ.shape[0], _d(Q), Q.shape[0], _d(w), *a),
+                          n_total, pairs, marginals, allow_rc, "irotavg_rotation_variance")
 
 
 def oneshot_cache(enable):

@@ -47,6 +47,7 @@ const char *irotavg_error_string(int code) {
     case IROTAVG_ERR_HIP: return "HIP runtime error";
     case IROTAVG_ERR_NO_DEVICE: return "no usable HIP device (this library has no CPU fallback)";
     case IROTAVG_ERR_NOT_CONVERGED: return "inner PCG did not converge within pcg_max_iters";
+    case IROTAVG_ERR_UNSUPPORTED: return "not supported on this handle (rotation variance: marginals need a dense or banded direct-solver handle)";
     default: return "unknown error";
     }
 }
@@ -401,6 +402,22 @@ int irotavg_graph_direct_info(irotavg_graph *h, int64_t *info, int cap) {
     if (!h || !info || cap < 1) return IROTAVG_ERR_BAD_ARG;
     API_TRY
     return bcr_info(h->g, info, cap);
+    API_CATCH
+}
+
+// arguments of a rotation-variance query, checked before any device work
+static bool variance_args_ok(int64_t n_total, int64_t npairs, const int32_t *pairs, const double *pair_var) {
+    if (npairs < 0 || (npairs > 0 && (!pairs || !pair_var))) return false;
+    for (int64_t t = 0; t < 2 * npairs; t++)
+        if (pairs[t] < 0 || pairs[t] >= n_total) return false;
+    return true;
+}
+
+int irotavg_graph_rotation_variance(irotavg_graph *h, double *var, int64_t npairs, const int32_t *pairs,
+                                    double *pair_var, double *scale) {
+    if (!h || !variance_args_ok(h->g.n_total, npairs, pairs, pair_var)) return IROTAVG_ERR_BAD_ARG;
+    API_TRY
+    return rotation_variance(h->g, var, npairs, pairs, pair_var, scale);
     API_CATCH
 }
 
@@ -822,6 +839,23 @@ int irotavg_l1ra(int64_t m, int64_t n_total, int f, const int32_t *I, const doub
     if (!h) return rc;
     if (rc == IROTAVG_OK || rc == IROTAVG_ERR_NOT_CONVERGED) (void)irotavg_graph_get_rotations(h, Q, ldq);
     oneshot_close(h, key, cached, rc);
+    return rc;
+}
+
+int irotavg_rotation_variance(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq,
+                              const double *Q, int64_t ldq, const double *weights, double *var, int64_t npairs,
+                              const int32_t *pairs, double *pair_var, double *scale) {
+    if (!Q || !weights || !variance_args_ok(n_total, npairs, pairs, pair_var)) return IROTAVG_ERR_BAD_ARG;
+    irotavg_graph *h = nullptr;
+    OneShotKey key;
+    bool cached = false;
+    int rc = oneshot_open(&h, &key, &cached, m, n_total, f, I, QQ, ldqq);
+    if (rc != IROTAVG_OK) return rc;
+    rc = irotavg_graph_set_rotations(h, Q, ldq);
+    if (rc == IROTAVG_OK) rc = irotavg_graph_set_weights(h, weights);
+    if (rc == IROTAVG_OK) rc = irotavg_graph_rotation_variance(h, var, npairs, pairs, pair_var, scale);
+    // (a handle the query refused is as good as before: it is kept like a successful one)
+    oneshot_close(h, key, cached, rc == IROTAVG_ERR_UNSUPPORTED || rc == IROTAVG_ERR_SOLVER ? IROTAVG_OK : rc);
     return rc;
 }
 

@@ -223,6 +223,8 @@ int l1decode_pd_dev(Graph &g, int coord_plane_from_er, const double *y_host, int
                     double *x_host, int *stuck, int out_component);
 int time_kernel(Graph &g, int which, int reps, double *ms);
 void release_l1_clones(Graph &g);
+// l1pd.hip: a solver clone -- the handle's static structure aliased, every array a solve writes its own (stream: `stream`)
+std::unique_ptr<Graph> make_solver_clone(Graph &g, hipStream_t stream);
 void normalise_rotations(Graph &g);
 void fill(Graph &g, double *p, long long n, double v);
 // device -> pinned host copy of scal + flags (one DMA) and stream synchronisation
@@ -357,6 +359,8 @@ void bcr_top_closures_alloc(Graph &g0, BcrTop &T, int r);
 void bcr_shard_closures_forward(Graph &g, BcrTop &T, int rank);
 void bcr_top_solve_closures(Graph &g, BcrTop &T);
 void bcr_shard_closures_correct(Graph &g, BcrTop &T);
+// marginals.hip: irotavg_graph_rotation_variance (arguments checked by the caller; outputs written only on success)
+int rotation_variance(Graph &g, double *var, int64_t npairs, const int32_t *pairs, double *pair_var, double *scale);
 // dense.hip
 void dense_refresh(Graph &g);
 void dense_select_slot(Graph &g, int slot);

@@ -810,7 +810,7 @@ int l1decode_pd_dev(Graph &g, int er_plane, const double *y_host, int pdmaxiter,
 // iteration (ral/l1_irls.cpp:889-892, independent by construction) run concurrently on three
 // streams. Every kernel of this latency-bound path leaves most of the chip idle, so the three
 // chains overlap almost perfectly.
-static std::unique_ptr<Graph> make_solver_clone(Graph &g, hipStream_t stream) {
+std::unique_ptr<Graph> make_solver_clone(Graph &g, hipStream_t stream) {
     std::unique_ptr<Graph> c(new Graph());
     Graph &q = *c;
     q.is_clone = true;
