@@ -17,6 +17,10 @@
  * Error convention: the reference prints to stderr and calls exit(-1); this ABI returns one of
  * the negative codes below and never throws or exits. There is NO CPU fallback: if no HIP
  * device is usable every compute entry point returns IROTAVG_ERR_NO_DEVICE.
+ *
+ * Environment: the IROTAVG_* variables this header names (README.md lists all of them) are read when the
+ * handle, the sharded handle or the view-graph is created -- once per call by the one-shot entry points -- and
+ * hold for that object's life; IROTAVG_ONESHOT_CACHE and IROTAVG_POOL_LIMIT_MB are read once per process.
  */
 #ifndef IROTAVG_HIP_H
 #define IROTAVG_HIP_H

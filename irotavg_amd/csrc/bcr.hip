@@ -1291,8 +1291,7 @@ template <int B>
 bool bcr_up_reserve(Graph &g, int nwg) {
     const int capwg = bcr_up_capacity<B>(g.device);
     if (capwg <= 0) return false;
-    int total = 1024;
-    if (const char *e = getenv("IROTAVG_BCR_UP_CAP")) total = atoi(e);
+    const int total = g.sw.bcr_up_cap;
     const int cost = (int)(((long long)nwg * 1024 + capwg - 1) / capwg);
     const int need = cost - g.bcr_up_held;
     if (need <= 0) return true;
@@ -2524,14 +2523,14 @@ static void bcr_alloc(Graph &g) {
         if (ncu <= 0) ncu = 256;
         const int cap = ncu * (B <= 24 && NR == 3 ? 2 : 1);
         const int full = nch0 / cap * cap, rem = nch0 - full;
-        if (full > 0 && rem > 0 && rem <= cap / 4 && !g.bcr_shard && !getenv("IROTAVG_BCR_NO_MIXED")) {
+        if (full > 0 && rem > 0 && rem <= cap / 4 && !g.bcr_shard && !g.sw.bcr_no_mixed) {
             nraw = nb0 - 8 * full;
             nch0 = full;
         }
     }
     // the last level: one chunk of <= 8 blocks, or (round 5) one workgroup of <= 16 blocks that also makes its way back
     // -- three right-hand sides, blocks up to 24 rows (LDS), no closures (their step programs know chunks), not a shard
-    S.top16 = B <= 24 && S.nfar == 0 && !g.bcr_shard && !getenv("IROTAVG_BCR_NO_TOP16");
+    S.top16 = B <= 24 && S.nfar == 0 && !g.bcr_shard && !g.sw.bcr_no_top16;
     const int topmax = S.top16 ? kTopMax : 8;
     int nb = nb0, nch = nch0;
     for (int l = 0;; l++) {
@@ -2597,9 +2596,7 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
     const int nl = (int)S.lev.size();
     // (the stamp helpers steer ONE handle through BcrState::dbg_word instead of rewriting the process environment under
     // other handles' and threads' solves -- advisor, round 5; the library itself never writes the environment)
-    const char *env_s = getenv("IROTAVG_BCR_DBG");
-    const int env_dbg = env_s ? atoi(env_s) : 0;
-    const int dbg = S.dbg_word >= 0 ? S.dbg_word : env_dbg;
+    const int dbg = S.dbg_word >= 0 ? S.dbg_word : g.sw.bcr_dbg;
     long long *stamps = nullptr;
     if (dbg & 64) {
         if (!S.stamps.p) S.stamps.alloc((size_t)S.lev[0].nch * 16);
@@ -2615,8 +2612,7 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
     bool fused_up = false;
     if constexpr (NR == 3 && B <= 24) {
         fused_up = nl >= 3 && nl - 1 <= kUpLevels && only < 0 && phase == 0 && !open_top && !g.bcr_shard && S.nfar == 0 &&
-                   S.lev[1].nch <= 256 && !(dbg & 64) && !getenv("IROTAVG_BCR_NARROW") && !getenv("IROTAVG_BCR_NO_FUSED_UP") &&
-                   !g.bcr_no_fused_up;
+                   S.lev[1].nch <= 256 && !(dbg & 64) && !g.bcr_no_fused_up;
         if ((dbg & 128) && !S.stamps.p) S.stamps.alloc((size_t)std::max(S.lev[0].nch * 16, 32 * kUpLevels));
         if (fused_up) fused_up = bcr_up_reserve<B>(g, S.lev[1].nch);
     }
@@ -2673,7 +2669,7 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
                     IRH_CHECK(hipStreamSynchronize(st));  // (A is on this stack)
                 }
                 // (tests: the give-up path without a second process -- the word is set as if a wait had timed out)
-                if (getenv("IROTAVG_BCR_FAKE_UP_FAIL") && g.stats.direct_up_fallbacks == 0)
+                if (g.sw.bcr_fake_up_fail && g.stats.direct_up_fallbacks == 0)
                     IRH_CHECK(hipMemsetAsync(S.up_cnt.p + kUpLevels, 1, sizeof(int), st));
                 const size_t lds = bcr_up_lds<B>(S.top16 ? S.lev[nl - 1].nb : 0);
                 static std::atomic<size_t> lds_set[16];
@@ -2698,7 +2694,7 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
         g.bval.p, S.ghost_extcol.p, (int)g.bcr_shard, stamps, S.nfar > 0 ? S.Dinv[(size_t)l].p : (double *)nullptr,         \
         S.nfar > 0 ? S.topDinv.p : (double *)nullptr, S.nfar > 0 ? S.dead.p : (int *)nullptr, (int)g.bcr_guard
         // eight waves per chunk when every chunk has a CU to itself (see k_bcr_reduce)
-        const bool wide = L.nch <= 256 && !getenv("IROTAVG_BCR_NARROW");
+        const bool wide = L.nch <= 256;
 #define IRH_BCR_LAUNCH(L0_, TOP_)                                                                                   \
     if constexpr (B <= 24) {                                                                                        \
         if (wide)                                                                                                   \
@@ -2720,13 +2716,13 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
 #undef IRH_BCR_LAUNCH
 #undef IRH_BCR_ARGS
     }
-    // the ways back of the levels above level 0 in one launch (k_bcr_back_top) unless this is a shard, the closures'
-    // columns ride along or IROTAVG_BCR_NO_FUSED_BACK is set
+    // the ways back of the levels above level 0 in one launch (k_bcr_back_top) unless this is a shard or the closures'
+    // columns ride along
     double4 *Xout = g.bcr_out ? g.bcr_out : g.X.p + g.ng;
     bool fused_back = false;
     // (a single-workgroup top has made its own way back: the levels below it are left)
     const int ltop = S.top16 ? nl - 2 : nl - 1;
-    if constexpr (NR == 3) fused_back = ltop >= 1 && !g.bcr_shard && !open_top && !getenv("IROTAVG_BCR_NO_FUSED_BACK");
+    if constexpr (NR == 3) fused_back = ltop >= 1 && !g.bcr_shard && !open_top;
     // K6 inside the ways back (run_irls asked for it and bcr_apply_ok() said yes): every solution row of level 0 is written
     // by k_bcr_back (level 0's chunks: slots 0 .. nch0 - 1) or, on a mixed level 1, by k_bcr_back_top (slots nch0 ...)
     const bool apply = NR == 3 && g.bcr_apply && only < 0 && phase == 0 && (fused_back || (S.top16 && nl == 2)) && !g.bcr_out &&
@@ -2792,9 +2788,8 @@ static void bcr_run_all(Graph &g, int only) {
     bcr_launch_forward<B>(st, P, r, S.cl_nslots, S.cl_off.p, S.cl_step.p, S.cl_init.p, S.cl_R.p, S.cl_W.p, S.cl_T.p, nullptr,
                           nullptr, nullptr, nullptr, 0, 0);
     const int nt = (npad + 15) / 16;
-    static const bool s_tiles = getenv("IROTAVG_BCR_S_TILES") != nullptr;  // A/B: the tile kernel for every closure count
     const size_t lds_pairs = (size_t)4 * (S.cl_maxsteps + 64) * sizeof(int);
-    if (r <= kClosurePairsMax && S.cl_maxsteps < 32768 && lds_pairs <= 60 * 1024 && !s_tiles)
+    if (r <= kClosurePairsMax && S.cl_maxsteps < 32768 && lds_pairs <= 60 * 1024 && !g.sw.bcr_s_tiles)  // (the switch: the tile kernel for every closure count)
         hipLaunchKernelGGL((k_bcr_closure_S_pairs<B>), dim3((npad + 3) / 4, npad), dim3(256), lds_pairs, st, r, npad,
                            S.cl_maxsteps, S.cl_off.p, S.cl_step.p, S.cl_R.p, S.cl_W.p, S.far_e.p, g.bcr_wsrc, g.bcr_wsquare,
                            S.cl_S.p, S.cl_T.p, S.cl_alive.p);
@@ -2988,23 +2983,9 @@ static void bcr_launch_forward(hipStream_t st, const BcrClPlan &P, int r, int ns
     const size_t lds_wg = ((size_t)4 * B * (3 * B + 3) + (size_t)4 * (3 * B + 3) + (size_t)nslots * B) * sizeof(double);
     // (blocks of 32: 100 KB, one workgroup per CU -- the chip takes 256 closures at a time then)
     const int r_wg = lds_wg * 2 <= 150 * 1024 ? 400 : 256;
-    // EIGHT steps per round trip (eight waves, twice the stages: IROTAVG_BCR_FORWARD8=1) was built and measured in round 6:
-    // 50 us against 35.5 at thirty closures -- the steps are bound by their two barriers each (sixteen waves' worth with
-    // 512 threads), not by the round trips. Kept behind the switch as the record of that measurement.
-    constexpr int kForward8Max = 128;
-    const size_t lds_wg8 = ((size_t)8 * B * (3 * B + 3) + (size_t)4 * (3 * B + 3) + (size_t)nslots * B) * sizeof(double);
-    if (r <= kForward8Max && lds_wg8 <= 150 * 1024 && !getenv("IROTAVG_BCR_FORWARD_WAVE") && getenv("IROTAVG_BCR_FORWARD8")) {
-        static std::atomic<size_t> lds_set8[16];
-        if (lds_wg8 > 64 * 1024 && lds_set8[dev & 15].load() < lds_wg8) {
-            IRH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bcr_closure_forward<B, 8>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wg8));
-            lds_set8[dev & 15].store(lds_wg8);
-        }
-        hipLaunchKernelGGL((k_bcr_closure_forward<B, 8>), dim3(r), dim3(512), lds_wg8, st, P, r, nslots, off, steps, init, recR,
-                           recW, T, slot_init, fin, gid, dep, world, rank);
-        return;
-    }
-    if (r <= r_wg && lds_wg <= 150 * 1024 && !getenv("IROTAVG_BCR_FORWARD_WAVE")) {
+    // (EIGHT steps per round trip -- eight waves, twice the stages -- measured 50 us against 35.5 at thirty closures in
+    // round 6: the steps are bound by their two barriers each, not by the round trips. DESIGN.md 5b keeps the record.)
+    if (r <= r_wg && lds_wg <= 150 * 1024) {
         static std::atomic<size_t> lds_set[16];
         if (lds_wg > 64 * 1024 && lds_set[dev & 15].load() < lds_wg) {
             IRH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bcr_closure_forward<B>),
@@ -3346,12 +3327,11 @@ int bcr_stamps_up(Graph &g, double *out) {
     if (!g.bcr_B) return IROTAVG_ERR_BAD_ARG;
     bcr_alloc(g);
     BcrState &S = *g.bcr;
-    const char *wgs = getenv("IROTAVG_BCR_STAMP_CHUNK");
     struct DbgScope {
         BcrState &S;
         ~DbgScope() { S.dbg_word = -1; }
     } dbg_scope{S};
-    S.dbg_word = 128 + 256 * (wgs ? atoi(wgs) : 0);
+    S.dbg_word = 128 + 256 * g.sw.bcr_stamp_chunk;
     const size_t cnt = (size_t)std::max(S.lev[0].nch * 16, 32 * kUpLevels);
     if (!S.stamps.p) S.stamps.alloc(cnt);
     IRH_CHECK(hipMemsetAsync(S.stamps.p, 0, sizeof(long long) * cnt, g.stream));
@@ -3470,9 +3450,7 @@ void bcr_gate(Graph &g, double *flags_copy) {
     if (dead) S->dead_clean = true;  // (the gate kernel leaves the counter at zero)
     const double *part = nullptr;
     int grid = 0;
-    // (IROTAVG_BCR_NO_RESIDUAL_GATE: the dead-pivot gate alone, as until round 5)
-    static const bool no_res = getenv("IROTAVG_BCR_NO_RESIDUAL_GATE") != nullptr;
-    if (S && S->nfar > 0 && g.ng == 0 && !g.bcr_shard && !no_res) {
+    if (S && S->nfar > 0 && g.ng == 0 && !g.bcr_shard) {
         // A x by the iterative solver's SpMV (13 us at 2M edges; a row per thread walking its SELL row, k_bcr_residual,
         // took 45), then b - A x and the two norms in one small pass over the rows
         Level &L0 = g.levels[0];
@@ -3488,7 +3466,7 @@ void bcr_gate(Graph &g, double *flags_copy) {
     }
     // (IROTAVG_BCR_FAKE_GIVE_UP, tests: no residual passes the gate)
     const double gate = std::max(g.opt.pcg_rtol, kBcrGateTolMin);
-    const double tol = getenv("IROTAVG_BCR_FAKE_GIVE_UP") ? -1.0 : gate * gate;
+    const double tol = g.sw.bcr_fake_give_up ? -1.0 : gate * gate;
     int *skip_out = (S && flags_copy) ? const_cast<int *>(bcr_gate_skip_word(g)) : nullptr;
     hipLaunchKernelGGL(k_bcr_gate, dim3(1), dim3(256), 0, g.stream, dead, g.flags.p, part, grid, tol, skip_out,
                        reinterpret_cast<int *>(flags_copy));
@@ -3500,9 +3478,7 @@ int bcr_closures(Graph &g) { return g.bcr_B ? (int)g.bcr_far_e.size() : 0; }
 // back), or 0 when such a solve cannot make the step itself: closures, a shard, one level, more slots than the pinned block
 // has doubles for
 int bcr_apply_slots(Graph &g) {
-    if (!g.bcr_B || !g.bcr_far_e.empty() || g.bcr_shard || g.ng != 0 || getenv("IROTAVG_BCR_NO_FUSED_BACK") ||
-        getenv("IROTAVG_BCR_NO_APPLY"))
-        return 0;
+    if (!g.bcr_B || !g.bcr_far_e.empty() || g.bcr_shard || g.ng != 0) return 0;
     bcr_alloc(g);
     const BcrState &S = *g.bcr;
     if (S.lev.size() < 2 || S.nfar != 0) return 0;
@@ -3575,15 +3551,34 @@ bool bcr_band_part_anchored(int64_t m, int f, int64_t nu, int B, const int32_t *
     return true;
 }
 
-void bcr_plan(Graph &g, const int32_t *I) {
+// The two plans (edge list on the host: bcr_plan; on the device: bcr_plan_dev) differ in how they scan the edges, not in
+// what they decide. Before the scan: nothing is planned; false = this handle solves iteratively whatever its edges are.
+static bool bcr_plan_begin(Graph &g, int *mode) {
     g.bcr_B = 0;
     g.band0 = -1;
     g.bcr_far_i.clear();
     g.bcr_far_j.clear();
     g.bcr_far_e.clear();
-    int mode = g.opt.band_direct;
-    if (const char *e = std::getenv("IROTAVG_BAND_DIRECT")) mode = std::atoi(e);
-    if (mode < 0 || g.ng > 0 || g.no < 1) return;
+    *mode = g.sw.has_band_direct ? g.sw.band_direct : g.opt.band_direct;
+    return *mode >= 0 && g.ng == 0 && g.no >= 1;
+}
+// After the scan (band: widest span <= 32, bandall: widest span, nfar: spans > 32, all between free views): records the
+// half-bandwidth and returns the block size of the direct solver, or 0 = iterative
+static int bcr_plan_block(Graph &g, int mode, int band, int bandall, long long nfar) {
+    g.band0 = bandall;
+    // closures cost the direct path 0.06 ms + 0.55 us r + 0.15 ns r^2 per solve (forward eliminations, inversion of the
+    // r x r Woodbury system, its assembly; measured at r = 12 ... 1000), the iterative solver ~0.9 ms per solve at 3000
+    // views with loop edges and ~2.2 ms at 20k ... 100k: up to 2048 closures stay direct, up to 1024 on small graphs
+    if (nfar > (g.no < 8192 ? kBcrMaxFar / 2 : kBcrMaxFar)) return 0;
+    if (mode == 0 && g.no <= 2048) return 0;
+    // blocks of 8, 12, ... 32 rows: the smallest multiple of four that holds the band (a shard of a sharded sequence
+    // keeps 8 / 16 / 24 / 32: its range is a multiple of 192 rows, dist.hip)
+    return band <= 8 ? 8 : (band + 3) / 4 * 4;
+}
+
+void bcr_plan(Graph &g, const int32_t *I) {
+    int mode = 0;
+    if (!bcr_plan_begin(g, &mode)) return;
     const int f = g.f;
     std::atomic<int> band(0), bandall(0);
     std::atomic<long long> nfar(0);
@@ -3614,20 +3609,8 @@ void bcr_plan(Graph &g, const int32_t *I) {
         nfar += far;
     });
     if (bad.load()) return;
-    g.band0 = bandall.load();
-    // closures cost the direct path 0.06 ms + 0.55 us r + 0.15 ns r^2 per solve (forward eliminations, inversion of the
-    // r x r Woodbury system, its assembly; measured at r = 12 ... 1000), the iterative solver ~0.9 ms per solve at 3000
-    // views with loop edges and ~2.2 ms at 20k ... 100k: up to 2048 closures stay direct, up to 1024 on small graphs
-    if (nfar.load() > (g.no < 8192 ? kBcrMaxFar / 2 : kBcrMaxFar)) return;
-    if (mode == 0 && g.no <= 2048) return;
-    const int b0 = band.load();
-    // blocks of 8, 12, ... 32 rows: the smallest multiple of four that holds the band (a shard of a sharded sequence
-    // keeps 8 / 16 / 24 / 32: its range is a multiple of 192 rows, dist.hip); IROTAVG_BCR_BLOCK asks for a larger one
-    int B = b0 <= 8 ? 8 : (b0 + 3) / 4 * 4;
-    if (const char *e = std::getenv("IROTAVG_BCR_BLOCK")) {
-        const int want = std::atoi(e);
-        if (want >= B && want <= 32 && want % 4 == 0) B = want;
-    }
+    const int B = bcr_plan_block(g, mode, band.load(), bandall.load(), nfar.load());
+    if (!B) return;
     if (nfar.load() > 0) {
         // long-range edges = those whose endpoints lie in blocks that are not neighbours (an edge of more than 32
         // views between neighbouring blocks is part of the block tridiagonal operator as it is)
@@ -3639,7 +3622,7 @@ void bcr_plan(Graph &g, const int32_t *I) {
                 g.bcr_far_e.push_back((int)k);
             }
         }
-        bool refuse = !g.bcr_far_e.empty() && getenv("IROTAVG_BCR_NO_CLOSURES");
+        bool refuse = !g.bcr_far_e.empty() && g.sw.bcr_no_closures;
         if (!g.bcr_far_e.empty() && !refuse) {
             // The Woodbury correction needs the BAND part alone to be positive definite: every free view must be
             // tied to a fixed one through band edges. Sufficient and cheap: every view has a band edge to an earlier
@@ -3754,14 +3737,8 @@ __global__ __launch_bounds__(256) void k_plan_uncovered(int no, const uint8_t *_
 }  // namespace
 
 void bcr_plan_dev(Graph &g, const DevEdgeSrc &src) {
-    g.bcr_B = 0;
-    g.band0 = -1;
-    g.bcr_far_i.clear();
-    g.bcr_far_j.clear();
-    g.bcr_far_e.clear();
-    int mode = g.opt.band_direct;
-    if (const char *e = std::getenv("IROTAVG_BAND_DIRECT")) mode = std::atoi(e);
-    if (mode < 0 || g.ng > 0 || g.no < 1) return;
+    int mode = 0;
+    if (!bcr_plan_begin(g, &mode)) return;
     const int f = g.f;
     hipStream_t s = g.stream;
     int *h = reinterpret_cast<int *>(PinPool::get().take());
@@ -3778,16 +3755,9 @@ void bcr_plan_dev(Graph &g, const DevEdgeSrc &src) {
     IRH_CHECK(hipMemcpyAsync(h, out.p, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
     IRH_CHECK(hipStreamSynchronize(s));
     if (h[2]) return;
-    g.band0 = h[1];
     const long long nfar = (long long)*reinterpret_cast<unsigned long long *>(h + 4);
-    if (nfar > (g.no < 8192 ? kBcrMaxFar / 2 : kBcrMaxFar)) return;
-    if (mode == 0 && g.no <= 2048) return;
-    const int b0 = h[0];
-    int B = b0 <= 8 ? 8 : (b0 + 3) / 4 * 4;
-    if (const char *e = std::getenv("IROTAVG_BCR_BLOCK")) {
-        const int want = std::atoi(e);
-        if (want >= B && want <= 32 && want % 4 == 0) B = want;
-    }
+    const int B = bcr_plan_block(g, mode, h[0], h[1], nfar);
+    if (!B) return;
     if (nfar > 0) {
         DevBuf<int> fl;
         DevBuf<uint8_t> ok;
@@ -3802,7 +3772,7 @@ void bcr_plan_dev(Graph &g, const DevEdgeSrc &src) {
         const int nl = h[0], uncovered = h[1];
         if (nl > kBcrMaxFar) return;  // (cannot happen: nl <= nfar)
         if (nl > 0) {
-            if (uncovered > 0 || getenv("IROTAVG_BCR_NO_CLOSURES")) return;  // see bcr_plan: the band part must be SPD alone
+            if (uncovered > 0 || g.sw.bcr_no_closures) return;  // see bcr_plan: the band part must be SPD alone
             std::vector<int> hl((size_t)3 * kBcrMaxFar);
             IRH_CHECK(hipMemcpyAsync(hl.data(), fl.p, sizeof(int) * hl.size(), hipMemcpyDeviceToHost, s));
             IRH_CHECK(hipStreamSynchronize(s));

@@ -88,7 +88,7 @@ HierPlan plan_hierarchy(Graph &g, int n0, int64_t nnz0, bool far0) {
     HierPlan P;
     P.n.push_back(n0);
     const int max_levels = std::max(1, std::min(g.opt.mg_levels_max, (int)kMaxLevels));
-    const bool tune = getenv("IROTAVG_NO_SMALL_TUNING") == nullptr;
+    const bool tune = !g.sw.no_small_tuning;
     if (g.opt.mg_dense_max <= 0) {
         // The dense level is re-inverted whenever the weights move non-uniformly. For a band graph that is the
         // cheap banded inverse and rare; with loop closures it is the full Gauss-Jordan sweep (n/32 block
@@ -150,13 +150,12 @@ int build_graph(Graph &g, const int32_t *I, const double *QQ, int64_t ldqq) {
     // Patterns on the device (gbuild.hip) for a single-GPU graph that is large enough to fill it; on the host for
     // shards (ghost views) and small graphs (sliding windows that miss the single-kernel path: a few hundred
     // edges are built faster than a dozen launches are issued). IROTAVG_HOST_BUILD=1 / =0 force either.
-    const char *e = getenv("IROTAVG_HOST_BUILD");
-    const bool host = e ? atoi(e) != 0 : (g.ng > 0 || g.m < 20000);
+    const bool host = g.sw.host_build >= 0 ? g.sw.host_build != 0 : (g.ng > 0 || g.m < 20000);
     return host ? build_graph_host(g, I, QQ, ldqq) : build_graph_device(g, I, QQ, ldqq);
 }
 
 int build_graph_host(Graph &g, const int32_t *I, const double *QQ, int64_t ldqq) {
-    const bool timing = getenv("IROTAVG_BUILD_TIMING") != nullptr;
+    const bool timing = g.sw.build_timing;
     double tlast = now_seconds();
     auto lap = [&](const char *what) {
         if (!timing) return;
@@ -464,7 +463,7 @@ int build_graph_host(Graph &g, const int32_t *I, const double *QQ, int64_t ldqq)
             g.slot_eid.upload(seid, s);
             // k_assemble0w: per slice, the first edge of the run it stages in LDS = the lowest edge id
             // among the slice's near entries (a view sequence: the edges of the slice's first view)
-            g.asm_windowed = getenv("IROTAVG_ASM_CLASSIC") ? 0 : 1;
+            g.asm_windowed = g.sw.asm_classic ? 0 : 1;
             std::vector<int> te0((size_t)M.nsl, 0);
             if (g.asm_windowed) parallel_for(M.nsl, 256, [&](int64_t s0, int64_t s1, int) {
                 for (int sl = (int)s0; sl < (int)s1; sl++) {
@@ -613,8 +612,6 @@ int finish_build(Graph &g, const BuildTail &T) {
         // measured faster (1M/20M: 1.88 vs 1.70 G)
         const bool one_tile = (g.levels[0].n + 63) / 64 <= 4 * kMaxParts;
         g.cg2 = (band8 && one_tile && g.ndense > 0 && g.opt.pcg_classic != 1) ? 1 : 0;
-        g.dense32 = 0;  // tile slices of the coarse solve read the fp64 inverse; IROTAVG_CG2_FP32_DENSE=1: an fp32 copy
-        if (const char *e = getenv("IROTAVG_CG2_FP32_DENSE")) g.dense32 = atoi(e) == 1 ? 1 : 0;
         if (g.cg2) {
             g.b2p.alloc((size_t)3 * g.ndense_pad);
             g.b2p.zero(s);

@@ -180,10 +180,11 @@ int64_t irotavg_make_A(int n, int f, int64_t m, const int32_t *I, int64_t *colpt
 // ---------------------------------------------------------------------------------------------
 }  // extern "C"
 
-// the handle behind irotavg_graph_create; src != nullptr: the edge list lives on the device already (resident.hip)
-static int graph_create_impl(irotavg_graph **out, int64_t m, int64_t n_total, int f, const int32_t *I,
-                             const double *QQ, int64_t ldqq, const irotavg_options *opt, const DevEdgeSrc *src) {
-    if (!out || (!src && (!I || !QQ || ldqq < m)) || m <= 0 || n_total <= 0 || f < 0 || n_total - f < 1 ||
+// the handle behind irotavg_graph_create; src != nullptr: the edge list lives on the device already (resident.hip).
+// sw: the switches the handle lives under from here on -- the plan, the build and every solve read this copy
+int irh::graph_create(irotavg_graph **out, int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ,
+                      int64_t ldqq, const irotavg_options *opt, const DevEdgeSrc *src, const Switches &sw) {
+    if (!out || (src ? !src->I || !src->QQ : !I || !QQ || ldqq < m) || m <= 0 || n_total <= 0 || f < 0 || n_total - f < 1 ||
         n_total > 0x7fffffffLL)
         return IROTAVG_ERR_BAD_ARG;
     *out = nullptr;
@@ -192,6 +193,7 @@ static int graph_create_impl(irotavg_graph **out, int64_t m, int64_t n_total, in
     API_TRY
     h = new irotavg_graph();
     Graph &g = h->g;
+    g.sw = sw;
     if (opt)
         g.opt = *opt;
     else
@@ -210,7 +212,6 @@ static int graph_create_impl(irotavg_graph **out, int64_t m, int64_t n_total, in
     g.nu = (int)(n_total - f);
     g.ng = 0;
     g.no = g.nu;
-    if (const char *e = std::getenv("IROTAVG_STALE_SPREAD")) g.stale_spread = std::max(1.0, std::atof(e));  // experiments
     // a banded operator (+ a few loop closures) is solved directly (bcr.hip): level 0 is all such a handle needs
     // (no coarse patterns, no dense level: a third of the build)
     if (src)
@@ -240,20 +241,13 @@ static int graph_create_impl(irotavg_graph **out, int64_t m, int64_t n_total, in
     }
 }
 
-namespace irh {
-int graph_create_dev(irotavg_graph **out, int64_t m, int64_t n_total, int f, const DevEdgeSrc &src,
-                     const irotavg_options *opt) {
-    if (!src.I || !src.QQ) return IROTAVG_ERR_BAD_ARG;
-    return graph_create_impl(out, m, n_total, f, nullptr, nullptr, 0, opt, &src);
-}
-Graph &graph_of(irotavg_graph *h) { return h->g; }
-}  // namespace irh
+Graph &irh::graph_of(irotavg_graph *h) { return h->g; }
 
 extern "C" {
 
 int irotavg_graph_create(irotavg_graph **out, int64_t m, int64_t n_total, int f, const int32_t *I,
                          const double *QQ, int64_t ldqq, const irotavg_options *opt) {
-    return graph_create_impl(out, m, n_total, f, I, QQ, ldqq, opt, nullptr);
+    return graph_create(out, m, n_total, f, I, QQ, ldqq, opt, nullptr, read_switches());
 }
 
 // Device buffers of destroyed handles are cached for reuse (common.hpp, DevPool): hand them back.
@@ -268,7 +262,7 @@ int64_t irotavg_trim_memory(void) {
 
 void irotavg_graph_destroy(irotavg_graph *h) {
     if (!h) return;
-    const bool timing = std::getenv("IROTAVG_BUILD_TIMING") != nullptr;
+    const bool timing = h->g.sw.build_timing;
     double t0 = now_seconds();
     auto lap = [&](const char *what) {
         if (!timing) return;
@@ -608,9 +602,10 @@ struct OneShotKey {
     int64_t m = 0, n_total = 0, ldqq = 0;
     int f = 0, dev = -1;
     uint64_t hI = 0, hQQ = 0;
+    Switches sw;  // of this call: a kept handle serves it only if it was made under the same ones
     bool same(const OneShotKey &o) const {
         return I == o.I && QQ == o.QQ && m == o.m && n_total == o.n_total && ldqq == o.ldqq && f == o.f && dev == o.dev &&
-               hI == o.hI && hQQ == o.hQQ;
+               hI == o.hI && hQQ == o.hQQ && sw == o.sw;
     }
 };
 std::mutex g_os_mu;
@@ -622,8 +617,7 @@ std::atomic<int64_t> g_os_hits{0}, g_os_misses{0};
 bool oneshot_cache_on() {
     int e = g_os_enabled.load();
     if (e < 0) {
-        const char *v = std::getenv("IROTAVG_ONESHOT_CACHE");
-        e = (v && std::atoi(v) == 0) ? 0 : 1;
+        e = env_oneshot_cache() ? 1 : 0;
         g_os_enabled.store(e);
     }
     return e != 0;
@@ -715,26 +709,29 @@ int oneshot_open(irotavg_graph **h, OneShotKey *key, bool *cached, int64_t m, in
     *cached = oneshot_cache_on() && I && QQ && m > 0 && ldqq >= m && irotavg_device_count() > 0;
     *h = nullptr;
     if (hit) *hit = false;
+    const Switches sw = read_switches();  // once per one-shot call: part of the key, and what a new handle is made under
     if (*cached) {
         *key = oneshot_key(m, n_total, f, I, QQ, ldqq);
+        key->sw = sw;
         *h = oneshot_take(*key);
         if (*h) {
             if (hit) *hit = true;
             return IROTAVG_OK;
         }
     }
-    return irotavg_graph_create(h, m, n_total, f, I, QQ, ldqq, nullptr);
+    return graph_create(h, m, n_total, f, I, QQ, ldqq, nullptr, nullptr, sw);
 }
 // A call that failed with a device or memory error on a KEPT handle (one that a device reset invalidated, or whose
 // pinned buffers are what the new work could not allocate next to) would have succeeded before handles were kept: the
 // kept one is destroyed, the pools are trimmed and the call gets ONE more attempt on a fresh handle (advisor, round 5).
 bool oneshot_retry_fresh(irotavg_graph **h, bool hit, int rc, int64_t m, int64_t n_total, int f, const int32_t *I,
                          const double *QQ, int64_t ldqq) {
-    if (!hit || (rc != IROTAVG_ERR_HIP && rc != IROTAVG_ERR_NOMEM)) return false;
-    if (*h) irotavg_graph_destroy(*h);
+    if (!hit || !*h || (rc != IROTAVG_ERR_HIP && rc != IROTAVG_ERR_NOMEM)) return false;
+    const Switches sw = (*h)->g.sw;
+    irotavg_graph_destroy(*h);
     *h = nullptr;
     (void)irotavg_trim_memory();
-    return irotavg_graph_create(h, m, n_total, f, I, QQ, ldqq, nullptr) == IROTAVG_OK;
+    return graph_create(h, m, n_total, f, I, QQ, ldqq, nullptr, nullptr, sw) == IROTAVG_OK;
 }
 // the handle of a failed one-shot call replaced by one that solves iteratively (band_direct = -1) -- when the failed one
 // was a direct-solver handle with loop closures; false: nothing to retry with
@@ -745,7 +742,7 @@ bool oneshot_retry_iterative(irotavg_graph **h, int64_t m, int64_t n_total, int 
     irotavg_default_options(&opt);
     opt.band_direct = -1;
     irotavg_graph *it = nullptr;
-    if (irotavg_graph_create(&it, m, n_total, f, I, QQ, ldqq, &opt) != IROTAVG_OK) return false;
+    if (graph_create(&it, m, n_total, f, I, QQ, ldqq, &opt, nullptr, (*h)->g.sw) != IROTAVG_OK) return false;
     irotavg_graph_destroy(*h);
     *h = it;
     return true;
@@ -779,7 +776,7 @@ int irotavg_irls(int64_t m, int64_t n_total, int f, const int32_t *I, const doub
                  double change_th, double *weights, int *iters, double *runtime) {
     if (!Q || !weights || !iters || !runtime) return IROTAVG_ERR_BAD_ARG;
     if (cost < IROTAVG_L2 || cost > IROTAVG_WELSCH) return IROTAVG_ERR_UNKNOWN_COST;
-    const bool timing = std::getenv("IROTAVG_BUILD_TIMING") != nullptr;
+    bool timing = false;  // the handle's build_timing switch, once there is a handle
     double t0 = now_seconds();
     auto lap = [&](const char *what) {
         if (!timing) return;
@@ -792,6 +789,7 @@ int irotavg_irls(int64_t m, int64_t n_total, int f, const int32_t *I, const doub
     bool cached = false, hit = false;
     int rc = oneshot_open(&h, &key, &cached, m, n_total, f, I, QQ, ldqq, &hit);
     if (rc != IROTAVG_OK) return rc;
+    timing = h->g.sw.build_timing;
     lap("handle (kept or created)");
     for (int attempt = 0; attempt < 2; attempt++) {
         rc = irotavg_graph_set_rotations(h, Q, ldq);

@@ -632,14 +632,11 @@ Cg2Bufs cg2_bufs(Graph &g) {
 }  // namespace
 
 // workgroups of the two kernels: 4 slices each (3 for some, so that the count is a multiple of 8), at
-// most kMaxParts partials. IROTAVG_CG2_SLICES=3 deals ~3 slices per workgroup (512 workgroups at 100k
-// views: every CU hosts two) -- measured 1 us per iteration SLOWER: a CU's two workgroups then each
-// carry the per-tile overhead (8 rows of the dense inverse, the level-2 right-hand side).
+// most kMaxParts partials. (~3 slices per workgroup -- 512 workgroups at 100k views, every CU hosts two --
+// measured 1 us per iteration SLOWER: a CU's two workgroups then each carry the per-tile overhead, 8 rows
+// of the dense inverse and the level-2 right-hand side.)
 int cg2_grid(const Level &L0) {
-    static const int per = [] {
-        const char *e = std::getenv("IROTAVG_CG2_SLICES");
-        return e ? std::min(4, std::max(1, std::atoi(e))) : 4;
-    }();
+    constexpr int per = 4;
     long long gsz = (L0.nsl + per - 1) / per;
     gsz = (gsz + 7) & ~7ll;
     gsz = std::min<long long>(gsz, kMaxParts);
@@ -682,29 +679,13 @@ void cg2_launch_apply(Graph &g, int first, int rcur, double rtol2, long long *db
                        (const double4 *)nullptr, EP, g.ndense, g.ndense_pad, g.dense_scale, dev_scale ? 1 : 0, g.opt.mg_omega, \
                        g.opt.mg_kc, g.part_rz.p, g.part_pq.p, g.part_rr.p, grid, first, rtol2, g.scal.p,        \
                        g.flags.p, dbg)
-        if (g.dense32) {
-            // the fp32 copy of the inverse (cg2_refresh_inv32): NJ = ceil(npad / 256) 16-byte steps per lane;
-            // next to it the lane's whole matrix row fits in registers (band graph: 5 batches of 8 entries)
-            const float *E = g.dense_inv32.p;
-            if (L0.max_near <= 40) {
-                if (g.ndense_pad <= 1024)
-                    CG_APPLY2(float, E, 4, 5);
-                else if (g.ndense_pad <= 1792)
-                    CG_APPLY2(float, E, 7, 5);
-                else
-                    CG_APPLY2(float, E, 8, 5);
-            } else {
-                CG_APPLY2(float, E, 8, 0);
-            }
-        } else {  // fp64 slices (default): NJ = ceil(npad / 128)
-            const double *E = g.dense_inv.p;
-            if (g.ndense_pad <= 1024)
-                CG_APPLY2(double, E, 8, 0);
-            else if (g.ndense_pad <= 1664)
-                CG_APPLY2(double, E, 13, 0);
-            else
-                CG_APPLY2(double, E, 16, 0);
-        }
+        const double *E = g.dense_inv.p;  // fp64 slices of the inverse: NJ = ceil(npad / 128)
+        if (g.ndense_pad <= 1024)
+            CG_APPLY2(double, E, 8, 0);
+        else if (g.ndense_pad <= 1664)
+            CG_APPLY2(double, E, 13, 0);
+        else
+            CG_APPLY2(double, E, 16, 0);
 #undef CG_APPLY2
     } else {
         // level 2 has levels below it: its correction comes from the generic cycle (solver.hip)
@@ -717,30 +698,10 @@ void cg2_launch_apply(Graph &g, int first, int rcur, double rtol2, long long *db
     }
 }
 
-// fp32 copy of the explicit inverse of the dense level for k_cg_apply: the coarse correction is a
-// preconditioner component, its rounding (6e-8 relative) does not touch the accuracy of the solve,
-// and half the bytes is half the registers a tile slice occupies while it is in flight.
-__global__ __launch_bounds__(256) void k_inv_to_f32(long long n, const double *__restrict__ a, float *__restrict__ b) {
-    const long long i = 2 * ((long long)blockIdx.x * blockDim.x + threadIdx.x);
-    if (i < n) {
-        const double2 v = *reinterpret_cast<const double2 *>(a + i);
-        *reinterpret_cast<float2 *>(b + i) = make_float2((float)v.x, (float)v.y);
-    }
-}
-static void cg2_refresh_inv32(Graph &g) {
-    if (!g.dense32 || g.inv32_epoch == g.dense_epoch) return;
-    const long long n = (long long)g.ndense_pad * g.ndense_pad;
-    if (g.dense_inv32.n < (size_t)n) g.dense_inv32.alloc((size_t)n);
-    hipLaunchKernelGGL(k_inv_to_f32, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, g.stream, n, g.dense_inv.p,
-                       g.dense_inv32.p);
-    g.inv32_epoch = g.dense_epoch;
-}
-
 // PCG on L X = levels[0].b (three columns), two launches per iteration. Same contract as pcg_solve.
 int pcg_solve_cg2(Graph &g, const std::function<void()> *tail, bool *tail_ran, bool device_scale) {
     if (tail_ran) *tail_ran = false;
     const double rtol2 = g.opt.pcg_rtol * g.opt.pcg_rtol;
-    if (g.levels.size() == 3) cg2_refresh_inv32(g);
     // k_cg_update<0> clears FL_DONE / FL_ITERS (not FL_STALE) and keeps a copy of the right-hand side in
     // levels[0].x (the residual ping-pongs through its buffer): a speculative solve may be handed back
     // (run_irls), and a system on which the Chronopoulos-Gear recurrences stall is solved again by the classic ones
@@ -789,7 +750,7 @@ int pcg_solve_cg2(Graph &g, const std::function<void()> *tail, bool *tail_ran, b
         first_poll = false;
         if (h_flags[FL_DONE] != 0) break;
         const double cur = std::max(h_scal[SC_RELRES], std::max(h_scal[SC_RELRES + 1], h_scal[SC_RELRES + 2]));
-        if (std::getenv("IROTAVG_PCG_TRACE") && (it < 80 || it % 100 < 4))
+        if (g.sw.pcg_trace && (it < 80 || it % 100 < 4))
             std::fprintf(stderr, "[pcg cg2]   it %d relres %.3e %.3e %.3e alpha %.3e %.3e gamma %.3e\n", it, h_scal[SC_RELRES],
                          h_scal[SC_RELRES + 1], h_scal[SC_RELRES + 2], h_scal[SC_ALF0], h_scal[SC_ALF1], h_scal[SC_GAM0]);
         if (cur < 0.5 * best) {
@@ -800,13 +761,12 @@ int pcg_solve_cg2(Graph &g, const std::function<void()> *tail, bool *tail_ran, b
             break;
         }
         if (it >= maxit) break;
-        const char *ge = std::getenv("IROTAVG_CG2_GIVEUP");  // tests force the hand-over
-        const int giveup = ge ? std::max(1, std::atoi(ge)) : kCg2GiveUp;
+        const int giveup = g.sw.cg2_giveup > 0 ? g.sw.cg2_giveup : kCg2GiveUp;  // tests force the hand-over
         if (it >= giveup) {
             // s = L p and r are carried by recurrences here; on a badly conditioned system their rounding
             // can stall the iteration far above the tolerance. The classic recurrences (one more launch
             // per iteration, q = L p computed) are the robust path: start over with them.
-            if (std::getenv("IROTAVG_PCG_TRACE")) std::fprintf(stderr, "[pcg cg2] giving up at %d iterations -> classic\n", it);
+            if (g.sw.pcg_trace) std::fprintf(stderr, "[pcg cg2] giving up at %d iterations -> classic\n", it);
             g.stats.pcg_iters += it;
             g.stats.pcg_handed_over += 1;
             // the classic launches take the scale of a re-used inverse from the host copy; in device_scale
@@ -822,7 +782,7 @@ int pcg_solve_cg2(Graph &g, const std::function<void()> *tail, bool *tail_ran, b
     g.stats.pcg_iters += stagnated ? it : h_flags[FL_ITERS];
     g.stats.pcg_iters_last = stagnated ? it : h_flags[FL_ITERS];
     for (int c = 0; c < 3; c++) g.stats.last_relres[c] = h_scal[SC_RELRES + c];
-    if (std::getenv("IROTAVG_PCG_TRACE"))
+    if (g.sw.pcg_trace)
         std::fprintf(stderr, "[pcg cg2] clone %d iters %d enqueued %d\n", g.is_clone ? 1 : 0, h_flags[FL_ITERS], it);
     if (h_flags[FL_DONE] == 2) return IROTAVG_ERR_SOLVER;
     if (stagnated) {
@@ -836,7 +796,6 @@ int pcg_solve_cg2(Graph &g, const std::function<void()> *tail, bool *tail_ran, b
 // kernel timing for bench.py's roofline leg (time_kernel, solver.hip): one launch of each kernel in
 // its steady-state form on whatever the buffers hold
 void cg2_time_once(Graph &g, int which) {
-    if (g.levels.size() == 3) cg2_refresh_inv32(g);
     if (which == 0)
         cg2_launch_apply(g, 0, 0, -1.0);
     else
@@ -844,14 +803,13 @@ void cg2_time_once(Graph &g, int which) {
 }
 
 // development aid: wall-clock stamps (100 MHz) of the phases of k_cg_apply in one mid-grid workgroup;
-// out[k] = microseconds from kernel entry to stamp k (IROTAVG_CG2_STAMPS, tools/)
+// out[k] = microseconds from kernel entry to stamp k (time_kernel 100 + k)
 int cg2_phase_stamps(Graph &g, double *out, int n) {
     DevBuf<long long> d;
     d.alloc(16);
     IRH_CHECK(hipMemsetAsync(d.p, 0, sizeof(long long) * 16, g.stream));
     IRH_CHECK(hipMemsetAsync(d.p + 12, 0xff, sizeof(long long), g.stream));  // atomicMin target
     IRH_CHECK(hipMemsetAsync(g.flags.p, 0, sizeof(int) * FL_COUNT, g.stream));
-    if (g.levels.size() == 3) cg2_refresh_inv32(g);
     for (int r = 0; r < 3; r++) {
         if (r == 2) {  // the grid-span slots refer to the last launch only
             IRH_CHECK(hipMemsetAsync(d.p + 12, 0xff, sizeof(long long), g.stream));

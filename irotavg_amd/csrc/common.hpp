@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/irotavg_hip.h"
+#include "switches.hpp"
 
 namespace irh {
 
@@ -53,7 +54,7 @@ struct DevPool {
     size_t cached = 0, limit = (size_t)16384 << 20;
     uint64_t epoch = 0;  // advances with every release
     DevPool() {
-        if (const char *e = std::getenv("IROTAVG_POOL_LIMIT_MB")) limit = (size_t)std::strtoull(e, nullptr, 10) << 20;
+        if (const char *e = env_pool_limit_mb()) limit = (size_t)std::strtoull(e, nullptr, 10) << 20;
     }
     static DevPool &get() {
         static DevPool *pool = new DevPool();  // never destroyed: no hipFree after runtime teardown
@@ -265,7 +266,7 @@ struct PinPool {
         void *p = nullptr;
         // mapped + coherent (fine-grained): a kernel may store into the block and the host may poll it while the
         // kernel's stream is still busy (publish_parts / wait_published, solver.hip)
-        static const bool plain = std::getenv("IROTAVG_PIN_DEFAULT") != nullptr;  // experiments (with IROTAVG_NO_POLL=1)
+        static const bool plain = env_pin_default();  // experiments (with the no-poll switch)
         IRH_CHECK(hipHostMalloc(&p, kBytes, plain ? hipHostMallocDefault : (hipHostMallocMapped | hipHostMallocCoherent)));
         std::memset(p, 0, kBytes);
         return p;
@@ -558,8 +559,7 @@ inline void parallel_for(int64_t n, int64_t min_chunk, F &&fn) {
         return;
     }
     static const unsigned hw = std::thread::hardware_concurrency();
-    const char *fe = getenv("IROTAVG_BUILD_THREADS");  // read every time: the thread-count test changes it
-    const int forced = fe ? std::min(16, std::max(1, atoi(fe))) : 0;
+    const int forced = env_build_threads();  // read every time: the thread-count test changes it
     int T = (int)std::min<int64_t>(std::max(1u, std::min(hw, 16u)), std::max<int64_t>(1, n / std::max<int64_t>(1, min_chunk)));
     if (forced) T = forced;
     if (T <= 1) {
@@ -571,7 +571,7 @@ inline void parallel_for(int64_t n, int64_t min_chunk, F &&fn) {
         const int64_t b = std::min(n, t * step), e = std::min(n, b + step);
         if (b < e) fn(b, e, t);
     };
-    if (!getenv("IROTAVG_NO_HOST_POOL") && HostPool::get().run(T, chunk)) return;
+    if (HostPool::get().run(T, chunk)) return;
     std::vector<std::thread> th;
     for (int t = 1; t < T; t++) th.emplace_back([&chunk, t]() { chunk(t); });
     chunk(0);

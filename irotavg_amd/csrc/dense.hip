@@ -732,7 +732,6 @@ static bool dense_lowrank_repair(Graph &g, double c) {
     hipLaunchKernelGGL(k_wb_ref_diag, dim3(1), dim3(1024), 0, g.stream, C.n, r, c, list, g.dense_ref_diag.p);
     IRH_CHECK(hipStreamSynchronize(g.stream));  // hSinv / hl leave scope
     g.dense_scale = 1.0;
-    g.dense_epoch++;  // dense_inv changed: copies of it (cgcg.hip) are stale
     g.stats.dense_repairs++;
     return true;
 }
@@ -874,7 +873,6 @@ void dense_select_slot(Graph &g, int slot) {
     }
     exchange(T);
     g.dense_slot = slot;
-    g.dense_epoch++;
 }
 
 // ---- last resort for a small single-level system: dense Cholesky + iterative refinement -----------------
@@ -1227,7 +1225,6 @@ static void band_inverse_launch(Graph &g, const LevelView &V) {
 
 void dense_refresh(Graph &g) {
     if (g.ndense <= 0) return;
-    g.dense_epoch++;
     g.dense_scale = 1.0;
     g.dense_repairs_in_a_row = 0;
     g.stats.dense_inversions++;
@@ -1245,7 +1242,7 @@ void dense_refresh(Graph &g) {
     const int npad = g.ndense_pad;
     LevelView V{C.n, C.nsl, C.agg, C.sl_off.p, C.sl_near.p, C.col.p, C.val.p, C.diag.p, C.idg.p};
     IRH_CHECK(hipMemsetAsync(g.dense_inv.p, 0, sizeof(double) * (size_t)npad * npad, g.stream));
-    if (g.dense_bw >= 1 && g.dense_bw <= kBandMax && !std::getenv("IROTAVG_NO_BAND_INVERSE")) {
+    if (g.dense_bw >= 1 && g.dense_bw <= kBandMax && !g.sw.no_band_inverse) {
         switch (g.dense_bw) {
         case 1: band_inverse_launch<1>(g, V); break;
         case 2: band_inverse_launch<2>(g, V); break;
@@ -1263,7 +1260,7 @@ void dense_refresh(Graph &g) {
         hipLaunchKernelGGL(k_dense_build, dim3((npad + kRowBlock - 1) / kRowBlock), dim3(kRowBlock), 0,
                            g.stream, V, npad, g.dense_inv.p, g.dense_maxdiag.p);
     const int nchunk = npad / GJT;
-    if (nchunk < 2 || std::getenv("IROTAVG_GJ_NO_LOOKAHEAD")) {
+    if (nchunk < 2) {
         for (int k0 = 0; k0 < npad; k0 += GJB) {
             hipLaunchKernelGGL(k_gj_panel, dim3(2 * nchunk), dim3(256), 0, g.stream, npad, k0,
                                g.dense_inv.p, g.dense_wr.p, g.dense_wc.p, g.dense_maxdiag.p);

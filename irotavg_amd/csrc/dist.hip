@@ -56,6 +56,7 @@ struct Dist {
     std::vector<double> hbuf, hbuf2;  // host staging of the hosted transport
     hipStream_t stream = nullptr;
     irotavg_options opt{};
+    Switches sw;  // read once in the create function; every shard's Graph gets this copy
     irotavg_stats stats{};
     // A view sequence (round 5: also with up to 2048 loop closures, cl_edge below) is solved DIRECTLY also when it is
     // sharded (bcr.hip): every rank
@@ -458,6 +459,7 @@ static int build_shard(Dist &D, Shard &S, const int32_t *I, const double *QQ, in
     }
     Graph &g = S.g;
     g.opt = D.opt;
+    g.sw = D.sw;
     g.opt.no_fused_pspmv = 1;  // the sharded PCG exchanges p between its p-update and its SpMV
     g.stream = D.stream;
     g.m = ml;
@@ -707,8 +709,7 @@ static int pcg_dist_cg(Dist &D) {
     // iterations, or when the residual has not halved for kStall iterations, the solve restarts with the
     // classic sharded recurrences from the saved right-hand side. The decision is taken from all-reduced
     // values (flags and relative residual are identical on every rank), so all ranks agree.
-    const char *ge = std::getenv("IROTAVG_CG2_GIVEUP");  // tests force the hand-over
-    const int giveup = ge ? std::max(1, std::atoi(ge)) : 400;
+    const int giveup = D.sw.cg2_giveup > 0 ? D.sw.cg2_giveup : 400;  // tests force the hand-over
     constexpr int kStall = 96;
     double best = HUGE_VAL;
     int best_it = 0;
@@ -895,9 +896,7 @@ __global__ __launch_bounds__(kRowBlock) void k_dot3(int n, const double4 *__rest
 // as many iterations. Host-driven (a rare path): three sums per iteration, combined over the processes.
 static int bcr_dist_checked(Dist &D) {
     int rc = bcr_dist(D);
-    static const bool no_res = std::getenv("IROTAVG_BCR_NO_RESIDUAL_GATE") != nullptr;
-    static const bool dbg = std::getenv("IROTAVG_DIST_DEBUG") != nullptr;
-    if (D.top.r == 0 || no_res) return rc;
+    if (D.top.r == 0) return rc;
     // (the preconditioner applications of the repair below are not linear systems of the caller's: direct_solves counts
     // this call once, as run_irls does on one GPU -- advisor, round 5)
     struct GuardOff {
@@ -971,7 +970,6 @@ static int bcr_dist_checked(Dist &D) {
             D.stats.last_relres[c] = rel;
             worst = std::max(worst, rel);
         }
-        if (dbg) std::fprintf(stderr, "[bcr_dist_checked] relres of the direct solve %.3e\n", worst);
         if (!(worst > std::max(D.opt.pcg_rtol, 1e-12))) return IROTAVG_OK;  // (the gate of the single-GPU handle: pcg_rtol)
         if (!std::isfinite(worst)) return IROTAVG_ERR_SOLVER;
     }
@@ -1034,8 +1032,6 @@ static int bcr_dist_checked(Dist &D) {
             D.stats.last_relres[c] = rel;
             worst = std::max(worst, rel);
         }
-        if (dbg) std::fprintf(stderr, "[bcr_dist_checked] cg %d relres %.3e (dead pivots %lld)\n", it + 1, worst,
-                              (long long)D.stats.direct_dead_pivots);
         if (!(worst > rtol) || !std::isfinite(worst) || it + 1 >= maxit) break;
     }
     // the solution where the callers read it, the right-hand side back
@@ -1203,6 +1199,7 @@ static int dist_create_impl(irotavg_dist **out, int world, int rank, const void 
         if (D.opt.mg_levels_max <= 0) D.opt.mg_levels_max = 16;
         if (D.opt.pcg_max_iters <= 0) D.opt.pcg_max_iters = 2000;
         if (D.opt.pcg_check_every <= 0) D.opt.pcg_check_every = 8;
+        D.sw = read_switches();
         if (D.opt.device >= 0) IRH_CHECK(hipSetDevice(D.opt.device));
         D.stream = StreamPool::get().take();
         D.world = world;
@@ -1211,8 +1208,7 @@ static int dist_create_impl(irotavg_dist **out, int world, int rank, const void 
         D.f = f;
         D.nu = n_total - f;
         {   // the direct solver for a sharded view sequence? Decided from the GLOBAL graph: every process agrees.
-            int mode = D.opt.band_direct;
-            if (const char *e = std::getenv("IROTAVG_BAND_DIRECT")) mode = std::atoi(e);
+            const int mode = D.sw.has_band_direct ? D.sw.band_direct : D.opt.band_direct;
             int band = 0, bandall = 0;
             int64_t nfar = 0;
             bool ok = mode >= 0 && world <= 8;
@@ -1228,7 +1224,7 @@ static int dist_create_impl(irotavg_dist **out, int world, int rank, const void 
             }
             D.band0 = ok ? bandall : -1;
             // (the limits of the single-GPU plan, bcr_plan: at most 2048 long-range edges, 1024 on small graphs)
-            const bool closures_ok = !std::getenv("IROTAVG_BCR_NO_CLOSURES") && !std::getenv("IROTAVG_DIST_NO_CLOSURES");
+            const bool closures_ok = !D.sw.bcr_no_closures && !D.sw.dist_no_closures;
             if (ok && nfar > 0 && (!closures_ok || nfar > (D.nu < 8192 ? 1024 : 2048))) ok = false;
             if (ok && (mode > 0 || D.nu > 2048)) {
                 const int B = band <= 8 ? 8 : band <= 16 ? 16 : band <= 24 ? 24 : 32;
@@ -1288,7 +1284,7 @@ static int dist_create_impl(irotavg_dist **out, int world, int rank, const void 
         // the gathered halo of a closure-free sequence (Dist::halo_gather): decided from what EVERY process derives alike
         // (the global plan above), then checked against this process's own shards -- a rank whose halo does not have the
         // promised shape fails loudly here instead of disagreeing with the others about the wire
-        if (D.bcr_B && D.cl_edge.empty() && !D.hosted && world > 1 && !std::getenv("IROTAVG_DIST_HALO_P2P")) {
+        if (D.bcr_B && D.cl_edge.empty() && !D.hosted && world > 1 && !D.sw.dist_halo_p2p) {
             D.halo_gather = true;
             D.halo_w = D.bcr_B;
             D.hall.alloc((size_t)world * 2 * D.halo_w);

@@ -455,7 +455,7 @@ void sell_map_device(Graph &g, Scratch &S, const DevCsr &A, DevSell &M, int *h_i
 }  // namespace
 
 int build_graph_device(Graph &g, const int32_t *I, const double *QQ, int64_t ldqq, const DevEdgeSrc *src) {
-    const bool timing = getenv("IROTAVG_BUILD_TIMING") != nullptr;
+    const bool timing = g.sw.build_timing;
     double tlast = now_seconds();
     auto lap = [&](const char *what) {
         if (!timing) return;
@@ -503,8 +503,7 @@ int build_graph_device(Graph &g, const int32_t *I, const double *QQ, int64_t ldq
         }
         ~QQUpload() { join(); }
     } qq_up;
-    const char *upenv = getenv("IROTAVG_UPLOAD_THREADS");
-    const int n_up = (m >= 100000 && !src) ? (upenv ? std::min(4, std::max(0, atoi(upenv))) : 4) : 0;
+    const int n_up = (m >= 100000 && !src) ? g.sw.upload_threads : 0;
     if (src) {
     } else if (n_up > 0) {
         double *dst = g.qq.p;
@@ -618,7 +617,7 @@ int build_graph_device(Graph &g, const int32_t *I, const double *QQ, int64_t ldq
     g.levels.clear();
     g.levels.resize(nlev);
     g.stats.levels = (int)nlev;
-    g.asm_windowed = getenv("IROTAVG_ASM_CLASSIC") ? 0 : 1;
+    g.asm_windowed = g.sw.asm_classic ? 0 : 1;
     g.asm_l1_fused = 0;
     BuildTail T;
     T.nlev = (int)nlev;

@@ -24,6 +24,7 @@ struct Graph {
     // of X), no = owned views = rows of the operator.
     int f = 0, nu = 0, ng = 0, no = 0;
     irotavg_options opt{};
+    Switches sw;  // the environment's switches as they were when the handle was made (switches.hpp)
     hipStream_t stream = nullptr;
     int device = 0;
 
@@ -41,7 +42,7 @@ struct Graph {
     // level-0 adjacency extras (CSR itself lives in levels[0])
     DevBuf<uint8_t> slot_cs;    // per level-0 SELL position: entry index in the level-1 row it sums into (255: none)
     DevBuf<int> tile_e0;        // per level-0 slice: first edge of the window k_assemble0w stages in LDS
-    int asm_windowed = 1;       // K3 by k_assemble0w (IROTAVG_ASM_CLASSIC=1: edge_pack + assemble0 + coarse kernels)
+    int asm_windowed = 1;       // K3 by k_assemble0w (Switches::asm_classic: edge_pack + assemble0 + coarse kernels)
     int asm_l1_fused = 0;       // ... which also refreshes level 1 (aggregates of 8, level-1 rows of <= 8 entries)
     DevBuf<uint32_t> slot_eid;  // SELL layout of level 0: (edge id << 1) | (row is the j endpoint); ~0u = padding
     DevBuf<int> bptr;           // per row: boundary slots (other endpoint fixed / self loop)
@@ -53,10 +54,6 @@ struct Graph {
 
     std::vector<Level> levels;
     DevBuf<double> dense_inv;  // explicit inverse of the coarsest level, ndense_pad^2 row-major
-    DevBuf<float> dense_inv32;  // fp32 copy for the tile slices of k_cg_apply (cgcg.hip), refreshed lazily
-    uint64_t dense_epoch = 1, inv32_epoch = 0;  // dense_epoch advances whenever dense_inv's content changes
-    int dense32 = 0;            // 1: k_cg_apply reads an fp32 copy of the inverse (IROTAVG_CG2_FP32_DENSE=1; measured
-                                // 2-3 % faster, not worth a preconditioner whose definiteness rests on fp32 rounding)
     DevBuf<double> dense_wr, dense_wc;  // Gauss-Jordan panels (32 x npad, npad x 32), two of each
     DevBuf<double> dense_chol;          // scratch of dense_direct_solve: the operator twice (factor, copy)
     DevBuf<double> dense_wb;            // scratch of the low-rank repair (Z, W, S, S^-1, entry list)
@@ -278,7 +275,7 @@ int cg2_phase_stamps(Graph &g, double *out, int n);
 void cycle_levels(Graph &g, int from);  // solver.hip: levels[from].b/.x -> levels[from].y
 // window.hip: single-kernel solve of small (sliding-window) problems
 struct WindowSolver;
-WindowSolver *window_solver_new();
+WindowSolver *window_solver_new(const Switches &sw);
 void window_solver_delete(WindowSolver *w);
 bool window_fits(int nv, int f, int ne);
 int window_solve(WindowSolver &ws, int nv, int f, int ne, const int32_t *I, const double *QQ_aos,
@@ -375,9 +372,10 @@ void dense_apply(Graph &g, const double4 *b, double4 *y, bool check, bool dot, d
 }  // namespace irh
 struct irotavg_graph;
 namespace irh {
-// capi.cpp: a handle built from an edge list on the device; the Graph behind a handle
-int graph_create_dev(irotavg_graph **out, int64_t m, int64_t n_total, int f, const DevEdgeSrc &src,
-                     const irotavg_options *opt);
+// capi.cpp: irotavg_graph_create under the switches of whoever makes the handle (src != nullptr: from an edge list on the
+// device instead of I / QQ); the Graph behind a handle
+int graph_create(irotavg_graph **out, int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq,
+                 const irotavg_options *opt, const DevEdgeSrc *src, const Switches &sw);
 Graph &graph_of(irotavg_graph *h);
 
 // resident.hip: the device-resident, growing copy of a view-graph behind rot_avg's global re-solves
@@ -396,8 +394,8 @@ long resident_views(const Resident &r);  // views / edges the device holds
 long resident_edges(const Resident &r);
 ResidentStage resident_stage(Resident &r, long n_views, long view_lo, long n_edges, long edge_lo);
 int resident_rot_avg(Resident &r, long n_views, long view_lo, long n_edges, long edge_lo, int f,
-                     const irotavg_options &opt, irotavg_rotavg_info &loc, bool timing, bool dry = false, int dry_a = -1,
-                     int dry_b = -1);
+                     const irotavg_options &opt, const Switches &sw, irotavg_rotavg_info &loc, bool timing, bool dry = false,
+                     int dry_a = -1, int dry_b = -1);
 
 inline double now_seconds() {
     using namespace std::chrono;

@@ -251,30 +251,10 @@ __device__ __forceinline__ double at_row(int row, int n, const int *__restrict__
     for (int t_ = t0_; t_ < t1_; t_++)                         \
         if (const int sl_ = t_ * 4 + (threadIdx.x >> 6); sl_ < (nsl))
 
-// out = A' t, partial sum of out^2
-__global__ __launch_bounds__(kRowBlock) void k_at_mul(int n, int nsl, const int *__restrict__ sl_off,
-                                                      const uint32_t *__restrict__ slot_eid,
-                                                      const int *__restrict__ bptr,
-                                                      const uint32_t *__restrict__ beid,
-                                                      const uint8_t *__restrict__ bflag,
-                                                      const double *__restrict__ t,
-                                                      double *__restrict__ out,
-                                                      double *__restrict__ part) {
-    double acc = 0.0;
-    PD_ROW_LOOP(nsl) {
-        const int row = sl_ * 64 + (threadIdx.x & 63);
-        const double s = at_row(row, n, sl_off, slot_eid, bptr, beid, bflag, t);
-        if (row < n) {
-            out[row] = s;
-            acc += s * s;
-        }
-    }
-    block_sum3_store(acc, 0.0, 0.0, part + 4 * blockIdx.x);
-}
-
-// The same product with the entries of a slice dealt to the FOUR waves of the workgroup (round 4). k_at_mul keeps one
-// lane per row and walks its ~40 entries in batches of eight behind dependent loads (slot id -> edge value): with ~390
-// workgroups that is six waves per CU and five serial round trips of ~2 us, 41 us under l1ra's three chains for 32 MB.
+// out = A' t, partial sum of out^2: the entries of a slice dealt to the FOUR waves of the workgroup (round 4). One lane
+// per row (at_row; the kernel this one replaced) walks its ~40 entries in batches of eight behind dependent loads (slot
+// id -> edge value): with ~390 workgroups that is six waves per CU and five serial round trips of ~2 us, 41 us under
+// l1ra's three chains for 32 MB.
 // Here wave w takes the entry pairs w, w + 4, ... of every row of the slice -- all its slot ids are requested at once, then
 // all its edge values --, the four partial sums meet in LDS ((p0 + p1) + p2) + p3, then the boundary slots. A workgroup
 // walks a contiguous range of slices (at most kMaxParts workgroups: one partial row each for the sum of squares). The
@@ -596,25 +576,18 @@ int l1decode_group(PdGroup &G, int pdmaxiter, int xplane, int *stuck) {
     }
     sync_all();
     const double maxabs = ext_members(0, ge, true);
-    static const bool at_classic = getenv("IROTAVG_AT_MUL_CLASSIC") != nullptr;  // A/B: one lane per row (k_at_mul)
-    auto gr4 = [](Graph &g) {  // k_at_mul4: a workgroup per slice, at most kMaxParts of them
+    auto gr4 = [](Graph &g) {  // k_at_mul4 (and the partial rows of its A' t product): a workgroup per slice, at most kMaxParts
         long long gsz = std::min<long long>(g.levels[0].nsl, kMaxParts);
         if (gsz >= 8) gsz &= ~7ll;
         return (int)std::max<long long>(gsz, 1);
     };
-    auto gat = [&](Graph &g) { return at_classic ? gr(g) : gr4(g); };  // partial rows of the A' t product
     auto at_mul = [&](int tplane, bool into_atdv, int slot) {
         for (auto &M : G.mem) {
             Graph &g = *M.g;
             Level &L0 = g.levels[0];
-            if (at_classic)
-                hipLaunchKernelGGL(k_at_mul, dim3(gr(g)), dim3(kRowBlock), 0, g.stream, g.no, L0.nsl, L0.sl_off.p,
-                                   g.slot_eid.p, g.bptr.p, g.beid.p, g.bflag.p, pl(g, tplane),
-                                   into_atdv ? atdv(g) : atv(g), pd_part_slot(g, slot));
-            else
-                hipLaunchKernelGGL(k_at_mul4, dim3(gr4(g)), dim3(kRowBlock), 0, g.stream, g.no, L0.nsl, L0.sl_off.p,
-                                   g.slot_eid.p, g.bptr.p, g.beid.p, g.bflag.p, pl(g, tplane),
-                                   into_atdv ? atdv(g) : atv(g), pd_part_slot(g, slot));
+            hipLaunchKernelGGL(k_at_mul4, dim3(gr4(g)), dim3(kRowBlock), 0, g.stream, g.no, L0.nsl, L0.sl_off.p,
+                               g.slot_eid.p, g.bptr.p, g.beid.p, g.bflag.p, pl(g, tplane),
+                               into_atdv ? atdv(g) : atv(g), pd_part_slot(g, slot));
         }
     };
     for (auto &M : G.mem) {
@@ -624,11 +597,11 @@ int l1decode_group(PdGroup &G, int pdmaxiter, int xplane, int *stuck) {
                            pd_part_slot(g, 0), M.eown);
     }
     at_mul(P_T1, false, 1);  // Atv = A'(lamu1 - lamu2) (:262) and its sum of squares
-    for (auto &M : G.mem) pd_publish(*M.g, {{0, ge(*M.g)}, {1, gat(*M.g)}});
+    for (auto &M : G.mem) pd_publish(*M.g, {{0, ge(*M.g)}, {1, gr4(*M.g)}});
     sync_all();
     double s4[4], v4[4];
     sum_members(0, ge, s4);
-    sum_members(1, gat, v4);
+    sum_members(1, gr4, v4);
     s4[3] = v4[0];
     if (G.combine) G.combine(s4, 4, 0);
     double sdg = -(s4[0] + s4[1]);      // :264
@@ -843,6 +816,7 @@ std::unique_ptr<Graph> make_solver_clone(Graph &g, hipStream_t stream) {
     }
     q.ndense = g.ndense; q.ndense_pad = g.ndense_pad; q.dense_bw = g.dense_bw; q.additive_top = g.additive_top;
     q.stale_spread = g.stale_spread;
+    q.sw = g.sw;
     q.l0_far_entries = g.l0_far_entries;
     q.l1_fused = g.l1_fused;
     q.cg2 = g.cg2;
@@ -851,7 +825,6 @@ std::unique_ptr<Graph> make_solver_clone(Graph &g, hipStream_t stream) {
     q.bcr_far_i = g.bcr_far_i;
     q.bcr_far_j = g.bcr_far_j;
     q.bcr_far_e = g.bcr_far_e;
-    q.dense32 = g.dense32;
     q.b2p.alloc_like(g.b2p, s);
     q.kc_auto = g.kc_auto;
     q.dense_inv.alloc_like(g.dense_inv, s); q.dense_wr.alloc_like(g.dense_wr, s);
@@ -947,7 +920,6 @@ int run_l1ra(Graph &g, int max_iters, double change_th, int *iters, double *runt
              double *trace) {
     pd_prepare(g);
     L1Crew crew;
-    const bool use_crew = !std::getenv("IROTAVG_L1_THREADS_PER_ITERATION");
     const double tic = now_seconds();
     double score = HUGE_VAL;
     int l1_step = 2;  // :868
@@ -987,13 +959,7 @@ int run_l1ra(Graph &g, int max_iters, double change_th, int *iters, double *runt
                 rcs[c] = IROTAVG_ERR_HIP;
             }
         };
-        if (use_crew) {
-            crew.run(chain);
-        } else {
-            std::thread th[3];
-            for (int c = 0; c < 3; c++) th[c] = std::thread(chain, c);
-            for (int c = 0; c < 3; c++) th[c].join();
-        }
+        crew.run(chain);
         for (int c = 0; c < 3; c++) {
             if (rcs[c] != IROTAVG_OK && rc == IROTAVG_OK) rc = rcs[c];
             Graph &q = *g.l1_clones[c];

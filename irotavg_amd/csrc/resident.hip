@@ -196,7 +196,8 @@ ResidentStage resident_stage(Resident &r, long n_views, long view_lo, long n_edg
 // rotation; < 0: none) behind the real records: the closure path of the direct solver (its plan, its kernels) is what
 // the first real call after a loop closure needs, and the graph a caller prepares usually has none yet.
 int resident_rot_avg(Resident &r, long n_views, long view_lo, long n_edges, long edge_lo, int f,
-                     const irotavg_options &opt, irotavg_rotavg_info &loc, bool timing, bool dry, int dry_a, int dry_b) {
+                     const irotavg_options &opt, const Switches &sw, irotavg_rotavg_info &loc, bool timing, bool dry, int dry_a,
+                     int dry_b) {
     if (view_lo > r.n_views || edge_lo > r.n_edges || view_lo < 0 || edge_lo < 0 || f <= 0 || f >= n_views)
         return IROTAVG_ERR_BAD_ARG;
     double tl = now_seconds();
@@ -265,7 +266,7 @@ int resident_rot_avg(Resident &r, long n_views, long view_lo, long n_edges, long
         // (the handle of a growing graph and everything its solves allocate: blocks half as large again, so that the next
         // re-solves find them in the pool)
         DevPool::HeadroomScope headroom;  // this thread; the handle's worker threads follow its flag (Graph::pool_headroom)
-        int rc = graph_create_dev(&h, ne_solve, n_views, f, src, &opt);
+        int rc = graph_create(&h, ne_solve, n_views, f, nullptr, nullptr, 0, &opt, &src, sw);
         if (rc != IROTAVG_OK) return rc;
         Graph &g = graph_of(h);
         g.pool_headroom = true;

@@ -2122,8 +2122,7 @@ int pcg_solve_classic(Graph &g, const std::function<void()> *tail, bool *tail_ra
     // residual is within pcg_rtol and has stopped halving (or after kRefineExtra more iterations).
     constexpr double kRefineTol = 1e-15;
     constexpr int kRefineExtra = 6;
-    static const bool no_refine = std::getenv("IROTAVG_NO_DENSE_REFINE") != nullptr;
-    const bool refine = g.levels.size() == 1 && g.ndense > 0 && !g.bcr_B && g.ng == 0 && !no_refine &&
+    const bool refine = g.levels.size() == 1 && g.ndense > 0 && !g.bcr_B && g.ng == 0 && !g.sw.no_dense_refine &&
                         g.opt.pcg_rtol > kRefineTol;
     const double rtol_dev = refine ? kRefineTol : g.opt.pcg_rtol;
     const double rtol2 = rtol_dev * rtol_dev;
@@ -2312,8 +2311,8 @@ void publish_parts(Graph &g, const PubPart *parts, int nparts) {
 
 void wait_published(Graph &g) {
     // (a pinned block that is not coherent -- the IROTAVG_PIN_DEFAULT experiment -- cannot be polled: every wait would run
-    // into the 2 ms limit)
-    static const bool no_poll = std::getenv("IROTAVG_NO_POLL") != nullptr || std::getenv("IROTAVG_PIN_DEFAULT") != nullptr;
+    // into the 2 ms limit; env_no_poll covers both switches. Process-wide, like the pinned pool.)
+    static const bool no_poll = env_no_poll();
     bool seen = false;
     if (!no_poll) {
         const double t0 = now_seconds();
@@ -2377,7 +2376,7 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
     if (!(score > change_th && 0 < max_iters)) fill(g, g.dw.p, (long long)g.mpad, 1.0);
     // the direct solver's plain loop (no closures, one GPU) runs the weight update and the NEXT iteration's residuals as
     // one kernel behind the step (k_weights_then_residual): er_fresh = the residual planes already belong to Q
-    const bool fuse_wr = g.bcr_B && g.ng == 0 && !g.bcr_shard && !std::getenv("IROTAVG_NO_FUSED_WR");
+    const bool fuse_wr = g.bcr_B && g.ng == 0 && !g.bcr_shard;
     bool er_fresh = false;
     // An iteration that is expected to be the last one skips the residual half (18 us at 2M edges that nobody would read):
     // expected = the previous step was within 50 x change_th (the iteration converges quadratically at the end: the
@@ -2402,14 +2401,11 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
         // the same 5 outer iterations, final rotations within 5e-8 rad (mean; 5e-7 max) of the all-exact run -- the
         // reference's QR is exact in every iteration (ral/l1_irls.cpp:536-556); the north star's bar is 1e-4 rad.
         // Opt-in (options.inexact_outer = 1 or IROTAVG_INEXACT=1): by default every system is solved to pcg_rtol, like
-        // the reference. IROTAVG_INEXACT_RTOL=<tol> fixes the early tolerance (experiments).
+        // the reference.
         const double rtol_keep = g.opt.pcg_rtol;
         if (!g.bcr_B && (it == 0 || score > 50.0 * change_th) && it + 1 < max_iters) {
-            const char *ev = std::getenv("IROTAVG_INEXACT");
-            const bool on = ev ? std::atoi(ev) != 0 : g.opt.inexact_outer == 1;
-            const char *ie = std::getenv("IROTAVG_INEXACT_RTOL");
-            if (ie) g.opt.pcg_rtol = std::max(rtol_keep, std::atof(ie));
-            else if (on) {
+            const bool on = g.sw.inexact >= 0 ? g.sw.inexact != 0 : g.opt.inexact_outer == 1;
+            if (on) {
                 const double last = it == 0 ? 1.0 : score;
                 g.opt.pcg_rtol = std::max(rtol_keep, std::min(1e-4, 0.01 * change_th / last));
             }
@@ -2424,7 +2420,7 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
             const double score_before = score;
             g.bcr_apply = ap_slots > 0;
             g.bcr_applied = false;
-            with_res = !(it + 1 >= max_iters || (it > 0 && score <= 50.0 * change_th)) || std::getenv("IROTAVG_NO_LAST_GUESS");
+            with_res = !(it + 1 >= max_iters || (it > 0 && score <= 50.0 * change_th));
             rc = ls_solve(g);
             g.bcr_apply = false;
             if (rc != IROTAVG_OK) break;
@@ -2440,7 +2436,7 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
                 // the edges (k_weights_then_residual, skipping behind the gate's verdict) whose first workgroup hands
                 // score AND verdict to the host -- three launches and a copy kernel were four (K2, K6, k_publish, K1)
                 const int sgrid = grid_for_elems(g.nu);
-                const bool fuse_cl = fuse_wr && 4 * sgrid + 2 <= 4 * kMaxParts && !std::getenv("IROTAVG_NO_FUSED_CL");
+                const bool fuse_cl = fuse_wr && 4 * sgrid + 2 <= 4 * kMaxParts && !g.sw.no_fused_cl;
                 if (fuse_cl) {
                     bcr_gate(g, g.part_score.p + 4 * (size_t)sgrid);
                     hipLaunchKernelGGL(k_apply_step, dim3(sgrid), dim3(kRowBlock), 0, g.stream, g.nu, g.f, g.ng, g.X.p, g.Q.p,
@@ -2498,7 +2494,7 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
                         if (!(worst <= kClosureRepairAccept)) rc = IROTAVG_ERR_SOLVER;
                     }
                     // (tests: the give-up path on a graph the iterative solver can take)
-                    if (std::getenv("IROTAVG_BCR_FAKE_GIVE_UP")) rc = IROTAVG_ERR_SOLVER;
+                    if (g.sw.bcr_fake_give_up) rc = IROTAVG_ERR_SOLVER;
                     if (rc != IROTAVG_OK) break;
                     launch_update_weights(g, cost, sigma);
                     score = apply_step(g);
@@ -2525,7 +2521,7 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
                 // reservation only knows this process): its solution is NaN, no view took a step, the kernel behind it left
                 // weights and residuals alone -- the iteration once more, level by level from now on
                 // (whichever kernel stood behind the solve: the plain weight update skips its work behind the same word
-                // as the fused weights-and-residual kernel does -- IROTAVG_NO_FUSED_WR, advisor round 5)
+                // as the fused weights-and-residual kernel does -- advisor round 5)
                 if (bcr_up_failed(g)) {
                     er_fresh = true;  // (no view took a step: the residual planes still belong to Q)
                     score = score_before;
@@ -2618,8 +2614,7 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
         } else {
             // the same one-round-trip scheme on the classic launches: weight and rotation update ride behind the
             // first convergence test, gated on its verdict
-            const bool no_settle = std::getenv("IROTAVG_NO_SETTLE") != nullptr;
-            g.irls_settle = (!no_settle && it > 0 && score <= 20.0 * change_th) ? score : -1.0;
+            g.irls_settle = (!g.sw.no_settle && it > 0 && score <= 20.0 * change_th) ? score : -1.0;
             bool tail_ran = false;
             const std::function<void()> tail = [&]() {
                 launch_update_weights(g, cost, sigma, true);
@@ -2668,8 +2663,7 @@ int time_kernel(Graph &g, int which, int reps, double *ms) {
     }
     if (which >= 200 && which < 200 + 16 * 16) {  // development aid: phase stamps (shader clocks) of k_bcr_reduce, level
         double st[16];                             // (which - 200) / 16, chunk IROTAVG_BCR_STAMP_CHUNK, see bcr.hip
-        const char *e = getenv("IROTAVG_BCR_STAMP_CHUNK");
-        const int rc = bcr_stamps(g, (which - 200) / 16, e ? atoi(e) : 0, st);
+        const int rc = bcr_stamps(g, (which - 200) / 16, g.sw.bcr_stamp_chunk, st);
         *ms = st[(which - 200) % 16];
         return rc;
     }

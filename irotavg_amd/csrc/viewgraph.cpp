@@ -94,6 +94,7 @@ struct irotavg_viewgraph {
     };
     std::vector<std::vector<Conn>> conn;
     irotavg_options opt;
+    irh::Switches sw;  // read when the view-graph is made; handed to every handle, resident graph and window solver it creates
     irotavg_rotavg_info last{};
     irh::WindowSolver *win = nullptr;  // persistent staging of the single-kernel window solve
     // The device-resident growing copy of the graph that the global re-solves run on (resident.hip) and what the
@@ -174,6 +175,7 @@ int irotavg_viewgraph_create(irotavg_viewgraph **vg, const irotavg_options *opt)
             (*vg)->opt = *opt;
         else
             irotavg_default_options(&(*vg)->opt);
+        (*vg)->sw = irh::read_switches();
     } catch (...) {
         return IROTAVG_ERR_NOMEM;
     }
@@ -273,10 +275,8 @@ namespace {
 // windows, graphs of fewer than 20000 connections, f == 0, no device); true with *rc set otherwise.
 bool rotavg_resident(irotavg_viewgraph *vg, irotavg_rotavg_info &loc, bool timing, int *rc, bool dry = false) {
     const long m = (long)vg->pose.size();
-    if (std::getenv("IROTAVG_NO_RESIDENT")) return false;
-    long min_edges = 20000;  // below: the host build of the general path (build.cpp) is the faster one
-    if (const char *e = std::getenv("IROTAVG_RESIDENT_MIN_EDGES")) min_edges = std::atol(e);
-    if (vg->n_conn < min_edges || vg->n_conn < m || vg->n_touched < m || vg->n_fixed < 1 || m - vg->n_fixed < 1) return false;
+    if (vg->sw.no_resident) return false;
+    if (vg->n_conn < vg->sw.resident_min_edges || vg->n_conn < m || vg->n_touched < m || vg->n_fixed < 1 || m - vg->n_fixed < 1) return false;
     if (vg->n_conn > 0x3fffffffL) return false;
     if (irotavg_device_count() <= 0) return false;
     const double t0 = irh::now_seconds();
@@ -332,7 +332,7 @@ bool rotavg_resident(irotavg_viewgraph *vg, irotavg_rotavg_info &loc, bool timin
             for (long x = m - 1; x > dry_a + 1000 && dry_b < 0; x--)
                 if (!vg->fixed[(size_t)x]) dry_b = (int)x;
         }
-        *rc = irh::resident_rot_avg(R, m, view_lo, ne, edge_lo, f, vg->opt, loc, timing, dry, dry_a, dry_b);
+        *rc = irh::resident_rot_avg(R, m, view_lo, ne, edge_lo, f, vg->opt, vg->sw, loc, timing, dry, dry_a, dry_b);
         loc.n_views = (int)m;
         loc.n_edges = (int)ne;
         loc.n_fixed = f;
@@ -380,7 +380,7 @@ bool rotavg_resident(irotavg_viewgraph *vg, irotavg_rotavg_info &loc, bool timin
 int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotavg_info *info) {
     if (!vg || win_size <= 2) return IROTAVG_ERR_BAD_ARG;  // assert(winSize > 2) :1265
     irotavg_rotavg_info loc{};
-    const bool timing = std::getenv("IROTAVG_ROTAVG_TIMING") != nullptr;
+    const bool timing = vg->sw.rotavg_timing;
     struct Total {
         bool on;
         double t0;
@@ -537,7 +537,7 @@ int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotav
         // small (sliding-window) problem: the whole l1ra + irls pipeline in ONE kernel launch
         if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
         try {
-            if (!vg->win) vg->win = irh::window_solver_new();
+            if (!vg->win) vg->win = irh::window_solver_new(vg->sw);
             std::vector<double> &Qa = vg->scratch.Qa;
             Qa.resize((size_t)4 * nv);
             for (long r = 0; r < nv; r++)
@@ -566,7 +566,7 @@ int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotav
         }
     } else {
         irotavg_graph *g = nullptr;
-        rc = irotavg_graph_create(&g, ne, nv, f, I.data(), QQ.data(), ne, &vg->opt);
+        rc = irh::graph_create(&g, ne, nv, f, I.data(), QQ.data(), ne, &vg->opt, nullptr, vg->sw);
         if (rc != IROTAVG_OK) return rc;
         rc = irotavg_graph_set_rotations(g, Q.data(), nv);
         lap("graph create + upload");
@@ -584,7 +584,7 @@ int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotav
             g = nullptr;
             irotavg_options it = vg->opt;
             it.band_direct = -1;
-            rc = irotavg_graph_create(&g, ne, nv, f, I.data(), QQ.data(), ne, &it);
+            rc = irh::graph_create(&g, ne, nv, f, I.data(), QQ.data(), ne, &it, nullptr, vg->sw);
             if (rc != IROTAVG_OK) return rc;
             rc = irotavg_graph_set_rotations(g, Q.data(), nv);
             if (rc == IROTAVG_OK) rc = irotavg_graph_l1ra(g, 100, change_th, &loc.l1_iters, &loc.l1_runtime, nullptr);
@@ -622,7 +622,7 @@ int irotavg_viewgraph_prepare(irotavg_viewgraph *vg) {
     if (!vg) return IROTAVG_ERR_BAD_ARG;
     irotavg_rotavg_info loc{};
     int rc = IROTAVG_OK;
-    const bool timing = std::getenv("IROTAVG_ROTAVG_TIMING") != nullptr;
+    const bool timing = vg->sw.rotavg_timing;
     if (!rotavg_resident(vg, loc, timing, &rc, true)) return IROTAVG_OK;
     return rc;
 }
@@ -672,7 +672,7 @@ int irotavg_viewgraph_rot_avg_batch(irotavg_viewgraph *const *vgs, int n, int wi
     int rc = IROTAVG_OK;
     try {
         irotavg_viewgraph *host = vgs[owner[0]];
-        if (!host->win) host->win = irh::window_solver_new();
+        if (!host->win) host->win = irh::window_solver_new(host->sw);
         const double t0 = irh::now_seconds();
         rc = irh::window_solve_batch(*host->win, (int)items.size(), items.data(), 100, 100, IROTAVG_GEMAN_MCCLURE,
                                      5 * M_PI / 180.0, .001);
@@ -757,7 +757,7 @@ int irotavg_window_solve_kernel(int64_t m, int64_t n_total, int f, const int32_t
             for (int c = 0; c < 4; c++) qa[(size_t)4 * k + c] = QQ[(size_t)c * ldqq + k];
         for (int64_t r = 0; r < n_total; r++)
             for (int c = 0; c < 4; c++) Qa[(size_t)4 * r + c] = Q[(size_t)c * ldq + r];
-        irh::WindowSolver *ws = irh::window_solver_new();
+        irh::WindowSolver *ws = irh::window_solver_new(irh::read_switches());
         const int rc = irh::window_solve(*ws, (int)n_total, f, (int)m, I, qa.data(), Qa.data(), weights,
                                          l1_iters, irls_iters, cost, sigma, change_th, l1_out, irls_out,
                                          kernel);

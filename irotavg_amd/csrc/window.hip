@@ -1133,6 +1133,7 @@ struct WindowSolver {
     size_t cap = 0;
     int seq = 0;       // sequence number of the last wave-kernel launch
     bool attr_set = false;
+    bool stamps = false;  // Switches::window_stamps of whoever made the solver: print the wave kernel's phase stamps
     unsigned char *bhost = nullptr, *bhdev = nullptr;  // pinned block of the batched form (window_solve_batch)
     size_t bcap = 0;
     ~WindowSolver() {
@@ -1223,8 +1224,7 @@ int window_solve(WindowSolver &ws, int nv, int f, int ne, const int32_t *I, cons
     }
     WinResult R;
     std::memcpy(&R, ws.host + oR, sizeof(R));
-    static const bool stamps = getenv("IROTAVG_WINDOW_STAMPS") != nullptr;
-    if (stamps && wave)  // s_memtime counts at 100 MHz
+    if (ws.stamps && wave)  // s_memtime counts at 100 MHz
         std::fprintf(stderr, "[window] nv %d f %d ne %d l1 %d irls %d: load+lists %.2f us, l1ra %.2f us, irls %.2f us, store %.2f us\n", nv,
                      f, ne, R.l1_iters, R.irls_iters, (R.stamp[1] - R.stamp[0]) * 1e-2, (R.stamp[2] - R.stamp[1]) * 1e-2,
                      (R.stamp[3] - R.stamp[2]) * 1e-2, (R.stamp[4] - R.stamp[3]) * 1e-2);
@@ -1303,7 +1303,11 @@ int window_solve_batch(WindowSolver &ws, int nb, WinBatchItem *items, int l1_max
     return rc;
 }
 
-WindowSolver *window_solver_new() { return new WindowSolver(); }
+WindowSolver *window_solver_new(const Switches &sw) {
+    WindowSolver *w = new WindowSolver();
+    w->stamps = sw.window_stamps;
+    return w;
+}
 void window_solver_delete(WindowSolver *w) { delete w; }
 
 }  // namespace irh

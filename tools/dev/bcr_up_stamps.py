@@ -12,14 +12,14 @@ wgs = [int(a) for a in sys.argv[3:]] or [0]
 S = synth.make_graph(n, m, 0.0, seed=0)
 Q = np.zeros((n, 4)); Q[:, 3] = 1; Q[0] = S["Qgt"][0]
 ral.init_mst(Q, S["QQ"], S["I"], 1)
-with capi.Graph(S["I"], S["QQ"], n, 1) as G:
-    G.set_rotations(Q)
-    G.irls(4, 5 * np.pi / 180, 50, 1e-3)
-    info = G.direct_info()
-    print(n, m, "block", info["block"], "levels", [(L["blocks"], L["chunks"]) for L in info["levels"]])
-    nl = len(info["levels"])
-    for wg in wgs:
-        os.environ["IROTAVG_BCR_STAMP_CHUNK"] = str(wg)
+for wg in wgs:
+    os.environ["IROTAVG_BCR_STAMP_CHUNK"] = str(wg)  # (read when the handle is made: a handle per workgroup)
+    with capi.Graph(S["I"], S["QQ"], n, 1) as G:
+        G.set_rotations(Q)
+        G.irls(4, 5 * np.pi / 180, 50, 1e-3)
+        info = G.direct_info()
+        print(n, m, "block", info["block"], "levels", [(L["blocks"], L["chunks"]) for L in info["levels"]])
+        nl = len(info["levels"])
         for i in range(nl - 1):
             if wg >= info["levels"][1 + i]["chunks"]:
                 break
