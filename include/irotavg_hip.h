@@ -42,7 +42,8 @@ extern "C" {
 #define IROTAVG_ERR_NOT_CONVERGED (-8) /* inner PCG hit its iteration cap -- after irls has re-inverted a re-used
                                           coarse inverse and, on a single level of <= 1024 views, tried the dense
                                           Cholesky solve; the iterate reached so far is left in place */
-#define IROTAVG_ERR_UNSUPPORTED (-9)  /* the query is not available on this kind of handle (irotavg_graph_rotation_variance) */
+#define IROTAVG_ERR_UNSUPPORTED (-9)  /* the query is not available on this kind of handle (irotavg_graph_rotation_variance,
+                                         irotavg_graph_edge_diagnostics) */
 
 /* ral/l1_irls.hpp:56-57 -- the integer values are ABI */
 enum irotavg_cost {
@@ -288,6 +289,27 @@ int irotavg_graph_rotation_variance(irotavg_graph *g, double *var /* n_total, or
 int irotavg_rotation_variance(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq,
                               const double *Q, int64_t ldq, const double *weights, double *var, int64_t npairs,
                               const int32_t *pairs, double *pair_var, double *scale);
+
+/* Diagnostics of every measurement (docs/edge_diagnostics.md), with A, d, M, Sigma, r_k and s^2 as above and u_k = row k
+ * of A. For every edge k < m:
+ *   edge_var[k] = u_k' Sigma u_k (0 for a zero row of A: an edge whose second view is fixed);
+ *   leverage[k] = d_k^2 edge_var[k], the diagonal of the hat matrix of the IRLS system: in [0, 1] up to rounding, summing
+ *                 to nu; 1 - leverage is the edge's redundancy (0: an error in this measurement could never be seen);
+ *   chi2[k]     = d_k^2 |r_k|^2 / (s^2 max(0, 1 - leverage[k])) in plain IEEE arithmetic (+inf for a residual on an edge
+ *                 without redundancy, NaN for 0/0 and whenever s^2 is NaN); approximately chi-square with 3 degrees of
+ *                 freedom under the reference's linearisation and Gaussian noise. Read leverage next to it.
+ * Each array has m entries or is NULL (not computed, not copied); scale receives s^2 and may be NULL; nothing asked for:
+ * IROTAVG_ERR_BAD_ARG before any device work. Routes: nu <= 2048 -- the dense inverse; the banded direct solver's handles
+ * (stats.band_block > 0) -- gathers from the block-tridiagonal selected inverse, Woodbury-corrected for the loop closures;
+ * any other (multigrid-PCG) handle: IROTAVG_ERR_UNSUPPORTED (irotavg_graph_rotation_variance's pairs serve a chosen
+ * few there). Read-only, deterministic (bitwise), singular M -> IROTAVG_ERR_SOLVER, outputs written only on success:
+ * all as irotavg_graph_rotation_variance. */
+int irotavg_graph_edge_diagnostics(irotavg_graph *g, double *edge_var /* m or NULL */, double *leverage /* m or NULL */,
+                                   double *chi2 /* m or NULL */, double *scale /* may be NULL */);
+/* The same query without a handle, through the one-shot calls' kept handle (as irotavg_rotation_variance). */
+int irotavg_edge_diagnostics(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq,
+                             const double *Q, int64_t ldq, const double *weights, double *edge_var, double *leverage,
+                             double *chi2, double *scale);
 
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash

@@ -42,6 +42,7 @@ SYMBOLS = [
     "irotavg_oneshot_cache", "irotavg_oneshot_cache_clear", "irotavg_oneshot_cache_stats",
     "irotavg_dist_timing",
     "irotavg_graph_rotation_variance", "irotavg_rotation_variance",
+    "irotavg_graph_edge_diagnostics", "irotavg_edge_diagnostics",
 ]
 
 
@@ -141,6 +142,9 @@ def lib():
     L.irotavg_graph_rotation_variance.argtypes = [vp, _dp, C.c_int64, _ip, _dp, _dp]
     L.irotavg_rotation_variance.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
                                             _dp, C.c_int64, _ip, _dp, _dp]
+    L.irotavg_graph_edge_diagnostics.argtypes = [vp, _dp, _dp, _dp, _dp]
+    L.irotavg_edge_diagnostics.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
+                                           _dp, _dp, _dp, _dp]
     L.irotavg_viewgraph_create.argtypes = [C.POINTER(vp), C.POINTER(Options)]
     L.irotavg_viewgraph_destroy.argtypes = [vp]
     L.irotavg_viewgraph_destroy.restype = None
@@ -391,6 +395,12 @@ class Graph:
         return _variance_call(lambda *a: lib().irotavg_graph_rotation_variance(self._h, *a), self.n_total, pairs,
                               marginals, allow_rc, "irotavg_graph_rotation_variance")
 
+    def edge_diagnostics(self, edge_var=True, leverage=True, chi2=True, allow_rc=()):
+        """irotavg_graph_edge_diagnostics: dict(rc, edge_var, leverage, chi2 (m each, or None), scale) for every edge
+        (docs/edge_diagnostics.md)."""
+        return _edge_call(lambda *a: lib().irotavg_graph_edge_diagnostics(self._h, *a), self.m, edge_var, leverage,
+                          chi2, allow_rc, "irotavg_graph_edge_diagnostics")
+
     def fingerprint(self):
         """Hashes of every structural array + the kernel-choosing scalars (irotavg_graph_fingerprint)."""
         out = (C.c_uint64 * 512)()
@@ -427,6 +437,28 @@ def rotation_variance(I, QQ, Q, weights, f, pairs=None, marginals=True, allow_rc
     return _variance_call(lambda *a: lib().irotavg_rotation_variance(len(I), n_total, int(f), _i(I), _d(QQ),
                                                                      QQ.shape[0], _d(Q), Q.shape[0], _d(w), *a),
                           n_total, pairs, marginals, allow_rc, "irotavg_rotation_variance")
+
+
+def _edge_call(call, m, edge_var, leverage, chi2, allow_rc, where):
+    out = [np.full(m, np.nan) if want else None for want in (edge_var, leverage, chi2)]
+    scale = C.c_double(np.nan)
+    rc = call(*[_d(a) if a is not None else None for a in out], C.byref(scale))
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, where)
+    return dict(rc=rc, edge_var=out[0], leverage=out[1], chi2=out[2], scale=scale.value)
+
+
+def edge_diagnostics(I, QQ, Q, weights, f, edge_var=True, leverage=True, chi2=True, allow_rc=()):
+    """irotavg_edge_diagnostics: the query without a handle (through the kept one-shot handle), from the rotations and
+    weights irls returned."""
+    I = edges(I)
+    QQ = fmat(QQ)
+    Q = fmat(Q)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    n_total = Q.shape[0]
+    return _edge_call(lambda *a: lib().irotavg_edge_diagnostics(len(I), n_total, int(f), _i(I), _d(QQ), QQ.shape[0],
+                                                                _d(Q), Q.shape[0], _d(w), *a),
+                      len(I), edge_var, leverage, chi2, allow_rc, "irotavg_edge_diagnostics")
 
 
 def oneshot_cache(enable):

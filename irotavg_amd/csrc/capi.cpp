@@ -6,6 +6,7 @@
 #include <new>
 
 #include "graph.hpp"
+#include "marginals.hpp"
 
 using namespace irh;
 
@@ -47,7 +48,7 @@ const char *irotavg_error_string(int code) {
     case IROTAVG_ERR_HIP: return "HIP runtime error";
     case IROTAVG_ERR_NO_DEVICE: return "no usable HIP device (this library has no CPU fallback)";
     case IROTAVG_ERR_NOT_CONVERGED: return "inner PCG did not converge within pcg_max_iters";
-    case IROTAVG_ERR_UNSUPPORTED: return "not supported on this handle (rotation variance: marginals need a dense or banded direct-solver handle)";
+    case IROTAVG_ERR_UNSUPPORTED: return "not supported on this handle (rotation variance: marginals, and edge diagnostics, need a dense or banded direct-solver handle)";
     default: return "unknown error";
     }
 }
@@ -412,6 +413,13 @@ int irotavg_graph_rotation_variance(irotavg_graph *h, double *var, int64_t npair
     if (!h || !variance_args_ok(h->g.n_total, npairs, pairs, pair_var)) return IROTAVG_ERR_BAD_ARG;
     API_TRY
     return rotation_variance(h->g, var, npairs, pairs, pair_var, scale);
+    API_CATCH
+}
+
+int irotavg_graph_edge_diagnostics(irotavg_graph *h, double *edge_var, double *leverage, double *chi2, double *scale) {
+    if (!h || (!edge_var && !leverage && !chi2 && !scale)) return IROTAVG_ERR_BAD_ARG;
+    API_TRY
+    return edge_diagnostics(h->g, edge_var, leverage, chi2, scale);
     API_CATCH
 }
 
@@ -852,6 +860,23 @@ int irotavg_rotation_variance(int64_t m, int64_t n_total, int f, const int32_t *
     rc = irotavg_graph_set_rotations(h, Q, ldq);
     if (rc == IROTAVG_OK) rc = irotavg_graph_set_weights(h, weights);
     if (rc == IROTAVG_OK) rc = irotavg_graph_rotation_variance(h, var, npairs, pairs, pair_var, scale);
+    // (a handle the query refused is as good as before: it is kept like a successful one)
+    oneshot_close(h, key, cached, rc == IROTAVG_ERR_UNSUPPORTED || rc == IROTAVG_ERR_SOLVER ? IROTAVG_OK : rc);
+    return rc;
+}
+
+int irotavg_edge_diagnostics(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq,
+                             const double *Q, int64_t ldq, const double *weights, double *edge_var, double *leverage,
+                             double *chi2, double *scale) {
+    if (!Q || !weights || (!edge_var && !leverage && !chi2 && !scale)) return IROTAVG_ERR_BAD_ARG;
+    irotavg_graph *h = nullptr;
+    OneShotKey key;
+    bool cached = false;
+    int rc = oneshot_open(&h, &key, &cached, m, n_total, f, I, QQ, ldqq);
+    if (rc != IROTAVG_OK) return rc;
+    rc = irotavg_graph_set_rotations(h, Q, ldq);
+    if (rc == IROTAVG_OK) rc = irotavg_graph_set_weights(h, weights);
+    if (rc == IROTAVG_OK) rc = irotavg_graph_edge_diagnostics(h, edge_var, leverage, chi2, scale);
     // (a handle the query refused is as good as before: it is kept like a successful one)
     oneshot_close(h, key, cached, rc == IROTAVG_ERR_UNSUPPORTED || rc == IROTAVG_ERR_SOLVER ? IROTAVG_OK : rc);
     return rc;

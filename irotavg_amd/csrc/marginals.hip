@@ -21,6 +21,7 @@
 
 #include "graph.hpp"
 #include "kernels.hpp"
+#include "marginals.hpp"
 
 namespace irh {
 namespace {
@@ -473,8 +474,12 @@ __global__ __launch_bounds__(256) void k_mv_scale(long long m, long long mpad, c
 
 int grid1(long long n) { return (int)((n + 255) / 256); }
 
-// what the device returns in one copy: [0] dead flag, [1] s^2 numerator, [2] m_A
-double residual_scale(Graph &g, double *num_out, double *cnt_out) {
+constexpr int kPairChunk = 1024;  // pair columns per multi right-hand-side solve
+
+}  // namespace
+
+// ---- shared with the edge diagnostics (marginals.hpp) ----------------------------------------------------------------
+double residual_scale(Graph &g, double *num_out, double *cnt_out, DevBuf<double> *er_keep) {
     DevBuf<double> er, part;
     er.alloc((size_t)3 * g.mpad);
     part.alloc(2 * kScaleGrid);
@@ -493,6 +498,7 @@ double residual_scale(Graph &g, double *num_out, double *cnt_out) {
     }
     *num_out = num;
     *cnt_out = cnt;
+    if (er_keep) *er_keep = std::move(er);
     return cnt > g.nu ? num / (3.0 * (cnt - g.nu)) : NAN;
 }
 
@@ -503,7 +509,6 @@ int read_dead(Graph &g, const DevBuf<int> &dead) {
     return h;
 }
 
-// dense_invert_spd on a buffer of the query's own; the handle's dead-pivot scale of its live inverse is kept
 void invert_own(Graph &g, double *A, int npad) {
     DevBuf<double> keep;
     const bool had = g.dense_maxdiag.n >= 1;
@@ -516,68 +521,58 @@ void invert_own(Graph &g, double *A, int npad) {
     IRH_CHECK(hipStreamSynchronize(g.stream));
 }
 
-// The band factor of A_b with its selected inverse.
-struct BandFactor {
-    int B = 0, nb = 0, n = 0;
-    DevBuf<double> D, U, Dinv, Ga, Gc, orig;  // D / U become SD / SU (Sigma blocks) in the downward sweep
-
-    void factor(Graph &g, int *dead) {
-        const Level &L0 = g.levels[0];
-        const size_t BB = (size_t)B * B, tot = (size_t)nb * BB;
-        D.alloc(tot);
-        U.alloc(tot);
-        Dinv.alloc(tot);
-        Ga.alloc(tot);
-        Gc.alloc(tot);
-        orig.alloc((size_t)nb * B);
-        D.zero(g.stream);
-        U.zero(g.stream);
-        hipLaunchKernelGGL(k_mv_band_assemble, dim3(grid1((long long)nb * B)), dim3(256), 0, g.stream, n, B, nb * B,
-                           L0.sl_off.p, L0.col.p, g.slot_eid.p, g.bptr.p, g.beid.p, g.bflag.p, g.dw.p, D.p, U.p, orig.p);
-        int s = 1;
-        for (; s < nb; s *= 2) {
-            const int ne = (nb - s + 2 * s - 1) / (2 * s), ns = (nb + 2 * s - 1) / (2 * s);
-            hipLaunchKernelGGL(k_mv_elim, dim3(ne), dim3(256), 0, g.stream, nb, B, s, 0, D.p, U.p, Dinv.p, Ga.p, Gc.p,
-                               orig.p, dead);
-            hipLaunchKernelGGL(k_mv_update, dim3(ns), dim3(256), 0, g.stream, nb, B, s, D.p, U.p, Ga.p, Gc.p);
-        }
-        hipLaunchKernelGGL(k_mv_elim, dim3(1), dim3(256), 0, g.stream, nb, B, s, 1, D.p, U.p, Dinv.p, Ga.p, Gc.p, orig.p,
-                           dead);
+void BandFactor::factor(Graph &g, int *dead) {
+    const Level &L0 = g.levels[0];
+    const size_t BB = (size_t)B * B, tot = (size_t)nb * BB;
+    D.alloc(tot);
+    U.alloc(tot);
+    Dinv.alloc(tot);
+    Ga.alloc(tot);
+    Gc.alloc(tot);
+    orig.alloc((size_t)nb * B);
+    D.zero(g.stream);
+    U.zero(g.stream);
+    hipLaunchKernelGGL(k_mv_band_assemble, dim3(grid1((long long)nb * B)), dim3(256), 0, g.stream, n, B, nb * B,
+                       L0.sl_off.p, L0.col.p, g.slot_eid.p, g.bptr.p, g.beid.p, g.bflag.p, g.dw.p, D.p, U.p, orig.p);
+    int s = 1;
+    for (; s < nb; s *= 2) {
+        const int ne = (nb - s + 2 * s - 1) / (2 * s), ns = (nb + 2 * s - 1) / (2 * s);
+        hipLaunchKernelGGL(k_mv_elim, dim3(ne), dim3(256), 0, g.stream, nb, B, s, 0, D.p, U.p, Dinv.p, Ga.p, Gc.p,
+                           orig.p, dead);
+        hipLaunchKernelGGL(k_mv_update, dim3(ns), dim3(256), 0, g.stream, nb, B, s, D.p, U.p, Ga.p, Gc.p);
     }
-    void select(Graph &g) {
-        IRH_CHECK(hipMemcpyAsync(D.p, Dinv.p, sizeof(double) * B * B, hipMemcpyDeviceToDevice, g.stream));
-        int top = 1;
-        while (top < nb) top *= 2;
-        for (int s = top / 2; s >= 1; s /= 2) {
-            const int ne = (nb - s + 2 * s - 1) / (2 * s);
-            if (ne > 0)
-                hipLaunchKernelGGL(k_mv_down, dim3(ne), dim3(256), 0, g.stream, nb, B, s, Dinv.p, Ga.p, Gc.p, D.p, U.p);
-        }
+    hipLaunchKernelGGL(k_mv_elim, dim3(1), dim3(256), 0, g.stream, nb, B, s, 1, D.p, U.p, Dinv.p, Ga.p, Gc.p, orig.p,
+                       dead);
+}
+void BandFactor::select(Graph &g) {
+    IRH_CHECK(hipMemcpyAsync(D.p, Dinv.p, sizeof(double) * B * B, hipMemcpyDeviceToDevice, g.stream));
+    int top = 1;
+    while (top < nb) top *= 2;
+    for (int s = top / 2; s >= 1; s /= 2) {
+        const int ne = (nb - s + 2 * s - 1) / (2 * s);
+        if (ne > 0)
+            hipLaunchKernelGGL(k_mv_down, dim3(ne), dim3(256), 0, g.stream, nb, B, s, Dinv.p, Ga.p, Gc.p, D.p, U.p);
     }
-    // Y (nb B rows x ld columns) <- A_b^-1 Y
-    void solve(Graph &g, double *Y, int ld) {
-        const int ct = ld / 64;
-        int s = 1;
-        for (; s < nb; s *= 2)
-            hipLaunchKernelGGL(k_mv_fwd, dim3((nb + 2 * s - 1) / (2 * s), ct), dim3(256), 0, g.stream, nb, B, s, ld, Ga.p,
-                               Gc.p, Y);
-        hipLaunchKernelGGL(k_mv_bwd, dim3(1, ct), dim3(256), 0, g.stream, nb, B, s, 1, ld, Dinv.p, Ga.p, Gc.p, Y);
-        for (s /= 2; s >= 1; s /= 2)
-            hipLaunchKernelGGL(k_mv_bwd, dim3((nb - s + 2 * s - 1) / (2 * s), ct), dim3(256), 0, g.stream, nb, B, s, 0,
-                               ld, Dinv.p, Ga.p, Gc.p, Y);
-    }
-};
+}
+void BandFactor::solve(Graph &g, double *Y, int ld) {
+    const int ct = ld / 64;
+    int s = 1;
+    for (; s < nb; s *= 2)
+        hipLaunchKernelGGL(k_mv_fwd, dim3((nb + 2 * s - 1) / (2 * s), ct), dim3(256), 0, g.stream, nb, B, s, ld, Ga.p,
+                           Gc.p, Y);
+    hipLaunchKernelGGL(k_mv_bwd, dim3(1, ct), dim3(256), 0, g.stream, nb, B, s, 1, ld, Dinv.p, Ga.p, Gc.p, Y);
+    for (s /= 2; s >= 1; s /= 2)
+        hipLaunchKernelGGL(k_mv_bwd, dim3((nb - s + 2 * s - 1) / (2 * s), ct), dim3(256), 0, g.stream, nb, B, s, 0,
+                           ld, Dinv.p, Ga.p, Gc.p, Y);
+}
 
-constexpr int kPairChunk = 1024;  // pair columns per multi right-hand-side solve
-
-int band_path(Graph &g, bool want_var, std::vector<double> &var, const std::vector<int> &pi,
-              const std::vector<int> &pj, std::vector<double> &pv) {
-    BandFactor F;
+int band_setup(Graph &g, BandFactor &F, BandClosures &C, DevBuf<int> &dead) {
     F.B = g.bcr_B;
     F.n = g.no;
     F.nb = (g.no + F.B - 1) / F.B;
     const int nrows = F.nb * F.B, nrowsZ = (nrows + 63) / 64 * 64;
-    DevBuf<int> dead;
+    C.nrows = nrows;
+    C.nrowsZ = nrowsZ;
     dead.alloc(1);
     dead.zero(g.stream);
     F.factor(g, dead.p);
@@ -602,44 +597,34 @@ int band_path(Graph &g, bool want_var, std::vector<double> &var, const std::vect
             cinv.push_back(1.0 / w);
         }
     }
-    const int k = (int)cp.size();
+    const int k = C.k = (int)cp.size();
     if (read_dead(g, dead)) return IROTAVG_ERR_SOLVER;
-    DevBuf<double> Z, S, corr, dvar;
-    DevBuf<int> dcp, dcq;
-    const int ldZ = std::max(64, (k + 63) / 64 * 64);
+    const int ldZ = C.ldZ = std::max(64, (k + 63) / 64 * 64);
     if (k > 0) {
-        dcp.upload(cp, g.stream);
-        dcq.upload(cq, g.stream);
+        C.dcp.upload(cp, g.stream);
+        C.dcq.upload(cq, g.stream);
         DevBuf<double> dcinv;
         dcinv.upload(cinv, g.stream);
-        Z.alloc((size_t)nrowsZ * ldZ);  // k_mv_wcorr reads whole 64-row tiles: the rows past nrows stay zero
-        Z.zero(g.stream);
-        hipLaunchKernelGGL(k_mv_rhs, dim3(grid1(k)), dim3(256), 0, g.stream, k, ldZ, dcp.p, dcq.p, Z.p);
-        F.solve(g, Z.p, ldZ);
-        S.alloc((size_t)ldZ * ldZ);
-        hipLaunchKernelGGL(k_mv_wsys, dim3(grid1((long long)ldZ * ldZ)), dim3(256), 0, g.stream, k, ldZ, ldZ, dcp.p,
-                           dcq.p, dcinv.p, Z.p, S.p);
-        invert_own(g, S.p, ldZ);
+        C.Z.alloc((size_t)nrowsZ * ldZ);  // k_mv_wcorr reads whole 64-row tiles: the rows past nrows stay zero
+        C.Z.zero(g.stream);
+        hipLaunchKernelGGL(k_mv_rhs, dim3(grid1(k)), dim3(256), 0, g.stream, k, ldZ, C.dcp.p, C.dcq.p, C.Z.p);
+        F.solve(g, C.Z.p, ldZ);
+        C.S.alloc((size_t)ldZ * ldZ);
+        hipLaunchKernelGGL(k_mv_wsys, dim3(grid1((long long)ldZ * ldZ)), dim3(256), 0, g.stream, k, ldZ, ldZ, C.dcp.p,
+                           C.dcq.p, dcinv.p, C.Z.p, C.S.p);
+        invert_own(g, C.S.p, ldZ);
         DevBuf<double> sd;
         sd.alloc((size_t)k);
         dead.zero(g.stream);
-        hipLaunchKernelGGL(k_mv_dense_var, dim3(grid1(k)), dim3(256), 0, g.stream, k, ldZ, S.p, nullptr, sd.p,
+        hipLaunchKernelGGL(k_mv_dense_var, dim3(grid1(k)), dim3(256), 0, g.stream, k, ldZ, C.S.p, nullptr, sd.p,
                            dead.p);
         if (read_dead(g, dead)) return IROTAVG_ERR_SOLVER;
     }
-    if (want_var) {
-        F.select(g);
-        if (k > 0) {
-            corr.alloc((size_t)nrowsZ);
-            hipLaunchKernelGGL(k_mv_wcorr, dim3(nrowsZ / 64), dim3(256), 0, g.stream, ldZ, Z.p, S.p, ldZ, corr.p);
-        }
-        dvar.alloc((size_t)F.n);
-        hipLaunchKernelGGL(k_mv_band_var, dim3(grid1(F.n)), dim3(256), 0, g.stream, F.n, F.B, F.D.p,
-                           k > 0 ? corr.p : nullptr, dvar.p, dead.p);
-        var.resize((size_t)F.n);
-        IRH_CHECK(hipMemcpyAsync(var.data(), dvar.p, sizeof(double) * F.n, hipMemcpyDeviceToHost, g.stream));
-        if (read_dead(g, dead)) return IROTAVG_ERR_SOLVER;
-    }
+    return IROTAVG_OK;
+}
+
+void band_pairs(Graph &g, BandFactor &F, const BandClosures &C, const std::vector<int> &pi, const std::vector<int> &pj,
+                std::vector<double> &pv) {
     const int np = (int)pi.size();
     pv.assign((size_t)np, 0.0);
     for (int p0 = 0; p0 < np; p0 += kPairChunk) {
@@ -651,45 +636,79 @@ int band_path(Graph &g, bool want_var, std::vector<double> &var, const std::vect
         da.upload(a, g.stream);
         db.upload(b, g.stream);
         DevBuf<double> Y, dpv;
-        Y.alloc((size_t)nrows * ld);
+        Y.alloc((size_t)C.nrows * ld);
         Y.zero(g.stream);
         dpv.alloc((size_t)nc);
         hipLaunchKernelGGL(k_mv_rhs, dim3(grid1(nc)), dim3(256), 0, g.stream, nc, ld, da.p, db.p, Y.p);
         F.solve(g, Y.p, ld);
-        hipLaunchKernelGGL(k_mv_band_pairs, dim3(nc), dim3(256), 0, g.stream, ld, da.p, db.p, Y.p, k, dcp.p, dcq.p, S.p,
-                           ldZ, dpv.p);
+        hipLaunchKernelGGL(k_mv_band_pairs, dim3(nc), dim3(256), 0, g.stream, ld, da.p, db.p, Y.p, C.k, C.dcp.p, C.dcq.p,
+                           C.S.p, C.ldZ, dpv.p);
         IRH_CHECK(hipMemcpyAsync(pv.data() + p0, dpv.p, sizeof(double) * nc, hipMemcpyDeviceToHost, g.stream));
         IRH_CHECK(hipStreamSynchronize(g.stream));  // the chunk's buffers go back to the pool
     }
-    IRH_CHECK(hipStreamSynchronize(g.stream));
-    return IROTAVG_OK;
 }
 
-int dense_path(Graph &g, bool want_var, std::vector<double> &var, const std::vector<int> &pi,
-               const std::vector<int> &pj, std::vector<double> &pv) {
+int dense_inverse(Graph &g, DenseInverse &Dn, DevBuf<int> &dead) {
     const Level &L0 = g.levels[0];
-    const int n = g.no, npad = std::max(64, (n + 63) / 64 * 64);
-    DevBuf<double> M, dvar;
-    DevBuf<int> dead;
+    const int n = Dn.n = g.no, npad = Dn.npad = std::max(64, (n + 63) / 64 * 64);
+    DevBuf<double> &M = Dn.M, &sc = Dn.sc;
     dead.alloc(1);
     dead.zero(g.stream);
     M.alloc((size_t)npad * npad);
     M.zero(g.stream);
     hipLaunchKernelGGL(k_mv_dense_assemble, dim3(grid1(npad)), dim3(256), 0, g.stream, n, npad, L0.sl_off.p, L0.col.p,
                        g.slot_eid.p, g.bptr.p, g.beid.p, g.bflag.p, g.dw.p, M.p);
-    DevBuf<double> sc;
     sc.alloc((size_t)npad);
     hipLaunchKernelGGL(k_mv_dense_diag, dim3(grid1(npad)), dim3(256), 0, g.stream, npad, M.p, sc.p, dead.p);
     if (read_dead(g, dead)) return IROTAVG_ERR_SOLVER;
     hipLaunchKernelGGL(k_mv_dense_scale, dim3(grid1((long long)npad * npad)), dim3(256), 0, g.stream, npad, M.p, sc.p);
     invert_own(g, M.p, npad);
     // every diagonal entry of the inverse is positive unless a pivot was dead (its row and column come back zero)
-    dvar.alloc((size_t)n);
-    hipLaunchKernelGGL(k_mv_dense_var, dim3(grid1(n)), dim3(256), 0, g.stream, n, npad, M.p, sc.p, dvar.p, dead.p);
+    Dn.dvar.alloc((size_t)n);
+    hipLaunchKernelGGL(k_mv_dense_var, dim3(grid1(n)), dim3(256), 0, g.stream, n, npad, M.p, sc.p, Dn.dvar.p, dead.p);
     if (read_dead(g, dead)) return IROTAVG_ERR_SOLVER;
+    return IROTAVG_OK;
+}
+
+namespace {
+
+int band_path(Graph &g, bool want_var, std::vector<double> &var, const std::vector<int> &pi,
+              const std::vector<int> &pj, std::vector<double> &pv) {
+    BandFactor F;
+    BandClosures C;
+    DevBuf<int> dead;
+    const int rc = band_setup(g, F, C, dead);
+    if (rc != IROTAVG_OK) return rc;
+    if (want_var) {
+        DevBuf<double> corr, dvar;
+        F.select(g);
+        if (C.k > 0) {
+            corr.alloc((size_t)C.nrowsZ);
+            hipLaunchKernelGGL(k_mv_wcorr, dim3(C.nrowsZ / 64), dim3(256), 0, g.stream, C.ldZ, C.Z.p, C.S.p, C.ldZ,
+                               corr.p);
+        }
+        dvar.alloc((size_t)F.n);
+        hipLaunchKernelGGL(k_mv_band_var, dim3(grid1(F.n)), dim3(256), 0, g.stream, F.n, F.B, F.D.p,
+                           C.k > 0 ? corr.p : nullptr, dvar.p, dead.p);
+        var.resize((size_t)F.n);
+        IRH_CHECK(hipMemcpyAsync(var.data(), dvar.p, sizeof(double) * F.n, hipMemcpyDeviceToHost, g.stream));
+        if (read_dead(g, dead)) return IROTAVG_ERR_SOLVER;
+    }
+    band_pairs(g, F, C, pi, pj, pv);
+    IRH_CHECK(hipStreamSynchronize(g.stream));
+    return IROTAVG_OK;
+}
+
+int dense_path(Graph &g, bool want_var, std::vector<double> &var, const std::vector<int> &pi,
+               const std::vector<int> &pj, std::vector<double> &pv) {
+    DenseInverse Dn;
+    DevBuf<int> dead;
+    const int rc = dense_inverse(g, Dn, dead);
+    if (rc != IROTAVG_OK) return rc;
+    const int n = Dn.n, npad = Dn.npad;
     if (want_var) {
         var.resize((size_t)n);
-        IRH_CHECK(hipMemcpyAsync(var.data(), dvar.p, sizeof(double) * n, hipMemcpyDeviceToHost, g.stream));
+        IRH_CHECK(hipMemcpyAsync(var.data(), Dn.dvar.p, sizeof(double) * n, hipMemcpyDeviceToHost, g.stream));
     }
     const int np = (int)pi.size();
     pv.assign((size_t)np, 0.0);
@@ -702,8 +721,8 @@ int dense_path(Graph &g, bool want_var, std::vector<double> &var, const std::vec
         da.upload(a, g.stream);
         db.upload(b, g.stream);
         dpv.alloc((size_t)np);
-        hipLaunchKernelGGL(k_mv_dense_pairs, dim3(grid1(np)), dim3(256), 0, g.stream, np, npad, da.p, db.p, M.p, sc.p,
-                           dpv.p);
+        hipLaunchKernelGGL(k_mv_dense_pairs, dim3(grid1(np)), dim3(256), 0, g.stream, np, npad, da.p, db.p, Dn.M.p,
+                           Dn.sc.p, dpv.p);
         IRH_CHECK(hipMemcpyAsync(pv.data(), dpv.p, sizeof(double) * np, hipMemcpyDeviceToHost, g.stream));
     }
     IRH_CHECK(hipStreamSynchronize(g.stream));
