@@ -43,7 +43,7 @@ extern "C" {
                                           coarse inverse and, on a single level of <= 1024 views, tried the dense
                                           Cholesky solve; the iterate reached so far is left in place */
 #define IROTAVG_ERR_UNSUPPORTED (-9)  /* the query is not available on this kind of handle (irotavg_graph_rotation_variance,
-                                         irotavg_graph_edge_diagnostics) */
+                                         irotavg_graph_edge_diagnostics, the view-graph queries built on them) */
 
 /* ral/l1_irls.hpp:56-57 -- the integer values are ABI */
 enum irotavg_cost {
@@ -222,6 +222,11 @@ int irotavg_graph_synchronize(irotavg_graph *g);
 
 /* K1: r_k = log(Qinv_j (x) QQ_k (x) Q_i) for every edge (ral/l1_irls.cpp:109-127 + :498-532). */
 int irotavg_graph_edge_residual(irotavg_graph *g);
+/* K1 and K2 at a zero step in one pass over the edges: the residuals of the handle's current rotations go into the
+ * residual planes (bit for bit what irotavg_graph_edge_residual leaves) and the weights become the cost's weights of those
+ * residuals (all 14 costs; L2 and Huber inliers keep the handle's current value, as irotavg_graph_update_weights does).
+ * "The uncertainty at these rotations" for irotavg_graph_rotation_variance / _edge_diagnostics without an irls. */
+int irotavg_graph_pose_weights(irotavg_graph *g, int cost, double sigma);
 /* D2H of the residual rows: out is m x 3 column-major, ld >= m. They are what the last irotavg_graph_edge_residual call
  * computed; irotavg_graph_irls / _l1ra use the planes as scratch and leave them unspecified (the residuals of the
  * rotations before OR after the last step, depending on the solver path). */
@@ -245,7 +250,8 @@ int irotavg_graph_l1decode_pd(irotavg_graph *g, const double *y, int pdmaxiter, 
  * 7 = dense coarse-level inversion (blocked Gauss-Jordan), 8 = the PCG p-update fused into the
  * level-0 SpMV (what a single-GPU solve of a graph without far entries runs instead of 4;
  * IROTAVG_ERR_BAD_ARG if this graph's PCG does not use it), 11 = K2 and the next iteration's K1 in one pass over the
- * edges (what the direct solver's irls loop runs from its second iteration on). */
+ * edges (what the direct solver's irls loop runs from its second iteration on), 12 = K1 and the weights of a zero step in
+ * one pass (irotavg_graph_pose_weights). */
 int irotavg_graph_time_kernel(irotavg_graph *g, int which, int reps, double *ms_per_launch);
 
 /* The banded direct solver of this handle (options.band_direct; irotavg_amd/csrc/bcr.hip): info[0] = block size (0: the
@@ -371,6 +377,46 @@ int irotavg_viewgraph_prepare(irotavg_viewgraph *vg);
  * window -- one window alone keeps 1 of the 256 compute units busy --, the others run one by one. Results are
  * those of n separate irotavg_viewgraph_rot_avg calls. infos: n entries or NULL. Returns the first error. */
 int irotavg_viewgraph_rot_avg_batch(irotavg_viewgraph *const *vgs, int n, int win_size, irotavg_rotavg_info *infos);
+
+/* Uncertainty queries on the view-graph (docs/viewgraph_uncertainty.md). All three are defined on the problem
+ * irotavg_viewgraph_rot_avg(win_size) would solve NOW -- the same connections in the same order, the touched views
+ * relabelled fixed-first, a global problem when win_size >= the number of views -- at the current poses, with the weights
+ * d_k = 1 / (|r_k|^2 + sigma^2) (Geman-McClure, sigma = 5 degrees: rot_avg's cost at a zero step), and M, Sigma, s^2,
+ * edge_var, leverage, chi2 as irotavg_graph_rotation_variance / irotavg_graph_edge_diagnostics define them. None moves a
+ * pose; the answers depend on the view-graph's state alone (poses, connections, fixed mask). A problem without a fixed
+ * pose holds its row 0 at the pose it has (rot_avg would hold it at the identity). Where rot_avg would skip: IROTAVG_OK,
+ * info->skipped set, every output NaN (conn: -1). Window-size problems (<= 64 free views, <= 640 edges, <= 320 views) run
+ * as ONE kernel launch (irotavg_amd/csrc/wincov.hip), larger ones through a graph handle -- built on the device from
+ * rot_avg's resident records where a global re-solve would run there, with the same delta upload -- and the handle queries (their
+ * routes and errors: IROTAVG_ERR_UNSUPPORTED for var / edge diagnostics on a multigrid-PCG graph, IROTAVG_ERR_SOLVER for a
+ * singular M, outputs untouched). Bad ids / counts: IROTAVG_ERR_BAD_ARG before any device work. */
+typedef struct irotavg_uncertainty_info {
+    int skipped, n_views, n_edges, n_fixed; /* as irotavg_rotavg_info */
+    int route;                              /* 1 window kernel, 2 dense inverse, 3 banded direct solver, 4 PCG (pairs only) */
+    int closures;                           /* loop closures the band route carried */
+    double scale;                           /* s^2 */
+} irotavg_uncertainty_info;
+/* var[v] (num_views entries, caller's view ids, or NULL): Sigma's entry of a free view of the problem, 0 for a view the
+ * problem holds (fixed, or outside the window), NaN for a view that is not in the problem. pair_var[t] = u' Sigma u for
+ * (pairs[2t], pairs[2t+1]): 0 when both are held, NaN when either is absent. */
+int irotavg_viewgraph_rotation_variance(irotavg_viewgraph *vg, int win_size, double *var, int64_t npairs,
+                                        const int32_t *pairs, double *pair_var, irotavg_uncertainty_info *info /* may be NULL */);
+/* edges of that problem (0 where rot_avg would skip), or a negative error */
+int64_t irotavg_viewgraph_num_connections(irotavg_viewgraph *vg, int win_size);
+/* conn: 2*cap view ids (i, j) of the problem's edges in problem order, edge_var / leverage / chi2: cap each; any may be
+ * NULL. Returns the number of edges, or a negative error (cap too small: IROTAVG_ERR_BAD_ARG). */
+int64_t irotavg_viewgraph_edge_diagnostics(irotavg_viewgraph *vg, int win_size, int64_t cap, int32_t *conn,
+                                           double *edge_var, double *leverage, double *chi2,
+                                           irotavg_uncertainty_info *info /* may be NULL */);
+/* The statistical gate in front of irotavg_viewgraph_connect: each candidate (pairs[2c], pairs[2c+1], Rij + 9c, as connect
+ * takes them; i != j) is a new, independent measurement, also when the pair is connected already; nothing is added to
+ * the graph. angle[c] = |r_c|, K1's residual of the candidate at the current poses (rad); pair_var[c] as above;
+ * chi2[c] = |r_c|^2 / (s^2 (pair_var[c] + sigma^4)), approximately chi-square with 3 degrees of freedom (sigma^4 = 1 / d0^2,
+ * d0 = 1 / sigma^2 the weight a zero-residual measurement gets); NaN when s^2 is NaN or a view is not in the problem.
+ * ncand entries each, or NULL. */
+int irotavg_viewgraph_gate_connections(irotavg_viewgraph *vg, int win_size, int64_t ncand, const int32_t *pairs,
+                                       const double *Rij, double *angle, double *pair_var, double *chi2,
+                                       irotavg_uncertainty_info *info /* may be NULL */);
 
 /* rmat2quat (src/ViewGraph.cpp:1175-1203) / q.normalized().toRotationMatrix() (:1426-1433);
  * row-major R, q = [x y z w] */

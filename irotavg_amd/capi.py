@@ -43,6 +43,8 @@ SYMBOLS = [
     "irotavg_dist_timing",
     "irotavg_graph_rotation_variance", "irotavg_rotation_variance",
     "irotavg_graph_edge_diagnostics", "irotavg_edge_diagnostics",
+    "irotavg_graph_pose_weights", "irotavg_viewgraph_rotation_variance", "irotavg_viewgraph_num_connections",
+    "irotavg_viewgraph_edge_diagnostics", "irotavg_viewgraph_gate_connections",
 ]
 
 
@@ -71,6 +73,11 @@ class RotAvgInfo(C.Structure):
     _fields_ = [("skipped", C.c_int), ("n_views", C.c_int), ("n_edges", C.c_int), ("n_fixed", C.c_int),
                 ("l1_iters", C.c_int), ("irls_iters", C.c_int), ("l1_runtime", C.c_double),
                 ("irls_runtime", C.c_double)]
+
+
+class UncertaintyInfo(C.Structure):
+    _fields_ = [("skipped", C.c_int), ("n_views", C.c_int), ("n_edges", C.c_int), ("n_fixed", C.c_int),
+                ("route", C.c_int), ("closures", C.c_int), ("scale", C.c_double)]
 
 
 class IrotavgError(RuntimeError):
@@ -145,6 +152,15 @@ def lib():
     L.irotavg_graph_edge_diagnostics.argtypes = [vp, _dp, _dp, _dp, _dp]
     L.irotavg_edge_diagnostics.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
                                            _dp, _dp, _dp, _dp]
+    L.irotavg_graph_pose_weights.argtypes = [vp, C.c_int, C.c_double]
+    L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
+    L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
+    L.irotavg_viewgraph_num_connections.restype = C.c_int64
+    L.irotavg_viewgraph_edge_diagnostics.argtypes = [vp, C.c_int, C.c_int64, _ip, _dp, _dp, _dp,
+                                                     C.POINTER(UncertaintyInfo)]
+    L.irotavg_viewgraph_edge_diagnostics.restype = C.c_int64
+    L.irotavg_viewgraph_gate_connections.argtypes = [vp, C.c_int, C.c_int64, _ip, _dp, _dp, _dp, _dp,
+                                                     C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_create.argtypes = [C.POINTER(vp), C.POINTER(Options)]
     L.irotavg_viewgraph_destroy.argtypes = [vp]
     L.irotavg_viewgraph_destroy.restype = None
@@ -400,6 +416,10 @@ class Graph:
         (docs/edge_diagnostics.md)."""
         return _edge_call(lambda *a: lib().irotavg_graph_edge_diagnostics(self._h, *a), self.m, edge_var, leverage,
                           chi2, allow_rc, "irotavg_graph_edge_diagnostics")
+
+    def pose_weights(self, cost, sigma):
+        """irotavg_graph_pose_weights: residuals of the current rotations + the cost's weights at a zero step, one pass."""
+        check(lib().irotavg_graph_pose_weights(self._h, int(cost), float(sigma)), "irotavg_graph_pose_weights")
 
     def fingerprint(self):
         """Hashes of every structural array + the kernel-choosing scalars (irotavg_graph_fingerprint)."""

@@ -457,6 +457,17 @@ int irotavg_graph_edge_residual(irotavg_graph *h) {
     API_CATCH
 }
 
+// the cost's weights at the handle's current rotations (a zero step) and the residuals of those rotations, one pass
+int irotavg_graph_pose_weights(irotavg_graph *h, int cost, double sigma) {
+    if (!h) return IROTAVG_ERR_BAD_ARG;
+    if (cost < IROTAVG_L2 || cost > IROTAVG_WELSCH) return IROTAVG_ERR_UNKNOWN_COST;
+    API_TRY
+    launch_pose_weights(h->g, cost, sigma);
+    IRH_CHECK(hipStreamSynchronize(h->g.stream));
+    return IROTAVG_OK;
+    API_CATCH
+}
+
 int irotavg_graph_get_residuals(irotavg_graph *h, double *out, int64_t ld) {
     if (!h || !out || ld < h->g.m) return IROTAVG_ERR_BAD_ARG;
     API_TRY

@@ -291,6 +291,31 @@ struct WinBatchItem {  // one problem of a batched launch: inputs as window_solv
 };
 int window_solve_batch(WindowSolver &ws, int nb, WinBatchItem *items, int l1_max, int irls_max, int cost, double sigma,
                        double change_th);
+// wincov.hip: the uncertainty queries of a window-size problem in one kernel launch (docs/viewgraph_uncertainty.md)
+struct WinCov;
+WinCov *wincov_new();
+void wincov_delete(WinCov *w);
+struct WinCovQuery {
+    int nv, f, ne;                  // a problem window_fits accepts
+    const int32_t *I;               // ne pairs of rows
+    const double *qq_aos, *Q_aos;   // 4 per edge / per view, [x y z w]
+    double sigma;
+    double *var;                    // OUT nv - f (or nullptr)
+    double *edge_var, *leverage, *chi2;  // OUT ne each (or nullptr)
+    int np;
+    const int32_t *prow;            // 2 np operator rows (+1, -1 coefficient; -1: held view, below: not in the problem -> NaN)
+    double *pair_var;               // OUT np
+    int nc;
+    const int32_t *crow;            // 2 nc operator rows of the candidates' ends, as prow
+    const double *cq;               // 12 per candidate: the quaternions of its lower view, its higher view, its R
+    double *angle, *cand_var, *cand_chi2;  // OUT nc each
+    double s2;                      // OUT
+};
+int wincov_query(WinCov &wc, WinCovQuery &q);  // IROTAVG_ERR_SOLVER: singular, outputs untouched
+// solver.hip: K1 + the robust weight at a zero step in one pass over the edges (irotavg_graph_pose_weights); the residual
+// norms of free-standing measurements (lower view, higher view, relative rotation: 3 quaternions each)
+void launch_pose_weights(Graph &g, int cost, double sigma);
+void candidate_angles(Graph &g, int64_t n, const double *q12, double *angle);
 // bcr.hip
 void bcr_plan(Graph &g, const int32_t *I);  // sets Graph::bcr_B / band0 (capi.cpp, ahead of the build)
 void bcr_plan_dev(Graph &g, const DevEdgeSrc &src);  // the same from an edge list on the device (needs g.stream)
@@ -396,6 +421,10 @@ ResidentStage resident_stage(Resident &r, long n_views, long view_lo, long n_edg
 int resident_rot_avg(Resident &r, long n_views, long view_lo, long n_edges, long edge_lo, int f,
                      const irotavg_options &opt, const Switches &sw, irotavg_rotavg_info &loc, bool timing, bool dry = false,
                      int dry_a = -1, int dry_b = -1);
+
+// the prologue of resident_rot_avg alone (deltas, relabelling, device build, poses): the handle of the global problem
+int resident_build_handle(Resident &r, long n_views, long view_lo, long n_edges, long edge_lo, int f,
+                          const irotavg_options &opt, const Switches &sw, irotavg_graph **out);
 
 inline double now_seconds() {
     using namespace std::chrono;

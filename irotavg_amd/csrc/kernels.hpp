@@ -312,6 +312,32 @@ __device__ __forceinline__ double4 qmul(const double4 a, const double4 b) {
     return r;
 }
 
+#define IRH_PI 3.141592653589793238462643383279502884
+#define IRH_EPS 2.2204e-16  // ral/l1_irls.hpp:40
+
+// K1's residual of one edge: delta_rel + log_map (ral/l1_irls.cpp:109-127, 498-532). The one copy every kernel that needs
+// "the residual K1 computes" uses (solver.hip's edge passes, wincov.hip).
+__device__ __forceinline__ void edge_log(const double4 qi, double4 qj, const double4 qq,
+                                         double &ox, double &oy, double &oz) {
+    qj.w = -qj.w;  // the reference's "inverse": only w negated (ral/l1_irls.cpp:114-115)
+    const double4 d = qmul(qj, qmul(qq, qi));
+    const double s2 = sqrt(d.x * d.x + d.y * d.y + d.z * d.z);
+    double th = 2.0 * atan2(s2, d.w);
+    if (th < -IRH_PI)  // wrap into [-pi, pi) (ral/l1_irls.cpp:510-517)
+        th += 2.0 * IRH_PI;
+    else if (th >= IRH_PI)
+        th -= 2.0 * IRH_PI;
+    const double aux = th / s2;
+    ox = d.x * aux;
+    oy = d.y * aux;
+    oz = d.z * aux;
+    if (s2 < IRH_EPS) {  // ral/l1_irls.cpp:527-531
+        ox = 0.0;
+        oy = 0.0;
+        oz = 0.0;
+    }
+}
+
 // One view's share of K6 (ral/l1_irls.cpp:729-737, exp_map :471-492): returns ||x|| (the view's term of the score, taken
 // BEFORE the exp map), Q[idx] <- Q[idx] (x) exp(x) (right-multiply, no renormalisation; every non-finite entry of the
 // exponential -> 0, :491). A step that is not finite leaves its rotation alone (the score turns non-finite instead).

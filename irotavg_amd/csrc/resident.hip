@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 
 #include "graph.hpp"
 
@@ -187,6 +188,107 @@ ResidentStage resident_stage(Resident &r, long n_views, long view_lo, long n_edg
     return st;
 }
 
+namespace {
+// What a call on the resident graph starts with, shared by the global re-solve and the view-graph's uncertainty queries
+// (docs/viewgraph_uncertainty.md): upload the deltas staged by resident_stage, relabel fixed-first, build the solver's
+// handle on the device from the resident records, gather the poses as its rotations. Throws like the code around it;
+// *h is the caller's to destroy, also when this throws after the build.
+int resident_prologue(Resident &r, long n_views, long view_lo, long n_edges, long edge_lo, int f, const irotavg_options &opt,
+                      const Switches &sw, bool dry, int dry_a, int dry_b, bool timing,
+                      const std::function<void(const char *)> &lap, irotavg_graph **h) {
+    if (opt.device >= 0) IRH_CHECK(hipSetDevice(opt.device));
+    if (!r.stream) {
+        IRH_CHECK(hipGetDevice(&r.device));
+        r.stream = StreamPool::get().take();
+    }
+    hipStream_t s = r.stream;
+    const size_t nv = (size_t)n_views, ne = (size_t)n_edges;
+    grow_keep(r.I, (size_t)edge_lo, ne + 1, s);
+    grow_keep(r.QQ, (size_t)edge_lo, ne + 1, s);
+    grow_keep(r.R, 9 * (size_t)view_lo, 9 * nv, s);
+    grow_keep(r.fixed, (size_t)view_lo, nv, s);
+    if (r.flag.n < nv + 1) {
+        r.flag.alloc(nv + nv / 2 + 1024);
+        r.before.alloc(r.flag.n);
+        r.v2i.alloc(r.flag.n);
+        r.qout.alloc(r.flag.n);
+    }
+    const size_t dv = nv - (size_t)view_lo, de = ne - (size_t)edge_lo;
+    if (de > 0) {
+        IRH_CHECK(hipMemcpyAsync(r.I.p + edge_lo, r.hI.p, sizeof(int2) * de, hipMemcpyHostToDevice, s));
+        IRH_CHECK(hipMemcpyAsync(r.QQ.p + edge_lo, r.hqq.p, sizeof(double4) * de, hipMemcpyHostToDevice, s));
+    }
+    if (dv > 0) {
+        IRH_CHECK(hipMemcpyAsync(r.R.p + 9 * (size_t)view_lo, r.hR.p, sizeof(double) * 9 * dv, hipMemcpyHostToDevice, s));
+        IRH_CHECK(hipMemcpyAsync(r.fixed.p + view_lo, r.hfixed.p, dv, hipMemcpyHostToDevice, s));
+    }
+    r.n_views = n_views;
+    r.n_edges = n_edges;
+    long ne_solve = n_edges;
+    if (dry && dry_a >= 0 && dry_b > dry_a && dry_b < n_views) {  // the made-up closure (never part of the resident records)
+        const int2 e = make_int2(dry_a, dry_b);
+        const double4 q = make_double4(0.0, 0.0, 0.0, 1.0);
+        IRH_CHECK(hipMemcpyAsync(r.I.p + ne, &e, sizeof(e), hipMemcpyHostToDevice, s));
+        IRH_CHECK(hipMemcpyAsync(r.QQ.p + ne, &q, sizeof(q), hipMemcpyHostToDevice, s));
+        IRH_CHECK(hipStreamSynchronize(s));
+        ne_solve = n_edges + 1;
+    }
+    // ---- fixed-first relabelling (src/ViewGraph.cpp:1323-1363): a scan over the mask
+    hipLaunchKernelGGL(k_res_flags, dim3(grid_of(n_views)), dim3(kT), 0, s, (int)n_views, r.fixed.p, r.flag.p);
+    {
+        size_t bytes = 0;
+        IRH_CHECK(rocprim::exclusive_scan(nullptr, bytes, r.flag.p, r.before.p, 0, nv, rocprim::plus<int>(), s));
+        if (r.scan_tmp.n < bytes) r.scan_tmp.alloc(bytes + 4096);
+        IRH_CHECK(rocprim::exclusive_scan(r.scan_tmp.p, bytes, r.flag.p, r.before.p, 0, nv, rocprim::plus<int>(), s));
+    }
+    hipLaunchKernelGGL(k_res_relabel, dim3(grid_of(n_views)), dim3(kT), 0, s, (int)n_views, f, r.fixed.p, r.before.p,
+                       r.v2i.p);
+    IRH_CHECK(hipStreamSynchronize(s));  // the build runs on the handle's own stream
+    lap("delta upload + relabel");
+    // ---- the solver's handle, built on the device from the resident records
+    DevEdgeSrc src;
+    src.I = r.I.p;
+    src.QQ = r.QQ.p;
+    src.relabel = r.v2i.p;
+    const int rc = graph_create(h, ne_solve, n_views, f, nullptr, nullptr, 0, &opt, &src, sw);
+    if (rc != IROTAVG_OK) return rc;
+    Graph &g = graph_of(*h);
+    g.pool_headroom = true;
+    hipLaunchKernelGGL(k_res_gather, dim3(grid_of(n_views)), dim3(kT), 0, g.stream, (int)n_views, r.R.p, r.v2i.p, g.Q.p);
+    if (timing) (void)hipStreamSynchronize(g.stream);
+    lap("handle (device build)");
+    return IROTAVG_OK;
+}
+}  // namespace
+
+// The handle of the global problem on the resident graph, at the poses the graph has (staging and marks as for
+// resident_rot_avg): for the uncertainty queries. *out is the caller's to destroy. Nothing on the device changes
+// beyond the upload of the deltas, so a later resident_rot_avg finds what it would have sent itself.
+int resident_build_handle(Resident &r, long n_views, long view_lo, long n_edges, long edge_lo, int f,
+                          const irotavg_options &opt, const Switches &sw, irotavg_graph **out) {
+    if (view_lo > r.n_views || edge_lo > r.n_edges || view_lo < 0 || edge_lo < 0 || f <= 0 || f >= n_views || !out)
+        return IROTAVG_ERR_BAD_ARG;
+    irotavg_graph *h = nullptr;
+    int rc = IROTAVG_ERR_HIP;
+    try {
+        DevPool::HeadroomScope headroom;
+        rc = resident_prologue(r, n_views, view_lo, n_edges, edge_lo, f, opt, sw, false, -1, -1, false,
+                               [](const char *) {}, &h);
+        if (rc == IROTAVG_OK) IRH_CHECK(hipStreamSynchronize(graph_of(h).stream));
+    } catch (const std::bad_alloc &) {
+        rc = IROTAVG_ERR_NOMEM;
+    } catch (...) {
+        rc = IROTAVG_ERR_HIP;
+    }
+    if (rc != IROTAVG_OK) {
+        if (h) irotavg_graph_destroy(h);
+        resident_invalidate(r);
+        return rc;
+    }
+    *out = h;
+    return IROTAVG_OK;
+}
+
 // One global re-solve on the resident graph. The staging blocks of resident_stage hold the records of the views
 // [view_lo, n_views) and of the edges [edge_lo, n_edges); everything below those marks must be what the device holds.
 // f = fixed views (> 0). On success st.Q (n_views x 4, AoS) holds the solved quaternion of every free view.
@@ -209,70 +311,13 @@ int resident_rot_avg(Resident &r, long n_views, long view_lo, long n_edges, long
     };
     irotavg_graph *h = nullptr;
     try {
-        if (opt.device >= 0) IRH_CHECK(hipSetDevice(opt.device));
-        if (!r.stream) {
-            IRH_CHECK(hipGetDevice(&r.device));
-            r.stream = StreamPool::get().take();
-        }
-        hipStream_t s = r.stream;
-        const size_t nv = (size_t)n_views, ne = (size_t)n_edges;
-        grow_keep(r.I, (size_t)edge_lo, ne + 1, s);
-        grow_keep(r.QQ, (size_t)edge_lo, ne + 1, s);
-        grow_keep(r.R, 9 * (size_t)view_lo, 9 * nv, s);
-        grow_keep(r.fixed, (size_t)view_lo, nv, s);
-        if (r.flag.n < nv + 1) {
-            r.flag.alloc(nv + nv / 2 + 1024);
-            r.before.alloc(r.flag.n);
-            r.v2i.alloc(r.flag.n);
-            r.qout.alloc(r.flag.n);
-        }
-        const size_t dv = nv - (size_t)view_lo, de = ne - (size_t)edge_lo;
-        if (de > 0) {
-            IRH_CHECK(hipMemcpyAsync(r.I.p + edge_lo, r.hI.p, sizeof(int2) * de, hipMemcpyHostToDevice, s));
-            IRH_CHECK(hipMemcpyAsync(r.QQ.p + edge_lo, r.hqq.p, sizeof(double4) * de, hipMemcpyHostToDevice, s));
-        }
-        if (dv > 0) {
-            IRH_CHECK(hipMemcpyAsync(r.R.p + 9 * (size_t)view_lo, r.hR.p, sizeof(double) * 9 * dv, hipMemcpyHostToDevice, s));
-            IRH_CHECK(hipMemcpyAsync(r.fixed.p + view_lo, r.hfixed.p, dv, hipMemcpyHostToDevice, s));
-        }
-        r.n_views = n_views;
-        r.n_edges = n_edges;
-        long ne_solve = n_edges;
-        if (dry && dry_a >= 0 && dry_b > dry_a && dry_b < n_views) {  // the made-up closure (never part of the resident records)
-            const int2 e = make_int2(dry_a, dry_b);
-            const double4 q = make_double4(0.0, 0.0, 0.0, 1.0);
-            IRH_CHECK(hipMemcpyAsync(r.I.p + ne, &e, sizeof(e), hipMemcpyHostToDevice, s));
-            IRH_CHECK(hipMemcpyAsync(r.QQ.p + ne, &q, sizeof(q), hipMemcpyHostToDevice, s));
-            IRH_CHECK(hipStreamSynchronize(s));
-            ne_solve = n_edges + 1;
-        }
-        // ---- fixed-first relabelling (src/ViewGraph.cpp:1323-1363): a scan over the mask
-        hipLaunchKernelGGL(k_res_flags, dim3(grid_of(n_views)), dim3(kT), 0, s, (int)n_views, r.fixed.p, r.flag.p);
-        {
-            size_t bytes = 0;
-            IRH_CHECK(rocprim::exclusive_scan(nullptr, bytes, r.flag.p, r.before.p, 0, nv, rocprim::plus<int>(), s));
-            if (r.scan_tmp.n < bytes) r.scan_tmp.alloc(bytes + 4096);
-            IRH_CHECK(rocprim::exclusive_scan(r.scan_tmp.p, bytes, r.flag.p, r.before.p, 0, nv, rocprim::plus<int>(), s));
-        }
-        hipLaunchKernelGGL(k_res_relabel, dim3(grid_of(n_views)), dim3(kT), 0, s, (int)n_views, f, r.fixed.p, r.before.p,
-                           r.v2i.p);
-        IRH_CHECK(hipStreamSynchronize(s));  // the build runs on the handle's own stream
-        lap("delta upload + relabel");
-        // ---- the solver's handle, built on the device from the resident records
-        DevEdgeSrc src;
-        src.I = r.I.p;
-        src.QQ = r.QQ.p;
-        src.relabel = r.v2i.p;
+        const size_t nv = (size_t)n_views;
         // (the handle of a growing graph and everything its solves allocate: blocks half as large again, so that the next
         // re-solves find them in the pool)
         DevPool::HeadroomScope headroom;  // this thread; the handle's worker threads follow its flag (Graph::pool_headroom)
-        int rc = graph_create(&h, ne_solve, n_views, f, nullptr, nullptr, 0, &opt, &src, sw);
+        int rc = resident_prologue(r, n_views, view_lo, n_edges, edge_lo, f, opt, sw, dry, dry_a, dry_b, timing, lap, &h);
         if (rc != IROTAVG_OK) return rc;
         Graph &g = graph_of(h);
-        g.pool_headroom = true;
-        hipLaunchKernelGGL(k_res_gather, dim3(grid_of(n_views)), dim3(kT), 0, g.stream, (int)n_views, r.R.p, r.v2i.p, g.Q.p);
-        if (timing) (void)hipStreamSynchronize(g.stream);
-        lap("handle (device build)");
         // ---- solve (src/ViewGraph.cpp:1396-1417)
         const double change_th = .001;
         rc = irotavg_graph_l1ra(h, 100, change_th, &loc.l1_iters, &loc.l1_runtime, nullptr);

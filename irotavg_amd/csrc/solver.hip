@@ -13,34 +13,12 @@
 
 namespace irh {
 
-#define IRH_PI 3.141592653589793238462643383279502884
-#define IRH_EPS 2.2204e-16  // ral/l1_irls.hpp:40
+// (IRH_PI, IRH_EPS and K1's edge_log: kernels.hpp)
 
 // =============================================================================================
 // K1 -- edge residual. Two edges per thread so every SoA stream moves as 16 B per lane.
 // Algorithmic traffic: 8 B indices + 32 B QQ + 24 B out per edge, 32 B per view.
 // =============================================================================================
-__device__ __forceinline__ void edge_log(const double4 qi, double4 qj, const double4 qq,
-                                         double &ox, double &oy, double &oz) {
-    qj.w = -qj.w;  // the reference's "inverse": only w negated (ral/l1_irls.cpp:114-115)
-    const double4 d = qmul(qj, qmul(qq, qi));
-    const double s2 = sqrt(d.x * d.x + d.y * d.y + d.z * d.z);
-    double th = 2.0 * atan2(s2, d.w);
-    if (th < -IRH_PI)  // wrap into [-pi, pi) (ral/l1_irls.cpp:510-517)
-        th += 2.0 * IRH_PI;
-    else if (th >= IRH_PI)
-        th -= 2.0 * IRH_PI;
-    const double aux = th / s2;
-    ox = d.x * aux;
-    oy = d.y * aux;
-    oz = d.z * aux;
-    if (s2 < IRH_EPS) {  // ral/l1_irls.cpp:527-531
-        ox = 0.0;
-        oy = 0.0;
-        oz = 0.0;
-    }
-}
-
 __global__ __launch_bounds__(256) void k_edge_residual(long long mpad, const int *__restrict__ ei,
                                                        const int *__restrict__ ej,
                                                        const double *__restrict__ qq,
@@ -220,6 +198,74 @@ void launch_update_weights(Graph &g, int cost, double sigma, bool gated) {
     else
         hipLaunchKernelGGL((k_update_weights<false, 2>), dim3(grid), dim3(256), 0, g.stream, (long long)g.m, (long long)g.mpad, g.f,
                            g.ei.p, g.ej.p, g.er.p, g.X.p, cost, sigma, g.dw.p, gate, skip);
+}
+
+// K1 and K2 at a ZERO step in one pass over the edges (irotavg_graph_pose_weights; the view-graph's uncertainty queries):
+// the residuals of the current rotations into the planes, and the cost's weight of |0 - r_k|^2 into dw. No step vector is
+// read. Two edges per thread, 16 B per lane and stream, as K1. Algorithmic traffic: 8 B indices + 32 B relative rotation
+// in, 24 B residual + 8 B weight out per edge (+ 8 B old weight for the costs that keep previous values), 32 B per view.
+template <bool PREV>
+__global__ __launch_bounds__(256) void k_pose_weights(long long m, long long mpad, const int *__restrict__ ei,
+                                                      const int *__restrict__ ej, const double *__restrict__ qq,
+                                                      const double4 *__restrict__ Q, double *__restrict__ er, int cost,
+                                                      double sigma, double *__restrict__ dw) {
+    const long long k = 2ll * ((long long)blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= mpad) return;
+    const int2 ii = *reinterpret_cast<const int2 *>(ei + k);
+    const int2 jj = *reinterpret_cast<const int2 *>(ej + k);
+    const double2 qx = *reinterpret_cast<const double2 *>(qq + k);
+    const double2 qy = *reinterpret_cast<const double2 *>(qq + mpad + k);
+    const double2 qz = *reinterpret_cast<const double2 *>(qq + 2 * mpad + k);
+    const double2 qw = *reinterpret_cast<const double2 *>(qq + 3 * mpad + k);
+    const double4 qi0 = Q[ii.x], qj0 = Q[jj.x], qi1 = Q[ii.y], qj1 = Q[jj.y];
+    double2 prev = make_double2(0.0, 0.0);
+    if (PREV && k < m) prev = *reinterpret_cast<const double2 *>(dw + k);
+    double2 rx, ry, rz;
+    edge_log(qi0, qj0, make_double4(qx.x, qy.x, qz.x, qw.x), rx.x, ry.x, rz.x);
+    edge_log(qi1, qj1, make_double4(qx.y, qy.y, qz.y, qw.y), rx.y, ry.y, rz.y);
+    *reinterpret_cast<double2 *>(er + k) = rx;
+    *reinterpret_cast<double2 *>(er + mpad + k) = ry;
+    *reinterpret_cast<double2 *>(er + 2 * mpad + k) = rz;
+    if (k >= m) return;
+    // step_residual2 with X = 0: e = -r
+    const double wa = robust_weight(cost, sigma, rx.x * rx.x + ry.x * ry.x + rz.x * rz.x, prev.x);
+    if (k + 1 < m)
+        *reinterpret_cast<double2 *>(dw + k) =
+            make_double2(wa, robust_weight(cost, sigma, rx.y * rx.y + ry.y * ry.y + rz.y * rz.y, prev.y));
+    else
+        dw[k] = wa;  // the pad entry behind an odd m keeps its value
+}
+
+void launch_pose_weights(Graph &g, int cost, double sigma) {
+    const int grid = (int)((g.mpad / 2 + 255) / 256);
+    if (cost == IROTAVG_L2 || cost == IROTAVG_HUBER)
+        hipLaunchKernelGGL((k_pose_weights<true>), dim3(grid), dim3(256), 0, g.stream, (long long)g.m, (long long)g.mpad,
+                           g.ei.p, g.ej.p, g.qq.p, g.Q.p, g.er.p, cost, sigma, g.dw.p);
+    else
+        hipLaunchKernelGGL((k_pose_weights<false>), dim3(grid), dim3(256), 0, g.stream, (long long)g.m, (long long)g.mpad,
+                           g.ei.p, g.ej.p, g.qq.p, g.Q.p, g.er.p, cost, sigma, g.dw.p);
+}
+
+// |r| of measurements that are not edges of the handle (the closure gate's candidates): per measurement the quaternions
+// of its first view, its second view and its relative rotation
+__global__ __launch_bounds__(256) void k_candidate_angles(long long n, const double4 *__restrict__ q3,
+                                                          double *__restrict__ angle) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    double rx, ry, rz;
+    edge_log(q3[3 * t], q3[3 * t + 1], q3[3 * t + 2], rx, ry, rz);
+    angle[t] = sqrt(rx * rx + ry * ry + rz * rz);
+}
+
+void candidate_angles(Graph &g, int64_t n, const double *q12, double *angle) {
+    if (n <= 0) return;
+    DevBuf<double4> dq;
+    DevBuf<double> da;
+    dq.upload(reinterpret_cast<const double4 *>(q12), (size_t)3 * n, g.stream);
+    da.alloc((size_t)n);
+    hipLaunchKernelGGL(k_candidate_angles, dim3((int)((n + 255) / 256)), dim3(256), 0, g.stream, (long long)n, dq.p, da.p);
+    IRH_CHECK(hipMemcpyAsync(angle, da.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g.stream));
+    IRH_CHECK(hipStreamSynchronize(g.stream));
 }
 
 // K2 and the NEXT iteration's K1 in one pass over the edges (round 4; the direct solver's irls loop, run_irls): the
@@ -2691,6 +2737,7 @@ int time_kernel(Graph &g, int which, int reps, double *ms) {
         case 9: cg2_time_once(g, 0); break;   // k_cg_apply (u = M^-1 r, w = L u) of the two-launch iteration
         case 10: cg2_time_once(g, 1); break;  // k_cg_update
         case 11: launch_weights_then_residual(g, IROTAVG_GEMAN_MCCLURE, 5 * IRH_PI / 180.0, nullptr, true); break;  // K2 + the next K1
+        case 12: launch_pose_weights(g, IROTAVG_GEMAN_MCCLURE, 5 * IRH_PI / 180.0); break;  // K1 + the weights of a zero step
         case 6:
             hipLaunchKernelGGL(k_apply_step, dim3(grid_for_elems(g.nu)), dim3(kRowBlock), 0, g.stream,
                                g.nu, g.f, g.ng, g.X.p, g.Q.p, g.part_score.p, 0, (const int *)nullptr);
@@ -2707,16 +2754,17 @@ int time_kernel(Graph &g, int which, int reps, double *ms) {
         if (!g.bcr_B) return IROTAVG_ERR_BAD_ARG;
         const int nl = bcr_levels(g);
         if ((which >= 20 && which < 40 && which - 20 >= nl) || (which >= 40 && which - 40 >= nl)) return IROTAVG_ERR_BAD_ARG;
-    } else if (which < 1 || which > 11) return IROTAVG_ERR_BAD_ARG;
+    } else if (which < 1 || which > 12) return IROTAVG_ERR_BAD_ARG;
     if ((which == 9 || which == 10) && !g.cg2) return IROTAVG_ERR_BAD_ARG;  // not this graph's PCG
     if (which == 8 && !(g.additive_top && g.levels.size() > 1 && g.ng == 0 && g.l0_far_entries == 0 &&
                         g.opt.no_fused_pspmv != 1))
         return IROTAVG_ERR_BAD_ARG;  // this graph's PCG does not use the fused kernel
     IRH_CHECK(hipMemsetAsync(g.flags.p, 0, sizeof(int) * FL_COUNT, g.stream));
-    // kernel 11 (weights, then the next residuals) writes the handle's weights and residual planes: they are put back
+    // kernels 11 (weights, then the next residuals) and 12 (residuals and the weights of a zero step) write the handle's
+    // weights and residual planes: they are put back
     // afterwards, so that a solve or a read-back behind the timing sees what it would have seen without it
     DevBuf<double> keep_dw, keep_er;
-    if (which == 11) {
+    if (which == 11 || which == 12) {
         keep_dw.alloc((size_t)g.mpad);
         keep_er.alloc((size_t)3 * g.mpad);
         IRH_CHECK(hipMemcpyAsync(keep_dw.p, g.dw.p, sizeof(double) * (size_t)g.mpad, hipMemcpyDeviceToDevice, g.stream));
@@ -2726,7 +2774,7 @@ int time_kernel(Graph &g, int which, int reps, double *ms) {
     IRH_CHECK(hipEventRecord(e0, g.stream));
     for (int r = 0; r < reps; r++) once();
     IRH_CHECK(hipEventRecord(e1, g.stream));
-    if (which == 11) {
+    if (which == 11 || which == 12) {
         IRH_CHECK(hipMemcpyAsync(g.dw.p, keep_dw.p, sizeof(double) * (size_t)g.mpad, hipMemcpyDeviceToDevice, g.stream));
         IRH_CHECK(hipMemcpyAsync(g.er.p, keep_er.p, sizeof(double) * 3 * (size_t)g.mpad, hipMemcpyDeviceToDevice, g.stream));
         IRH_CHECK(hipStreamSynchronize(g.stream));

@@ -12,9 +12,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <new>
 #include <vector>
 
 #include "graph.hpp"
+#include "marginals.hpp"
 
 namespace {
 
@@ -97,6 +99,7 @@ struct irotavg_viewgraph {
     irh::Switches sw;  // read when the view-graph is made; handed to every handle, resident graph and window solver it creates
     irotavg_rotavg_info last{};
     irh::WindowSolver *win = nullptr;  // persistent staging of the single-kernel window solve
+    irh::WinCov *cov = nullptr;        // ... and of the single-kernel uncertainty queries (wincov.hip)
     // The device-resident growing copy of the graph that the global re-solves run on (resident.hip) and what the
     // host has changed since the device last saw it: poses / fixed flags of views >= res_pose_lo, edge records of
     // views >= res_edge_view (a connection is filed under its HIGHER view); eoff[t] = edges of the views below t,
@@ -142,6 +145,7 @@ struct irotavg_viewgraph {
     } pending;
     ~irotavg_viewgraph() {
         if (win) irh::window_solver_delete(win);
+        if (cov) irh::wincov_delete(cov);
         if (res) irh::resident_delete(res);
     }
 };
@@ -273,58 +277,87 @@ namespace {
 // (fewer than the window -> early-out 3, so a call that goes on has ALL views), f = the fixed views, relabelled
 // fixed-first in ascending id. Returns false when the call is not of that kind (the caller takes the general path:
 // windows, graphs of fewer than 20000 connections, f == 0, no device); true with *rc set otherwise.
-bool rotavg_resident(irotavg_viewgraph *vg, irotavg_rotavg_info &loc, bool timing, int *rc, bool dry = false) {
+// the call is of that kind
+bool resident_wanted(const irotavg_viewgraph *vg) {
     const long m = (long)vg->pose.size();
     if (vg->sw.no_resident) return false;
     if (vg->n_conn < vg->sw.resident_min_edges || vg->n_conn < m || vg->n_touched < m || vg->n_fixed < 1 || m - vg->n_fixed < 1) return false;
     if (vg->n_conn > 0x3fffffffL) return false;
-    if (irotavg_device_count() <= 0) return false;
+    return irotavg_device_count() > 0;
+}
+void resident_drop(irotavg_viewgraph *vg) {  // whatever failed: the resident copy is sent as a whole next time
+    if (vg->res) irh::resident_invalidate(*vg->res);
+    vg->res_pose_lo = 0;
+    vg->res_edge_view = 0;
+}
+// What the host does ahead of a call on the resident graph, shared by the global re-solve and the uncertainty queries:
+// the records of what changed since the device last saw the graph go into the staging blocks, and the marks move up.
+struct ResidentCall {
+    long m = 0, view_lo = 0, ne = 0, edge_lo = 0;
+    int f = 0;
+    irh::ResidentStage st{};
+};
+bool resident_pack(irotavg_viewgraph *vg, bool timing, ResidentCall &c) {
+    const long m = (long)vg->pose.size();
     const double t0 = irh::now_seconds();
+    if (!vg->res) vg->res = irh::resident_new();
+    irh::Resident &R = *vg->res;
+    // what the device holds is valid below these marks
+    long view_lo = std::min({vg->res_pose_lo, irh::resident_views(R), m});
+    long ev = std::min({vg->res_edge_view, m});
+    if (irh::resident_views(R) == 0 || irh::resident_edges(R) == 0) {
+        view_lo = 0;
+        ev = 0;
+    }
+    std::vector<long> &eoff = vg->eoff;
+    if ((long)eoff.size() < m + 1) eoff.resize((size_t)m + 1 + (size_t)m / 2, 0);
+    for (long t = ev; t < m; t++) eoff[(size_t)t + 1] = eoff[(size_t)t] + (long)vg->conn[(size_t)t].size();
+    const long ne = eoff[(size_t)m], edge_lo = eoff[(size_t)ev];
+    if (edge_lo > irh::resident_edges(R)) {  // (cannot happen: the marks only move down between calls)
+        resident_drop(vg);
+        return false;
+    }
+    irh::ResidentStage st = irh::resident_stage(R, m, view_lo, ne, edge_lo);
+    irh::parallel_for((int64_t)(m - ev), 2048, [&](int64_t a, int64_t b, int) {
+        for (int64_t t = ev + a; t < ev + b; t++) {
+            size_t e = (size_t)(eoff[(size_t)t] - edge_lo);
+            for (const auto &cn : vg->conn[(size_t)t]) {
+                st.I[2 * e] = cn.i;
+                st.I[2 * e + 1] = (int32_t)t;
+                for (int q = 0; q < 4; q++) st.qq[4 * e + q] = cn.q[q];
+                e++;
+            }
+        }
+    });
+    irh::parallel_for((int64_t)(m - view_lo), 4096, [&](int64_t a, int64_t b, int) {
+        for (int64_t x = view_lo + a; x < view_lo + b; x++) {
+            const double *P = vg->pose_m((size_t)x);
+            std::copy(P, P + 9, st.R + 9 * (size_t)(x - view_lo));
+            st.fixed[(size_t)(x - view_lo)] = (uint8_t)(vg->fixed[(size_t)x] ? 1 : 0);
+        }
+    });
+    if (timing) std::fprintf(stderr, "[rot_avg resident] %-24s %8.3f ms (%ld views, %ld edges sent)\n", "delta packing",
+                             1e3 * (irh::now_seconds() - t0), m - view_lo, ne - edge_lo);
+    // the marks move up BEFORE the call: whatever fails inside invalidates the resident copy as a whole
+    vg->res_pose_lo = m;
+    vg->res_edge_view = m;
+    c.m = m;
+    c.view_lo = view_lo;
+    c.ne = ne;
+    c.edge_lo = edge_lo;
+    c.f = (int)vg->n_fixed;
+    c.st = st;
+    return true;
+}
+bool rotavg_resident(irotavg_viewgraph *vg, irotavg_rotavg_info &loc, bool timing, int *rc, bool dry = false) {
+    if (!resident_wanted(vg)) return false;
     try {
-        if (!vg->res) vg->res = irh::resident_new();
+        ResidentCall rcall;
+        if (!resident_pack(vg, timing, rcall)) return false;
         irh::Resident &R = *vg->res;
-        // what the device holds is valid below these marks
-        long view_lo = std::min({vg->res_pose_lo, irh::resident_views(R), m});
-        long ev = std::min({vg->res_edge_view, m});
-        if (irh::resident_views(R) == 0 || irh::resident_edges(R) == 0) {
-            view_lo = 0;
-            ev = 0;
-        }
-        std::vector<long> &eoff = vg->eoff;
-        if ((long)eoff.size() < m + 1) eoff.resize((size_t)m + 1 + (size_t)m / 2, 0);
-        for (long t = ev; t < m; t++) eoff[(size_t)t + 1] = eoff[(size_t)t] + (long)vg->conn[(size_t)t].size();
-        const long ne = eoff[(size_t)m], edge_lo = eoff[(size_t)ev];
-        if (edge_lo > irh::resident_edges(R)) {  // (cannot happen: the marks only move down between calls)
-            irh::resident_invalidate(R);
-            vg->res_pose_lo = 0;
-            vg->res_edge_view = 0;
-            return false;
-        }
-        irh::ResidentStage st = irh::resident_stage(R, m, view_lo, ne, edge_lo);
-        irh::parallel_for((int64_t)(m - ev), 2048, [&](int64_t a, int64_t b, int) {
-            for (int64_t t = ev + a; t < ev + b; t++) {
-                size_t e = (size_t)(eoff[(size_t)t] - edge_lo);
-                for (const auto &c : vg->conn[(size_t)t]) {
-                    st.I[2 * e] = c.i;
-                    st.I[2 * e + 1] = (int32_t)t;
-                    for (int q = 0; q < 4; q++) st.qq[4 * e + q] = c.q[q];
-                    e++;
-                }
-            }
-        });
-        irh::parallel_for((int64_t)(m - view_lo), 4096, [&](int64_t a, int64_t b, int) {
-            for (int64_t x = view_lo + a; x < view_lo + b; x++) {
-                const double *P = vg->pose_m((size_t)x);
-                std::copy(P, P + 9, st.R + 9 * (size_t)(x - view_lo));
-                st.fixed[(size_t)(x - view_lo)] = (uint8_t)(vg->fixed[(size_t)x] ? 1 : 0);
-            }
-        });
-        if (timing) std::fprintf(stderr, "[rot_avg resident] %-24s %8.3f ms (%ld views, %ld edges sent)\n", "delta packing",
-                                 1e3 * (irh::now_seconds() - t0), m - view_lo, ne - edge_lo);
-        const int f = (int)vg->n_fixed;
-        // the marks move up BEFORE the call: whatever fails inside invalidates the resident copy as a whole
-        vg->res_pose_lo = m;
-        vg->res_edge_view = m;
+        const long m = rcall.m, view_lo = rcall.view_lo, ne = rcall.ne, edge_lo = rcall.edge_lo;
+        const int f = rcall.f;
+        const irh::ResidentStage &st = rcall.st;
         int dry_a = -1, dry_b = -1;
         if (dry) {  // two free views far apart for the dry run's made-up closure
             for (long x = 0; x < m && dry_a < 0; x++)
@@ -375,41 +408,13 @@ bool rotavg_resident(irotavg_viewgraph *vg, irotavg_rotavg_info &loc, bool timin
 }
 }  // namespace
 
-// ViewGraph::rotAvg(winSize), src/ViewGraph.cpp:1263-1435. Returns IROTAVG_OK also for the
-// reference's silent early-outs (info->skipped tells which).
-int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotavg_info *info) {
-    if (!vg || win_size <= 2) return IROTAVG_ERR_BAD_ARG;  // assert(winSize > 2) :1265
-    irotavg_rotavg_info loc{};
-    const bool timing = vg->sw.rotavg_timing;
-    struct Total {
-        bool on;
-        double t0;
-        ~Total() {
-            if (on) std::fprintf(stderr, "[rot_avg] %-28s %8.3f ms\n", "total (incl. clean-up)", 1e3 * (irh::now_seconds() - t0));
-        }
-    } total{timing, irh::now_seconds()};
-    double tl = irh::now_seconds();
-    auto lap = [&](const char *what) {
-        if (!timing) return;
-        const double t = irh::now_seconds();
-        std::fprintf(stderr, "[rot_avg] %-28s %8.3f ms\n", what, 1e3 * (t - tl));
-        tl = t;
-    };
+namespace {
+// The problem rot_avg(win) solves (src/ViewGraph.cpp:1282-1386), extracted into vg->scratch: I (relabelled fixed-first),
+// qq, QQ, Q, vertices, i2v. Returns what irotavg_rotavg_info.skipped reports (0: there is a problem; 2-4: the reference's
+// early-outs). Shared by rot_avg and the uncertainty queries (docs/viewgraph_uncertainty.md). gauge_identity: with no
+// fixed pose in the problem, row 0 becomes the identity as the reference has it; a query holds it at the pose it has.
+int rotavg_extract(irotavg_viewgraph *vg, int win, bool gauge_identity, long &ne_out, long &nv_out, int &f_out) {
     const long m = (long)vg->pose.size();
-    int win = (int)std::min<long>(m, win_size);  // :1269
-    if (win < 2) {
-        loc.skipped = 1;
-        if (info) *info = loc;
-        return IROTAVG_OK;  // :1270-1273
-    }
-    if (win == m) {  // a global re-solve: on the device-resident copy of the graph when it is of that kind
-        int rrc = IROTAVG_OK;
-        if (rotavg_resident(vg, loc, timing, &rrc)) {
-            if (rrc == IROTAVG_OK) vg->last = loc;
-            if (info) *info = loc;
-            return rrc;
-        }
-    }
     // ---- local connections (:1282-1307): for the last `win` views, edges with i < j.
     // `vertices` of the reference is a std::set<int> (ascending ids); here: a mark array + sort.
     std::vector<int32_t> &I = vg->scratch.I;
@@ -468,18 +473,13 @@ int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotav
         }
     std::sort(vertices.begin(), vertices.end());
     const long ne = (long)qq.size() / 4, nv = (long)vertices.size();
-    if (ne < win) {  // :1313-1316
-        loc.skipped = 2;
-        if (info) *info = loc;
-        return IROTAVG_OK;
-    }
-    if (nv < win) {  // :1318-1321
-        loc.skipped = 3;
-        if (info) *info = loc;
-        return IROTAVG_OK;
-    }
+    ne_out = ne;
+    nv_out = nv;
+    if (ne < win) return 2;  // :1313-1316
+    if (nv < win) return 3;  // :1318-1321
     // ---- fixed count and relabelling (:1323-1363)
-    int f = (int)nv - win;
+    int &f = f_out;
+    f = (int)nv - win;
     for (int x : vertices)
         if (x >= m - win && vg->fixed[x]) f++;
     std::vector<int> &i2v = vg->scratch.i2v;
@@ -509,25 +509,71 @@ int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotav
             for (int c = 0; c < 4; c++) Q[(size_t)c * nv + r] = q[c];
         }
     });
-    if (f == 0) {  // :1382-1386
-        Q[0] = 0;
-        Q[nv] = 0;
-        Q[2 * nv] = 0;
-        Q[3 * nv] = 1;
+    if (f == 0) {  // :1382-1386 (a query holds row 0 at the pose it has: it moves nothing)
+        if (gauge_identity) {
+            Q[0] = 0;
+            Q[nv] = 0;
+            Q[2 * nv] = 0;
+            Q[3 * nv] = 1;
+        }
         f = 1;
     }
     // make_A asserts n - f > 1 (ral/l1_irls.cpp:758); fewer unknowns cannot be solved
-    if (nv - f < 1) {
-        loc.skipped = 4;
-        if (info) *info = loc;
-        return IROTAVG_OK;
-    }
+    if (nv - f < 1) return 4;
     std::vector<double> &QQ = vg->scratch.QQ;
     QQ.resize((size_t)4 * ne);
     irh::parallel_for((int64_t)ne, 32768, [&](int64_t a, int64_t b, int) {
         for (int64_t e = a; e < b; e++)
             for (int c = 0; c < 4; c++) QQ[(size_t)c * ne + e] = qq[(size_t)4 * e + c];
     });
+    return 0;
+}
+}  // namespace
+
+// ViewGraph::rotAvg(winSize), src/ViewGraph.cpp:1263-1435. Returns IROTAVG_OK also for the
+// reference's silent early-outs (info->skipped tells which).
+int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotavg_info *info) {
+    if (!vg || win_size <= 2) return IROTAVG_ERR_BAD_ARG;  // assert(winSize > 2) :1265
+    irotavg_rotavg_info loc{};
+    const bool timing = vg->sw.rotavg_timing;
+    struct Total {
+        bool on;
+        double t0;
+        ~Total() {
+            if (on) std::fprintf(stderr, "[rot_avg] %-28s %8.3f ms\n", "total (incl. clean-up)", 1e3 * (irh::now_seconds() - t0));
+        }
+    } total{timing, irh::now_seconds()};
+    double tl = irh::now_seconds();
+    auto lap = [&](const char *what) {
+        if (!timing) return;
+        const double t = irh::now_seconds();
+        std::fprintf(stderr, "[rot_avg] %-28s %8.3f ms\n", what, 1e3 * (t - tl));
+        tl = t;
+    };
+    const long m = (long)vg->pose.size();
+    int win = (int)std::min<long>(m, win_size);  // :1269
+    if (win < 2) {
+        loc.skipped = 1;
+        if (info) *info = loc;
+        return IROTAVG_OK;  // :1270-1273
+    }
+    if (win == m) {  // a global re-solve: on the device-resident copy of the graph when it is of that kind
+        int rrc = IROTAVG_OK;
+        if (rotavg_resident(vg, loc, timing, &rrc)) {
+            if (rrc == IROTAVG_OK) vg->last = loc;
+            if (info) *info = loc;
+            return rrc;
+        }
+    }
+    long ne = 0, nv = 0;
+    int f = 0;
+    loc.skipped = rotavg_extract(vg, win, true, ne, nv, f);
+    if (loc.skipped) {
+        if (info) *info = loc;
+        return IROTAVG_OK;
+    }
+    std::vector<int32_t> &I = vg->scratch.I;
+    std::vector<double> &qq = vg->scratch.qq, &Q = vg->scratch.Q, &QQ = vg->scratch.QQ;
     lap("window extraction + packing");
     // ---- solve (:1396-1417): no init_mst (refine from the current poses); l1ra 100 iterations,
     // then irls Geman-McClure, sigma 5 deg, 100 iterations, change_th 1e-3
@@ -611,6 +657,302 @@ int irotavg_viewgraph_rot_avg(irotavg_viewgraph *vg, int win_size, irotavg_rotav
     vg->last = loc;
     if (info) *info = loc;
     return IROTAVG_OK;
+}
+
+// ---- uncertainty queries (docs/viewgraph_uncertainty.md) ---------------------------------------------------------------
+// All three are defined on the problem rot_avg(win_size) would solve now (rotavg_extract), at the current poses, with
+// Geman-McClure weights (sigma = 5 degrees) of a zero step; none moves a pose.
+namespace {
+struct UncRequest {
+    double *var = nullptr;  // num_views
+    int64_t npairs = 0;
+    const int32_t *pairs = nullptr;
+    double *pair_var = nullptr;
+    bool edges = false;
+    int64_t cap = 0, count = 0;
+    int32_t *conn = nullptr;
+    double *edge_var = nullptr, *leverage = nullptr, *chi2 = nullptr;
+    int64_t ncand = 0;
+    const int32_t *cpairs = nullptr;
+    const double *Rij = nullptr;
+    double *angle = nullptr, *cand_var = nullptr, *cand_chi2 = nullptr;
+};
+
+void fill_nan(double *p, int64_t n) {
+    if (p) std::fill(p, p + n, (double)NAN);
+}
+
+int vg_uncertainty(irotavg_viewgraph *vg, int win_size, UncRequest &rq, irotavg_uncertainty_info *info) {
+    if (!vg || win_size <= 2) return IROTAVG_ERR_BAD_ARG;
+    const long m = (long)vg->pose.size();
+    if (rq.npairs < 0 || (rq.npairs > 0 && (!rq.pairs || !rq.pair_var))) return IROTAVG_ERR_BAD_ARG;
+    if (rq.ncand < 0 || (rq.ncand > 0 && (!rq.cpairs || !rq.Rij))) return IROTAVG_ERR_BAD_ARG;
+    if (rq.npairs > 0x3fffffff || rq.ncand > 0x3fffffff || rq.cap < 0) return IROTAVG_ERR_BAD_ARG;
+    for (int64_t t = 0; t < 2 * rq.npairs; t++)
+        if (rq.pairs[t] < 0 || rq.pairs[t] >= m) return IROTAVG_ERR_BAD_ARG;
+    for (int64_t t = 0; t < rq.ncand; t++) {
+        const int a = rq.cpairs[2 * t], b = rq.cpairs[2 * t + 1];
+        if (a < 0 || b < 0 || a >= m || b >= m || a == b) return IROTAVG_ERR_BAD_ARG;
+    }
+    irotavg_uncertainty_info loc{};
+    loc.scale = NAN;
+    const int win = (int)std::min<long>(m, win_size);
+    long ne = 0, nv = 0;
+    int f = 0;
+    // A global problem of the kind rot_avg solves on the device-resident copy of the graph: its handle comes from those
+    // records -- the same delta upload, the same marks, so a later rot_avg re-sends nothing -- and the host extracts
+    // nothing (every view is in the problem, fixed ones first, both groups in ascending id; edge k is the k-th connection).
+    // Whatever fails there drops the resident copy and the call takes the general path, as rot_avg does.
+    struct Handle {
+        irotavg_graph *g = nullptr;
+        ~Handle() {
+            if (g) irotavg_graph_destroy(g);
+        }
+    } h;
+    bool resident = false;
+    if (win == m && win >= 2 && resident_wanted(vg) &&
+        !(vg->opt.no_window_kernel != 1 && irh::window_fits((int)m, (int)vg->n_fixed, (int)vg->n_conn)) &&
+        !(rq.edges && rq.cap < vg->n_conn)) {
+        try {
+            ResidentCall rc0;
+            if (resident_pack(vg, vg->sw.rotavg_timing, rc0)) {
+                const int rrc = irh::resident_build_handle(*vg->res, rc0.m, rc0.view_lo, rc0.ne, rc0.edge_lo, rc0.f, vg->opt,
+                                                           vg->sw, &h.g);
+                if (rrc == IROTAVG_OK) {
+                    resident = true;
+                    ne = rc0.ne;
+                    nv = m;
+                    f = rc0.f;
+                    std::vector<int> &i2v = vg->scratch.i2v;
+                    i2v.assign((size_t)m, 0);
+                    int t = 0, k = f;
+                    for (long x = 0; x < m; x++) i2v[(size_t)(vg->fixed[(size_t)x] ? t++ : k++)] = (int)x;
+                } else {
+                    resident_drop(vg);
+                    (void)hipGetLastError();
+                    (void)irotavg_trim_memory();
+                }
+            }
+        } catch (...) {
+            resident_drop(vg);
+            (void)hipGetLastError();
+            (void)irotavg_trim_memory();
+        }
+    }
+    if (!resident) loc.skipped = win < 2 ? 1 : rotavg_extract(vg, win, false, ne, nv, f);
+    if (loc.skipped) {  // where rot_avg would do nothing there is no problem to ask about
+        fill_nan(rq.var, m);
+        fill_nan(rq.pair_var, rq.npairs);
+        fill_nan(rq.edge_var, rq.cap);
+        fill_nan(rq.leverage, rq.cap);
+        fill_nan(rq.chi2, rq.cap);
+        if (rq.conn) std::fill(rq.conn, rq.conn + 2 * rq.cap, -1);
+        fill_nan(rq.angle, rq.ncand);
+        fill_nan(rq.cand_var, rq.ncand);
+        fill_nan(rq.cand_chi2, rq.ncand);
+        rq.count = 0;
+        if (info) *info = loc;
+        return IROTAVG_OK;
+    }
+    rq.count = ne;
+    loc.n_views = (int)nv;
+    loc.n_edges = (int)ne;
+    loc.n_fixed = f;
+    if (rq.edges && rq.cap < ne) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    const std::vector<int32_t> &I = vg->scratch.I;
+    const std::vector<int> &i2v = vg->scratch.i2v;
+    const double sigma = 5 * M_PI / 180.0, sg2 = sigma * sigma;
+    // caller's view id -> row of the problem, for the pairs and the candidates: rotavg_extract has put its own use of the
+    // map back to "unseen" on return, so it is filled again from i2v here (and restored on exit in the same way)
+    std::vector<int> &v2i = vg->mark;
+    struct Unmark {
+        std::vector<int> &map;
+        const std::vector<int> &rows;
+        ~Unmark() {
+            for (int x : rows) map[(size_t)x] = -1;
+        }
+    } unmark{v2i, i2v};
+    for (long r = 0; r < nv; r++) v2i[(size_t)i2v[(size_t)r]] = (int)r;
+    const int64_t np = rq.npairs, nc = rq.ncand;
+    // pairs and candidates as problem rows (view numbering of the problem; -1: not in it), u = e_first - e_second
+    std::vector<int32_t> prow((size_t)2 * (np + nc));
+    std::vector<double> cq((size_t)12 * nc);
+    for (int64_t t = 0; t < np; t++) {
+        prow[2 * t] = v2i[(size_t)rq.pairs[2 * t]];
+        prow[2 * t + 1] = v2i[(size_t)rq.pairs[2 * t + 1]];
+    }
+    for (int64_t t = 0; t < nc; t++) {
+        // as irotavg_viewgraph_connect files it: under (lo, hi) with R_hi = R R_lo
+        const int a = rq.cpairs[2 * t], b = rq.cpairs[2 * t + 1], lo = std::min(a, b), hi = std::max(a, b);
+        double R[9], P[9];
+        for (int r = 0; r < 3; r++)
+            for (int q = 0; q < 3; q++) R[3 * r + q] = a < b ? rq.Rij[9 * t + 3 * r + q] : rq.Rij[9 * t + 3 * q + r];
+        vg->pose_read((size_t)lo, P);
+        rmat2quat(P, &cq[12 * t]);
+        vg->pose_read((size_t)hi, P);
+        rmat2quat(P, &cq[12 * t + 4]);
+        rmat2quat(R, &cq[12 * t + 8]);
+        prow[2 * (np + t)] = v2i[(size_t)hi];
+        prow[2 * (np + t) + 1] = v2i[(size_t)lo];
+    }
+    // (the edge arrays are in problem order as they come: they go straight into the caller's buffers by the routes' own
+    // last step, which writes on success only)
+    std::vector<double> varl, pv((size_t)(np + nc)), ang((size_t)nc), cchi((size_t)nc);
+    if (rq.var) varl.resize((size_t)nv);
+    double s2 = NAN;
+    int rc = IROTAVG_OK;
+    try {
+        if (vg->opt.no_window_kernel != 1 && irh::window_fits((int)nv, f, (int)ne)) {
+            // ---- route 1: one launch of k_window_cov, no handle
+            loc.route = 1;
+            if (!vg->cov) vg->cov = irh::wincov_new();
+            const std::vector<double> &Q = vg->scratch.Q;
+            std::vector<double> &Qa = vg->scratch.Qa;
+            Qa.resize((size_t)4 * nv);
+            for (long r = 0; r < nv; r++)
+                for (int c = 0; c < 4; c++) Qa[(size_t)4 * r + c] = Q[(size_t)c * nv + r];
+            // operator rows: -1 a held view, -2 a view that is not in the problem
+            std::vector<int32_t> orow(prow.size());
+            for (size_t t = 0; t < orow.size(); t++) orow[t] = prow[t] < 0 ? -2 : (prow[t] < f ? -1 : prow[t] - f);
+            for (size_t t = 0; t + 1 < orow.size(); t += 2)
+                if (prow[t] >= 0 && prow[t] == prow[t + 1]) orow[t] = orow[t + 1] = -1;  // i == j: u = 0
+            irh::WinCovQuery q{};
+            q.nv = (int)nv;
+            q.f = f;
+            q.ne = (int)ne;
+            q.I = I.data();
+            q.qq_aos = vg->scratch.qq.data();
+            q.Q_aos = Qa.data();
+            q.sigma = sigma;
+            q.var = rq.var ? varl.data() + f : nullptr;
+            q.edge_var = rq.edge_var;
+            q.leverage = rq.leverage;
+            q.chi2 = rq.chi2;
+            q.np = (int)np;
+            q.prow = orow.data();
+            q.pair_var = pv.data();
+            q.nc = (int)nc;
+            q.crow = orow.data() + 2 * np;
+            q.cq = cq.data();
+            q.angle = ang.data();
+            q.cand_var = pv.data() + np;
+            q.cand_chi2 = cchi.data();
+            rc = irh::wincov_query(*vg->cov, q);
+            s2 = q.s2;
+            for (int r = 0; r < f && rq.var; r++) varl[(size_t)r] = 0.0;
+        } else {
+            // ---- routes 2-4: a handle built as rot_avg builds it, the weights of the poses, the handle queries
+            if (!resident) {
+                rc = irh::graph_create(&h.g, ne, nv, f, I.data(), vg->scratch.QQ.data(), ne, &vg->opt, nullptr, vg->sw);
+                if (rc == IROTAVG_OK) rc = irotavg_graph_set_rotations(h.g, vg->scratch.Q.data(), nv);
+            }
+            if (rc == IROTAVG_OK) {
+                irh::Graph &g = irh::graph_of(h.g);
+                loc.route = g.no <= 2048 ? 2 : (g.bcr_B > 0 ? 3 : 4);
+                if (loc.route == 3) loc.closures = irh::bcr_closures(g);
+                irh::launch_pose_weights(g, IROTAVG_GEMAN_MCCLURE, sigma);
+                // the handle query takes view numbers; a pair with a view outside the problem is asked as (0, 0)
+                std::vector<int32_t> hp(prow);
+                for (size_t t = 0; t + 1 < hp.size(); t += 2)
+                    if (hp[t] < 0 || hp[t + 1] < 0) hp[t] = hp[t + 1] = 0;
+                if (rq.var || np + nc > 0)
+                    rc = irh::rotation_variance(g, rq.var ? varl.data() : nullptr, np + nc, hp.data(), pv.data(), &s2);
+                if (rc == IROTAVG_OK && rq.edges)
+                    rc = irh::edge_diagnostics(g, rq.edge_var, rq.leverage, rq.chi2, &s2);
+                if (rc == IROTAVG_OK && nc > 0) {
+                    irh::candidate_angles(g, nc, cq.data(), ang.data());
+                    const double s4 = sg2 * sg2;  // as k_window_cov forms it
+                    for (int64_t t = 0; t < nc; t++)
+                        cchi[(size_t)t] = ang[(size_t)t] * ang[(size_t)t] / (s2 * (pv[(size_t)(np + t)] + s4));
+                }
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        return IROTAVG_ERR_NOMEM;
+    } catch (...) {
+        return IROTAVG_ERR_HIP;
+    }
+    if (rc != IROTAVG_OK) {  // outputs untouched
+        if (info) *info = loc;
+        return rc;
+    }
+    // ---- into the caller's order: views by their ids (0 held, NaN not in the problem), edges in problem order
+    for (int64_t t = 0; t < np + nc; t++)
+        if (prow[2 * t] < 0 || prow[2 * t + 1] < 0) {
+            pv[(size_t)t] = NAN;
+            if (t >= np) cchi[(size_t)(t - np)] = NAN;
+        }
+    if (rq.var) {
+        fill_nan(rq.var, m);
+        for (long r = 0; r < nv; r++) rq.var[(size_t)i2v[(size_t)r]] = r < f ? 0.0 : varl[(size_t)r];
+    }
+    if (np > 0) std::copy(pv.begin(), pv.begin() + np, rq.pair_var);
+    if (rq.conn && resident) {
+        long k = 0;
+        for (long t = 0; t < m; t++)
+            for (const auto &c : vg->conn[(size_t)t]) {
+                rq.conn[k++] = c.i;
+                rq.conn[k++] = (int32_t)t;
+            }
+    } else if (rq.conn) {
+        for (long k = 0; k < 2 * ne; k++) rq.conn[k] = i2v[(size_t)I[(size_t)k]];
+    }
+    if (rq.angle) std::copy(ang.begin(), ang.end(), rq.angle);
+    if (rq.cand_var) std::copy(pv.begin() + np, pv.end(), rq.cand_var);
+    if (rq.cand_chi2) std::copy(cchi.begin(), cchi.end(), rq.cand_chi2);
+    loc.scale = s2;
+    if (info) *info = loc;
+    return IROTAVG_OK;
+}
+}  // namespace
+
+int irotavg_viewgraph_rotation_variance(irotavg_viewgraph *vg, int win_size, double *var, int64_t npairs,
+                                        const int32_t *pairs, double *pair_var, irotavg_uncertainty_info *info) {
+    UncRequest rq;
+    rq.var = var;
+    rq.npairs = npairs;
+    rq.pairs = pairs;
+    rq.pair_var = pair_var;
+    return vg_uncertainty(vg, win_size, rq, info);
+}
+
+// edges of the problem rot_avg(win_size) would solve now (0 where it would skip); < 0: an error code
+int64_t irotavg_viewgraph_num_connections(irotavg_viewgraph *vg, int win_size) {
+    if (!vg || win_size <= 2) return IROTAVG_ERR_BAD_ARG;
+    const long m = (long)vg->pose.size();
+    const int win = (int)std::min<long>(m, win_size);
+    if (win < 2) return 0;
+    long ne = 0, nv = 0;
+    int f = 0;
+    return rotavg_extract(vg, win, false, ne, nv, f) ? 0 : (int64_t)ne;
+}
+
+int64_t irotavg_viewgraph_edge_diagnostics(irotavg_viewgraph *vg, int win_size, int64_t cap, int32_t *conn,
+                                           double *edge_var, double *leverage, double *chi2,
+                                           irotavg_uncertainty_info *info) {
+    UncRequest rq;
+    rq.edges = true;
+    rq.cap = cap;
+    rq.conn = conn;
+    rq.edge_var = edge_var;
+    rq.leverage = leverage;
+    rq.chi2 = chi2;
+    const int rc = vg_uncertainty(vg, win_size, rq, info);
+    return rc != IROTAVG_OK ? (int64_t)rc : rq.count;
+}
+
+int irotavg_viewgraph_gate_connections(irotavg_viewgraph *vg, int win_size, int64_t ncand, const int32_t *pairs,
+                                       const double *Rij, double *angle, double *pair_var, double *chi2,
+                                       irotavg_uncertainty_info *info) {
+    UncRequest rq;
+    rq.ncand = ncand;
+    rq.cpairs = pairs;
+    rq.Rij = Rij;
+    rq.angle = angle;
+    rq.cand_var = pair_var;
+    rq.cand_chi2 = chi2;
+    return vg_uncertainty(vg, win_size, rq, info);
 }
 
 // Takes what a process pays ONCE for its first global re-solve -- the resident copy of the graph on the device,

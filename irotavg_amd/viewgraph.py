@@ -80,6 +80,65 @@ class ViewGraph:
         capi.check(capi.lib().irotavg_viewgraph_rot_avg(self._h, int(winSize), C.byref(info)), "rotAvg")
         return {k: getattr(info, k) for k, _ in capi.RotAvgInfo._fields_}
 
+    @staticmethod
+    def _info(info, rc):
+        d = {k: getattr(info, k) for k, _ in capi.UncertaintyInfo._fields_}
+        d["rc"] = rc
+        return d
+
+    def rotationVariance(self, winSize, pairs=None, marginals=True, allow_rc=()):
+        """irotavg_viewgraph_rotation_variance (docs/viewgraph_uncertainty.md): the info record as a dict plus
+        var (numViews entries: 0 held, NaN not in the problem; None without marginals) and pair_var."""
+        P = np.zeros((0, 2), dtype=np.int32) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        var = np.full(self.numViews(), -1.0) if marginals else None
+        pv = np.full(max(len(P), 1), -1.0)
+        info = capi.UncertaintyInfo()
+        rc = capi.lib().irotavg_viewgraph_rotation_variance(self._h, int(winSize), capi._d(var) if marginals else None,
+                                                            len(P), capi._i(P) if len(P) else None, capi._d(pv),
+                                                            C.byref(info))
+        if rc != capi.OK and rc not in allow_rc:
+            raise capi.IrotavgError(rc, "rotationVariance")
+        return dict(self._info(info, rc), var=var, pair_var=pv[:len(P)])
+
+    def numConnections(self, winSize):
+        """Edges of the problem rotAvg(winSize) would solve now (0 where it would skip)."""
+        n = capi.lib().irotavg_viewgraph_num_connections(self._h, int(winSize))
+        if n < 0:
+            raise capi.IrotavgError(int(n), "numConnections")
+        return int(n)
+
+    def edgeDiagnostics(self, winSize, edge_var=True, leverage=True, chi2=True, cap=None, allow_rc=()):
+        """irotavg_viewgraph_edge_diagnostics: the info record plus n, conn (n x 2 view ids, problem order), edge_var,
+        leverage, chi2 (n each, or None). cap: room to offer (default: numConnections)."""
+        cap = self.numConnections(winSize) if cap is None else int(cap)
+        conn = np.full((max(cap, 1), 2), -7, dtype=np.int32)
+        out = [np.full(max(cap, 1), -1.0) if want else None for want in (edge_var, leverage, chi2)]
+        info = capi.UncertaintyInfo()
+        n = capi.lib().irotavg_viewgraph_edge_diagnostics(self._h, int(winSize), cap, capi._i(conn),
+                                                          *[capi._d(a) if a is not None else None for a in out],
+                                                          C.byref(info))
+        rc = int(n) if n < 0 else capi.OK
+        if rc != capi.OK and rc not in allow_rc:
+            raise capi.IrotavgError(rc, "edgeDiagnostics")
+        k = cap if (n <= 0) else int(n)
+        return dict(self._info(info, rc), n=max(int(n), 0), conn=conn[:k], edge_var=None if out[0] is None else out[0][:k],
+                    leverage=None if out[1] is None else out[1][:k], chi2=None if out[2] is None else out[2][:k])
+
+    def gateConnections(self, winSize, pairs, Rij, allow_rc=()):
+        """irotavg_viewgraph_gate_connections: candidates (i, j, R_ij) as connect takes them, judged as new measurements
+        against the current graph; nothing is added. The info record plus angle, pair_var, chi2 (one per candidate)."""
+        P = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        R = np.ascontiguousarray(Rij, dtype=np.float64).reshape(-1, 9)
+        if len(R) != len(P):
+            raise ValueError("one 3x3 rotation per candidate pair")
+        out = [np.full(max(len(P), 1), -1.0) for _ in range(3)]
+        info = capi.UncertaintyInfo()
+        rc = capi.lib().irotavg_viewgraph_gate_connections(self._h, int(winSize), len(P), capi._i(P), capi._d(R),
+                                                           *[capi._d(a) for a in out], C.byref(info))
+        if rc != capi.OK and rc not in allow_rc:
+            raise capi.IrotavgError(rc, "gateConnections")
+        return dict(self._info(info, rc), angle=out[0][:len(P)], pair_var=out[1][:len(P)], chi2=out[2][:len(P)])
+
     def prepare(self):
         """irotavg_viewgraph_prepare: a dry run of the global re-solve (no pose changes) that takes the one-time
         costs of a process out of the first loop closure's latency."""
