@@ -317,6 +317,50 @@ int irotavg_edge_diagnostics(int64_t m, int64_t n_total, int f, const int32_t *I
                              const double *Q, int64_t ldq, const double *weights, double *edge_var, double *leverage,
                              double *chi2, double *scale);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device-pointer handle API (docs/device_api.md): the same handle, fed from and read into arrays that live in HBM
+ * already -- no host round trip. Every DATA pointer below is a DEVICE pointer on the handle's device (`scale` alone is
+ * a host pointer); `stream` is the caller's hipStream_t (NULL = the null stream).
+ *
+ * Ordering: on entry the handle's stream waits for an event recorded on `stream`; before returning, `stream` waits for
+ * an event recorded on the handle's stream. The caller never needs a host synchronise before or after a call: inputs
+ * may still be in flight on `stream`, outputs are ready for whatever is enqueued on `stream` next. The copy calls
+ * (set / get) never block the host; create, the solves and the two queries read small results back and do.
+ *
+ * A strided matrix is (ptr, row_stride, col_stride) in ELEMENTS: element (k, c) lives at ptr[k * row_stride +
+ * c * col_stride]; quaternion columns are [x, y, z, w]. Column-major planes are (1, ld), a contiguous (rows, 4) array
+ * is (4, 1), strides may be negative. Accepted are exactly the stride pairs with
+ *     rs != 0, cs != 0, and (|rs| >= cols * |cs|  or  |cs| >= rows * |rs|)
+ * (rows that do not overlap, or columns that do not): anything else could alias and is IROTAVG_ERR_BAD_ARG, like a NULL
+ * pointer, a pointer that is not 8-byte aligned, and a matrix whose lowest or highest element hipPointerGetAttributes
+ * does not report as device memory of the handle's device. All of these are checked before any device work is enqueued.
+ * ------------------------------------------------------------------------------------------ */
+
+/* irotavg_graph_create from arrays on the device: I_dev = m pairs of int32 (8-byte aligned), QQ_dev = strided m x 4.
+ * The handle is built on the device from the caller's arrays as they are (no relabelling; the build code of
+ * IROTAVG_HOST_BUILD=0) and keeps its own copies: the caller's buffers are only read and are free again on return.
+ * opt->device (or the current device) is the handle's device. An edge index outside [0, n_total) is found by the
+ * build's first kernel: IROTAVG_ERR_BAD_ARG, *g stays NULL. No HIP device: IROTAVG_ERR_NO_DEVICE. init_mst has no
+ * device form (its sweep is order-dependent): bring initial rotations with irotavg_graph_set_rotations_dev. */
+int irotavg_graph_create_dev(irotavg_graph **g, int64_t m, int64_t n_total, int f, const int32_t *I_dev,
+                             const double *QQ_dev, int64_t qq_rs, int64_t qq_cs, const irotavg_options *opt,
+                             void *stream);
+/* all n_total rows, strided n_total x 4 */
+int irotavg_graph_set_rotations_dev(irotavg_graph *g, const double *Q_dev, int64_t rs, int64_t cs, void *stream);
+int irotavg_graph_get_rotations_dev(irotavg_graph *g, double *Q_dev, int64_t rs, int64_t cs, void *stream);
+/* m contiguous doubles */
+int irotavg_graph_set_weights_dev(irotavg_graph *g, const double *w_dev, void *stream);
+int irotavg_graph_get_weights_dev(irotavg_graph *g, double *w_dev, void *stream);
+/* the m x 3 residuals of irotavg_graph_get_residuals, strided */
+int irotavg_graph_get_residuals_dev(irotavg_graph *g, double *out_dev, int64_t rs, int64_t cs, void *stream);
+/* irotavg_graph_rotation_variance's marginals (var_dev: n_total contiguous doubles, required) and scale (HOST, may be
+ * NULL); pairs stay with the host call. Same routes, errors and read-only guarantee; var_dev is written only on success. */
+int irotavg_graph_rotation_variance_dev(irotavg_graph *g, double *var_dev, double *scale, void *stream);
+/* irotavg_graph_edge_diagnostics with the three arrays on the device (m contiguous doubles each, or NULL); scale is a
+ * HOST pointer and may be NULL. Same definitions, routes, error codes and read-only guarantee; written only on success. */
+int irotavg_graph_edge_diagnostics_dev(irotavg_graph *g, double *edge_var_dev, double *leverage_dev, double *chi2_dev,
+                                       double *scale, void *stream);
+
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash
  * each, followed by the scalars that choose kernels (level shapes, far-entry count, fused-assembly / two-launch

@@ -45,6 +45,9 @@ SYMBOLS = [
     "irotavg_graph_edge_diagnostics", "irotavg_edge_diagnostics",
     "irotavg_graph_pose_weights", "irotavg_viewgraph_rotation_variance", "irotavg_viewgraph_num_connections",
     "irotavg_viewgraph_edge_diagnostics", "irotavg_viewgraph_gate_connections",
+    "irotavg_graph_create_dev", "irotavg_graph_set_rotations_dev", "irotavg_graph_get_rotations_dev",
+    "irotavg_graph_set_weights_dev", "irotavg_graph_get_weights_dev", "irotavg_graph_get_residuals_dev",
+    "irotavg_graph_rotation_variance_dev", "irotavg_graph_edge_diagnostics_dev",
 ]
 
 
@@ -153,6 +156,16 @@ def lib():
     L.irotavg_edge_diagnostics.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
                                            _dp, _dp, _dp, _dp]
     L.irotavg_graph_pose_weights.argtypes = [vp, C.c_int, C.c_double]
+    # the device-pointer API (irotavg_amd/torch_api.py): data pointers and the stream travel as plain addresses
+    L.irotavg_graph_create_dev.argtypes = [C.POINTER(vp), C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int64,
+                                           C.POINTER(Options), vp]
+    L.irotavg_graph_set_rotations_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
+    L.irotavg_graph_get_rotations_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
+    L.irotavg_graph_set_weights_dev.argtypes = [vp, vp, vp]
+    L.irotavg_graph_get_weights_dev.argtypes = [vp, vp, vp]
+    L.irotavg_graph_get_residuals_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
+    L.irotavg_graph_rotation_variance_dev.argtypes = [vp, vp, _dp, vp]
+    L.irotavg_graph_edge_diagnostics_dev.argtypes = [vp, vp, vp, vp, _dp, vp]
     L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
     L.irotavg_viewgraph_num_connections.restype = C.c_int64

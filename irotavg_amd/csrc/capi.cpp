@@ -185,7 +185,7 @@ int64_t irotavg_make_A(int n, int f, int64_t m, const int32_t *I, int64_t *colpt
 // sw: the switches the handle lives under from here on -- the plan, the build and every solve read this copy
 int irh::graph_create(irotavg_graph **out, int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ,
                       int64_t ldqq, const irotavg_options *opt, const DevEdgeSrc *src, const Switches &sw) {
-    if (!out || (src ? !src->I || !src->QQ : !I || !QQ || ldqq < m) || m <= 0 || n_total <= 0 || f < 0 || n_total - f < 1 ||
+    if (!out || (src ? !src->I || !src->qq : !I || !QQ || ldqq < m) || m <= 0 || n_total <= 0 || f < 0 || n_total - f < 1 ||
         n_total > 0x7fffffffLL)
         return IROTAVG_ERR_BAD_ARG;
     *out = nullptr;
@@ -213,6 +213,7 @@ int irh::graph_create(irotavg_graph **out, int64_t m, int64_t n_total, int f, co
     g.nu = (int)(n_total - f);
     g.ng = 0;
     g.no = g.nu;
+    if (src && src->ordered) order_streams(g, src->caller, g.stream, true);  // the caller's arrays are ready behind its stream
     // a banded operator (+ a few loop closures) is solved directly (bcr.hip): level 0 is all such a handle needs
     // (no coarse patterns, no dense level: a third of the build)
     if (src)

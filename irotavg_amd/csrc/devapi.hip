@@ -1,0 +1,357 @@
+// devapi.hip -- the `_dev` entry points of include/irotavg_hip.h (docs/device_api.md): a caller whose arrays live in HBM
+// already (torch tensors, another library's buffers) builds, fills, solves and queries a handle without a host round trip.
+//
+// Nothing here computes: the entry points put a copy in front of and behind the kernels the host-pointer API runs, so
+// every result is bitwise what the host call gives. What is new is
+//  * the ordering contract: on entry the handle's stream waits for an event recorded on the caller's stream, before
+//    returning the caller's stream waits for an event recorded on the handle's stream (order_streams);
+//  * strided matrices (ptr, row_stride, col_stride) in elements, moved by kernels with three paths each:
+//      AoS     rs == 4, cs == 1, 16-byte aligned: 16-byte accesses on both sides;
+//      planes  rs == 1, cs even, 16-byte aligned: 16-byte accesses on both sides, two rows per thread;
+//      generic anything else that does not alias: 8-byte accesses (coalesced on the handle's side);
+//  * argument checks that keep a wrong pointer away from every kernel: strides that alias, and the lowest and highest
+//    element of every array asked of hipPointerGetAttributes (device memory of the handle's device, or BAD_ARG).
+// The kernels stream: no reuse, one or two rows per thread, 256-thread workgroups, a grid that covers the array once.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdlib>
+#include <new>
+
+#include "graph.hpp"
+#include "kernels.hpp"
+#include "marginals.hpp"
+
+namespace irh {
+namespace {
+
+constexpr int kT = 256;
+inline unsigned grid_of(long long n) { return (unsigned)std::max<long long>(1, (n + kT - 1) / kT); }
+
+enum Path { kAos = 0, kPlanes = 1, kGeneric = 2 };
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline Path path_of(const double *p, long long rs, long long cs, bool allow_aos) {
+    if (allow_aos && rs == 4 && cs == 1 && aligned16(p)) return kAos;
+    if (rs == 1 && (cs & 1) == 0 && aligned16(p)) return kPlanes;
+    return kGeneric;
+}
+
+// one value between the caller's side and the handle's side; kOut: the handle's value goes out
+template <bool kOut, typename T>
+__device__ __forceinline__ void mv(T *user, T *own) {
+    if (kOut) *user = *own;
+    else *own = *user;
+}
+
+// ---- relative rotations: strided m x 4 -> the four planes of mpad doubles, [m, mpad) zero ------------------------------
+// kAos / kPlanes: two consecutive edges per thread (mpad is a multiple of 64), kGeneric: one
+template <int kPath>
+__global__ __launch_bounds__(kT) void k_ingest_qq(long long m, long long mpad, const double *__restrict__ src, long long rs,
+                                                  long long cs, double *__restrict__ planes) {
+    const long long t = (long long)blockIdx.x * kT + threadIdx.x;
+    if (kPath == kGeneric) {
+        if (t >= mpad) return;
+#pragma unroll
+        for (int c = 0; c < 4; c++) planes[c * mpad + t] = t < m ? src[t * rs + c * cs] : 0.0;
+        return;
+    }
+    const long long k = 2 * t;
+    if (k >= mpad) return;
+    double2 v[4];  // per plane: the values of edges k, k + 1
+    if (kPath == kAos) {
+        const double2 *s2 = reinterpret_cast<const double2 *>(src);
+        const double2 z = make_double2(0.0, 0.0);
+        const double2 a0 = k < m ? s2[2 * k] : z, a1 = k < m ? s2[2 * k + 1] : z;
+        const double2 b0 = k + 1 < m ? s2[2 * k + 2] : z, b1 = k + 1 < m ? s2[2 * k + 3] : z;
+        v[0] = make_double2(a0.x, b0.x);
+        v[1] = make_double2(a0.y, b0.y);
+        v[2] = make_double2(a1.x, b1.x);
+        v[3] = make_double2(a1.y, b1.y);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const double *col = src + c * cs;
+            if (k + 1 < m) v[c] = *reinterpret_cast<const double2 *>(col + k);
+            else v[c] = make_double2(k < m ? col[k] : 0.0, 0.0);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) reinterpret_cast<double2 *>(planes + c * mpad)[t] = v[c];
+}
+
+// ---- rotations: the handle's double4 rows <-> strided n x 4 ------------------------------------------------------------
+template <bool kOut, int kPath>
+__global__ __launch_bounds__(kT) void k_rotations(long long n, double4 *__restrict__ Q, double *__restrict__ u, long long rs,
+                                                  long long cs) {
+    const long long t = (long long)blockIdx.x * kT + threadIdx.x;
+    if (kPath == kAos) {  // a row each: two 16-byte accesses on either side
+        if (t >= n) return;
+        double2 *q2 = reinterpret_cast<double2 *>(Q) + 2 * t, *u2 = reinterpret_cast<double2 *>(u) + 2 * t;
+        mv<kOut>(u2, q2);
+        mv<kOut>(u2 + 1, q2 + 1);
+    } else if (kPath == kPlanes) {  // two rows each: 16-byte accesses on the caller's columns
+        const long long k = 2 * t;
+        if (k >= n) return;
+        double *q = reinterpret_cast<double *>(Q + k);
+        if (k + 1 < n) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                double2 *uc = reinterpret_cast<double2 *>(u + c * cs + k);
+                if (kOut) *uc = make_double2(q[c], q[4 + c]);
+                else {
+                    const double2 w = *uc;
+                    q[c] = w.x;
+                    q[4 + c] = w.y;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; c++) mv<kOut>(u + c * cs + k, q + c);
+        }
+    } else {
+        if (t >= n) return;
+        double *q = reinterpret_cast<double *>(Q + t);
+#pragma unroll
+        for (int c = 0; c < 4; c++) mv<kOut>(u + t * rs + c * cs, q + c);
+    }
+}
+
+// ---- residuals: three planes of mpad doubles -> strided m x 3 (no AoS path: three columns have no 16-byte rows) --------
+template <int kPath>
+__global__ __launch_bounds__(kT) void k_residuals_out(long long m, long long mpad, const double *__restrict__ planes,
+                                                      double *__restrict__ u, long long rs, long long cs) {
+    const long long t = (long long)blockIdx.x * kT + threadIdx.x;
+    if (kPath == kPlanes) {
+        const long long k = 2 * t;
+        if (k >= m) return;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            if (k + 1 < m) *reinterpret_cast<double2 *>(u + c * cs + k) = reinterpret_cast<const double2 *>(planes + c * mpad)[t];
+            else u[c * cs + k] = planes[c * mpad + k];
+        }
+    } else {
+        if (t >= m) return;
+#pragma unroll
+        for (int c = 0; c < 3; c++) u[t * rs + c * cs] = planes[c * mpad + t];
+    }
+}
+
+// ---- argument checks (before any device work) ----------------------------------------------------------------------------
+// A strided rows x cols matrix does not alias itself when its rows do not overlap (|rs| >= cols |cs|) or its columns
+// do not (|cs| >= rows |rs|), both strides non-zero: the rule include/irotavg_hip.h states.
+bool strides_ok(int64_t rows, int cols, int64_t rs, int64_t cs) {
+    const int64_t a = std::llabs(rs), b = std::llabs(cs), lim = (int64_t)1 << 31;
+    if (a == 0 || b == 0 || a > lim || b > lim || rows <= 0) return false;
+    return a >= (int64_t)cols * b || b >= rows * a;
+}
+
+bool dev_ptr_ok(const void *p, int device) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // an address the runtime does not know: not device memory
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice && at.device == device;
+}
+// the lowest and the highest element of the matrix (negative strides reach below ptr)
+bool dev_matrix_ok(const double *p, int64_t rows, int cols, int64_t rs, int64_t cs, int device) {
+    if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return false;
+    const int64_t r = (rows - 1) * rs, c = (int64_t)(cols - 1) * cs;
+    const int64_t lo = std::min<int64_t>(0, r) + std::min<int64_t>(0, c), hi = std::max<int64_t>(0, r) + std::max<int64_t>(0, c);
+    return dev_ptr_ok(p + lo, device) && dev_ptr_ok(p + hi, device);
+}
+bool dev_vector_ok(const double *p, int64_t n, int device) { return dev_matrix_ok(p, n, 1, 1, 1, device); }
+
+// the ordering contract of a call on an existing handle
+struct Ordered {
+    Graph &g;
+    hipStream_t caller;
+    Ordered(Graph &g_, void *stream) : g(g_), caller(static_cast<hipStream_t>(stream)) { order_streams(g, caller, g.stream, true); }
+    void done() { order_streams(g, g.stream, caller, false); }
+};
+
+template <typename F>
+int guarded(F &&body) {  // no exception crosses the C boundary
+    try {
+        return body();
+    } catch (const HipError &) {
+        return IROTAVG_ERR_HIP;
+    } catch (const std::bad_alloc &) {
+        return IROTAVG_ERR_NOMEM;
+    } catch (...) {
+        return IROTAVG_ERR_HIP;
+    }
+}
+
+template <bool kOut>
+void launch_rotations(Graph &g, double *u, long long rs, long long cs) {
+    const long long n = g.n_total;
+    switch (path_of(u, rs, cs, true)) {
+    case kAos:
+        hipLaunchKernelGGL((k_rotations<kOut, kAos>), dim3(grid_of(n)), dim3(kT), 0, g.stream, n, g.Q.p, u, rs, cs);
+        break;
+    case kPlanes:
+        hipLaunchKernelGGL((k_rotations<kOut, kPlanes>), dim3(grid_of((n + 1) / 2)), dim3(kT), 0, g.stream, n, g.Q.p, u, rs, cs);
+        break;
+    default:
+        hipLaunchKernelGGL((k_rotations<kOut, kGeneric>), dim3(grid_of(n)), dim3(kT), 0, g.stream, n, g.Q.p, u, rs, cs);
+    }
+    IRH_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+void order_streams(Graph &g, hipStream_t from, hipStream_t to, bool in) {
+    hipEvent_t &ev = in ? g.ev_in : g.ev_out;
+    if (!ev) IRH_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    IRH_CHECK(hipEventRecord(ev, from));
+    IRH_CHECK(hipStreamWaitEvent(to, ev, 0));
+}
+
+void ingest_qq(Graph &g, const double *src, long long rs, long long cs) {
+    const long long m = g.m, mpad = g.mpad;
+    switch (path_of(src, rs, cs, true)) {
+    case kAos:
+        hipLaunchKernelGGL(k_ingest_qq<kAos>, dim3(grid_of(mpad / 2)), dim3(kT), 0, g.stream, m, mpad, src, rs, cs, g.qq.p);
+        break;
+    case kPlanes:
+        hipLaunchKernelGGL(k_ingest_qq<kPlanes>, dim3(grid_of(mpad / 2)), dim3(kT), 0, g.stream, m, mpad, src, rs, cs, g.qq.p);
+        break;
+    default:
+        hipLaunchKernelGGL(k_ingest_qq<kGeneric>, dim3(grid_of(mpad)), dim3(kT), 0, g.stream, m, mpad, src, rs, cs, g.qq.p);
+    }
+    IRH_CHECK(hipGetLastError());
+}
+
+}  // namespace irh
+
+using namespace irh;
+
+extern "C" {
+
+int irotavg_graph_create_dev(irotavg_graph **out, int64_t m, int64_t n_total, int f, const int32_t *I_dev,
+                             const double *QQ_dev, int64_t qq_rs, int64_t qq_cs, const irotavg_options *opt, void *stream) {
+    if (!out) return IROTAVG_ERR_BAD_ARG;
+    *out = nullptr;
+    if (!I_dev || !QQ_dev || m <= 0 || m > 0x3fffffffLL || n_total <= 0 || f < 0 || n_total - f < 1 ||
+        n_total > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(I_dev) & 7) != 0 || !strides_ok(m, 4, qq_rs, qq_cs))
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        int device = opt ? opt->device : -1;
+        if (device < 0) IRH_CHECK(hipGetDevice(&device));
+        if (!dev_ptr_ok(I_dev, device) || !dev_ptr_ok(I_dev + 2 * m - 1, device) ||
+            !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device))
+            return IROTAVG_ERR_BAD_ARG;
+        DevEdgeSrc src;
+        src.I = reinterpret_cast<const int2 *>(I_dev);
+        src.qq = QQ_dev;
+        src.qq_rs = qq_rs;
+        src.qq_cs = qq_cs;
+        src.ordered = true;
+        src.caller = static_cast<hipStream_t>(stream);
+        // (an edge index out of range is found by the build's first kernel: IROTAVG_ERR_BAD_ARG, the handle destroyed)
+        const int rc = graph_create(out, m, n_total, f, nullptr, nullptr, 0, opt, &src, read_switches());
+        if (rc == IROTAVG_OK) {
+            Graph &g = graph_of(*out);
+            order_streams(g, g.stream, src.caller, false);
+        }
+        return rc;
+    });
+}
+
+int irotavg_graph_set_rotations_dev(irotavg_graph *h, const double *Q_dev, int64_t rs, int64_t cs, void *stream) {
+    if (!h || !Q_dev || !strides_ok(graph_of(h).n_total, 4, rs, cs)) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        Graph &g = graph_of(h);
+        if (!dev_matrix_ok(Q_dev, g.n_total, 4, rs, cs, g.device)) return IROTAVG_ERR_BAD_ARG;
+        Ordered o(g, stream);
+        launch_rotations<false>(g, const_cast<double *>(Q_dev), rs, cs);
+        o.done();
+        return IROTAVG_OK;
+    });
+}
+
+int irotavg_graph_get_rotations_dev(irotavg_graph *h, double *Q_dev, int64_t rs, int64_t cs, void *stream) {
+    if (!h || !Q_dev || !strides_ok(graph_of(h).n_total, 4, rs, cs)) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        Graph &g = graph_of(h);
+        if (!dev_matrix_ok(Q_dev, g.n_total, 4, rs, cs, g.device)) return IROTAVG_ERR_BAD_ARG;
+        Ordered o(g, stream);
+        launch_rotations<true>(g, Q_dev, rs, cs);
+        o.done();
+        return IROTAVG_OK;
+    });
+}
+
+int irotavg_graph_set_weights_dev(irotavg_graph *h, const double *w_dev, void *stream) {
+    if (!h || !w_dev) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        Graph &g = graph_of(h);
+        if (!dev_vector_ok(w_dev, g.m, g.device)) return IROTAVG_ERR_BAD_ARG;
+        Ordered o(g, stream);
+        IRH_CHECK(hipMemcpyAsync(g.dw.p, w_dev, sizeof(double) * (size_t)g.m, hipMemcpyDeviceToDevice, g.stream));
+        o.done();
+        return IROTAVG_OK;
+    });
+}
+
+int irotavg_graph_get_weights_dev(irotavg_graph *h, double *w_dev, void *stream) {
+    if (!h || !w_dev) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        Graph &g = graph_of(h);
+        if (!dev_vector_ok(w_dev, g.m, g.device)) return IROTAVG_ERR_BAD_ARG;
+        Ordered o(g, stream);
+        IRH_CHECK(hipMemcpyAsync(w_dev, g.dw.p, sizeof(double) * (size_t)g.m, hipMemcpyDeviceToDevice, g.stream));
+        o.done();
+        return IROTAVG_OK;
+    });
+}
+
+int irotavg_graph_get_residuals_dev(irotavg_graph *h, double *out_dev, int64_t rs, int64_t cs, void *stream) {
+    if (!h || !out_dev || !strides_ok(graph_of(h).m, 3, rs, cs)) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        Graph &g = graph_of(h);
+        if (!dev_matrix_ok(out_dev, g.m, 3, rs, cs, g.device)) return IROTAVG_ERR_BAD_ARG;
+        Ordered o(g, stream);
+        const long long m = g.m, mpad = g.mpad;
+        if (path_of(out_dev, rs, cs, false) == kPlanes)
+            hipLaunchKernelGGL(k_residuals_out<kPlanes>, dim3(grid_of((m + 1) / 2)), dim3(kT), 0, g.stream, m, mpad, g.er.p,
+                               out_dev, (long long)rs, (long long)cs);
+        else
+            hipLaunchKernelGGL(k_residuals_out<kGeneric>, dim3(grid_of(m)), dim3(kT), 0, g.stream, m, mpad, g.er.p, out_dev,
+                               (long long)rs, (long long)cs);
+        IRH_CHECK(hipGetLastError());
+        o.done();
+        return IROTAVG_OK;
+    });
+}
+
+int irotavg_graph_rotation_variance_dev(irotavg_graph *h, double *var_dev, double *scale, void *stream) {
+    if (!h || !var_dev) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        Graph &g = graph_of(h);
+        if (!dev_vector_ok(var_dev, g.n_total, g.device)) return IROTAVG_ERR_BAD_ARG;
+        Ordered o(g, stream);
+        const int rc = rotation_variance(g, nullptr, 0, nullptr, nullptr, scale, var_dev);
+        o.done();
+        return rc;
+    });
+}
+
+int irotavg_graph_edge_diagnostics_dev(irotavg_graph *h, double *edge_var_dev, double *leverage_dev, double *chi2_dev,
+                                       double *scale, void *stream) {
+    if (!h || (!edge_var_dev && !leverage_dev && !chi2_dev && !scale)) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        Graph &g = graph_of(h);
+        for (double *p : {edge_var_dev, leverage_dev, chi2_dev})
+            if (p && !dev_vector_ok(p, g.m, g.device)) return IROTAVG_ERR_BAD_ARG;
+        Ordered o(g, stream);
+        const int rc = edge_diagnostics(g, edge_var_dev, leverage_dev, chi2_dev, scale, true);
+        o.done();
+        return rc;
+    });
+}
+
+}  // extern "C"

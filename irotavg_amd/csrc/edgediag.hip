@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void k_ed_closures(int nf, long long mpad, con
 
 }  // namespace
 
-int edge_diagnostics(Graph &g, double *edge_var, double *leverage, double *chi2, double *scale) {
+int edge_diagnostics(Graph &g, double *edge_var, double *leverage, double *chi2, double *scale, bool dev_out) {
     if (g.ng != 0 || g.is_clone || g.levels.empty()) return IROTAVG_ERR_UNSUPPORTED;
     const bool dense = g.no <= 2048, band = !dense && g.bcr_B > 0;
     if (!dense && !band) return IROTAVG_ERR_UNSUPPORTED;  // no factorisation to read all edges off
@@ -229,10 +229,13 @@ int edge_diagnostics(Graph &g, double *edge_var, double *leverage, double *chi2,
         } else if (read_dead(g, dead)) {
             return IROTAVG_ERR_SOLVER;
         }
+        // Both edge kernels raise the dead-pivot word in the very pass that writes the arrays, on every route: the
+        // caller's arrays -- host or device -- are filled from the query's own buffers once that word has been read.
         const size_t bytes = sizeof(double) * (size_t)g.m;
-        if (edge_var) IRH_CHECK(hipMemcpyAsync(edge_var, dev.p, bytes, hipMemcpyDeviceToHost, g.stream));
-        if (leverage) IRH_CHECK(hipMemcpyAsync(leverage, dlev.p, bytes, hipMemcpyDeviceToHost, g.stream));
-        if (chi2) IRH_CHECK(hipMemcpyAsync(chi2, dchi.p, bytes, hipMemcpyDeviceToHost, g.stream));
+        const hipMemcpyKind kind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (edge_var) IRH_CHECK(hipMemcpyAsync(edge_var, dev.p, bytes, kind, g.stream));
+        if (leverage) IRH_CHECK(hipMemcpyAsync(leverage, dlev.p, bytes, kind, g.stream));
+        if (chi2) IRH_CHECK(hipMemcpyAsync(chi2, dchi.p, bytes, kind, g.stream));
         IRH_CHECK(hipStreamSynchronize(g.stream));
     }
     if (scale) *scale = s2;

@@ -79,18 +79,6 @@ __global__ __launch_bounds__(kT) void k_gb_edges(long long m, long long mpad, in
     eflag[k] = fl;
 }
 
-// relative rotations held on the device as one double4 per edge -> the four planes of the edge kernels
-__global__ __launch_bounds__(kT) void k_gb_qq_planes(long long m, long long mpad, const double4 *__restrict__ q,
-                                                     double *__restrict__ planes) {
-    const long long k = (long long)blockIdx.x * kT + threadIdx.x;
-    if (k >= mpad) return;
-    const double4 v = k < m ? q[k] : make_double4(0, 0, 0, 0);
-    planes[k] = v.x;
-    planes[mpad + k] = v.y;
-    planes[2 * mpad + k] = v.z;
-    planes[3 * mpad + k] = v.w;
-}
-
 // level-0 matrix entries and boundary slots, generated in EDGE order: edge k yields the entries 2k (row j:
 // the +1 coefficient) and 2k + 1 (row i) when both endpoints are free and differ, otherwise at most one
 // boundary slot. Keys of what an edge does not yield are `inv` (sorted to the end).
@@ -484,9 +472,8 @@ int build_graph_device(Graph &g, const int32_t *I, const double *QQ, int64_t ldq
         IRH_CHECK(hipMemcpyAsync(dI.p, I, sizeof(int) * 2 * (size_t)m, hipMemcpyHostToDevice, s));
     }
     g.qq.alloc((size_t)4 * g.mpad);
-    if (src)  // the edge list is resident on the device already (resident.hip): planes from its records, no upload
-        hipLaunchKernelGGL(k_gb_qq_planes, dim3(grid_of(g.mpad)), dim3(kT), 0, s, (long long)m, (long long)g.mpad, src->QQ,
-                           g.qq.p);
+    if (src)  // the edge list is on the device already (resident.hip, devapi.hip): planes from its rows, no upload
+        ingest_qq(g, src->qq, src->qq_rs, src->qq_cs);
     else if (g.mpad > m)
         for (int c = 0; c < 4; c++)
             IRH_CHECK(hipMemsetAsync(g.qq.p + (size_t)c * g.mpad + m, 0, sizeof(double) * (size_t)(g.mpad - m), s));

@@ -121,8 +121,12 @@ struct Graph {
     // kernel stores last (publish_parts)
     int *h_seq() { return reinterpret_cast<int *>(hpin + 8192); }
     int pub_seq = 0;
+    // devapi.hip: the two events behind the ordering contract of the `_dev` entry points (made on first use)
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
     ~Graph() {
         bcr_up_release(*this);
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        if (ev_out) (void)hipEventDestroy(ev_out);
         if (hpin) PinPool::get().give(hpin);
     }
     Graph() = default;
@@ -183,17 +187,27 @@ struct HierPlan {
     std::vector<int> n, agg;  // rows and aggregation factor per level (agg of the coarsest level: 0)
 };
 HierPlan plan_hierarchy(Graph &g, int n0, int64_t nnz0, bool far0);
-// a build whose edge list lives on the device already (a resident view-graph, resident.hip): m pairs in the caller's
-// view ids, one double4 [x y z w] per edge, and the caller id -> row map of this problem (nullptr: identity)
+// a build whose edge list lives on the device already (a resident view-graph, resident.hip; a caller of
+// irotavg_graph_create_dev, devapi.hip): m pairs in the caller's view ids, the relative rotations as a strided m x 4
+// matrix [x y z w] (element (k, c) at qq[k qq_rs + c qq_cs]; one double4 per edge = strides 4, 1), and the caller id ->
+// row map of this problem (nullptr: identity). ordered: the arrays are produced on `caller` -- the handle's stream
+// waits for what is enqueued there before it reads them.
 struct DevEdgeSrc {
     const int2 *I = nullptr;
-    const double4 *QQ = nullptr;
+    const double *qq = nullptr;
+    long long qq_rs = 4, qq_cs = 1;
     const int *relabel = nullptr;
+    bool ordered = false;
+    hipStream_t caller = nullptr;
 };
 int build_graph(Graph &g, const int32_t *I, const double *QQ, int64_t ldqq);
 int build_graph_host(Graph &g, const int32_t *I, const double *QQ, int64_t ldqq);
 int build_graph_device(Graph &g, const int32_t *I, const double *QQ, int64_t ldqq, const DevEdgeSrc *src = nullptr);
 int finish_build(Graph &g, const BuildTail &T);
+// devapi.hip: a strided m x 4 matrix on the device -> the handle's four qq planes, the padding [m, mpad) zeroed
+void ingest_qq(Graph &g, const double *src, long long rs, long long cs);
+// devapi.hip: everything enqueued on `to` after this call runs behind what is enqueued on `from` now
+void order_streams(Graph &g, hipStream_t from, hipStream_t to, bool in);
 
 // solver entry points (solver.hip)
 void launch_edge_residual(Graph &g, bool weights_to_one = false);
@@ -382,7 +396,9 @@ void bcr_shard_closures_forward(Graph &g, BcrTop &T, int rank);
 void bcr_top_solve_closures(Graph &g, BcrTop &T);
 void bcr_shard_closures_correct(Graph &g, BcrTop &T);
 // marginals.hip: irotavg_graph_rotation_variance (arguments checked by the caller; outputs written only on success)
-int rotation_variance(Graph &g, double *var, int64_t npairs, const int32_t *pairs, double *pair_var, double *scale);
+// var_dev: the marginals go to this DEVICE array (n_total entries) instead of var
+int rotation_variance(Graph &g, double *var, int64_t npairs, const int32_t *pairs, double *pair_var, double *scale,
+                      double *var_dev = nullptr);
 // dense.hip
 void dense_refresh(Graph &g);
 void dense_select_slot(Graph &g, int slot);

@@ -474,6 +474,13 @@ __global__ __launch_bounds__(256) void k_mv_scale(long long m, long long mpad, c
 
 int grid1(long long n) { return (int)((n + 255) / 256); }
 
+// the marginals of the nu free views -> the caller's device array of n_total entries (0 for the f fixed views)
+__global__ __launch_bounds__(256) void k_mv_var_out(long long n_total, int f, const double *__restrict__ dvar,
+                                                    double *__restrict__ out) {
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v < n_total) out[v] = v < f ? 0.0 : dvar[v - f];
+}
+
 constexpr int kPairChunk = 1024;  // pair columns per multi right-hand-side solve
 
 }  // namespace
@@ -672,8 +679,14 @@ int dense_inverse(Graph &g, DenseInverse &Dn, DevBuf<int> &dead) {
 
 namespace {
 
+// var_dev: the marginals go to the caller's device array (behind the dead-pivot test: written only on success)
+void var_to_device(Graph &g, const double *dvar, double *var_dev) {
+    hipLaunchKernelGGL(k_mv_var_out, dim3(grid1(g.n_total)), dim3(256), 0, g.stream, (long long)g.n_total, g.f, dvar,
+                       var_dev);
+}
+
 int band_path(Graph &g, bool want_var, std::vector<double> &var, const std::vector<int> &pi,
-              const std::vector<int> &pj, std::vector<double> &pv) {
+              const std::vector<int> &pj, std::vector<double> &pv, double *var_dev) {
     BandFactor F;
     BandClosures C;
     DevBuf<int> dead;
@@ -690,9 +703,15 @@ int band_path(Graph &g, bool want_var, std::vector<double> &var, const std::vect
         dvar.alloc((size_t)F.n);
         hipLaunchKernelGGL(k_mv_band_var, dim3(grid1(F.n)), dim3(256), 0, g.stream, F.n, F.B, F.D.p,
                            C.k > 0 ? corr.p : nullptr, dvar.p, dead.p);
-        var.resize((size_t)F.n);
-        IRH_CHECK(hipMemcpyAsync(var.data(), dvar.p, sizeof(double) * F.n, hipMemcpyDeviceToHost, g.stream));
+        if (!var_dev) {
+            var.resize((size_t)F.n);
+            IRH_CHECK(hipMemcpyAsync(var.data(), dvar.p, sizeof(double) * F.n, hipMemcpyDeviceToHost, g.stream));
+        }
         if (read_dead(g, dead)) return IROTAVG_ERR_SOLVER;
+        if (var_dev) {
+            var_to_device(g, dvar.p, var_dev);
+            IRH_CHECK(hipStreamSynchronize(g.stream));  // dvar goes back to the pool
+        }
     }
     band_pairs(g, F, C, pi, pj, pv);
     IRH_CHECK(hipStreamSynchronize(g.stream));
@@ -700,13 +719,15 @@ int band_path(Graph &g, bool want_var, std::vector<double> &var, const std::vect
 }
 
 int dense_path(Graph &g, bool want_var, std::vector<double> &var, const std::vector<int> &pi,
-               const std::vector<int> &pj, std::vector<double> &pv) {
+               const std::vector<int> &pj, std::vector<double> &pv, double *var_dev) {
     DenseInverse Dn;
     DevBuf<int> dead;
     const int rc = dense_inverse(g, Dn, dead);
     if (rc != IROTAVG_OK) return rc;
     const int n = Dn.n, npad = Dn.npad;
-    if (want_var) {
+    if (want_var && var_dev) {
+        var_to_device(g, Dn.dvar.p, var_dev);
+    } else if (want_var) {
         var.resize((size_t)n);
         IRH_CHECK(hipMemcpyAsync(var.data(), Dn.dvar.p, sizeof(double) * n, hipMemcpyDeviceToHost, g.stream));
     }
@@ -783,11 +804,13 @@ int pcg_pairs(Graph &g, const std::vector<int> &pi, const std::vector<int> &pj, 
 
 }  // namespace
 
-int rotation_variance(Graph &g, double *var, int64_t npairs, const int32_t *pairs, double *pair_var, double *scale) {
+int rotation_variance(Graph &g, double *var, int64_t npairs, const int32_t *pairs, double *pair_var, double *scale,
+                      double *var_dev) {
     if (g.ng != 0 || g.is_clone || g.levels.empty()) return IROTAVG_ERR_UNSUPPORTED;
     const int f = g.f;
     const bool dense = g.no <= 2048, band = !dense && g.bcr_B > 0;
-    if (!dense && !band && var) return IROTAVG_ERR_UNSUPPORTED;  // marginals of a PCG handle: not offered
+    const bool want_var = var || var_dev;
+    if (!dense && !band && want_var) return IROTAVG_ERR_UNSUPPORTED;  // marginals of a PCG handle: not offered
     // pair ends as operator rows (-1: a fixed view, dropped from u)
     std::vector<int> pi((size_t)npairs), pj((size_t)npairs);
     for (int64_t t = 0; t < npairs; t++) {
@@ -795,8 +818,8 @@ int rotation_variance(Graph &g, double *var, int64_t npairs, const int32_t *pair
         pj[(size_t)t] = pairs[2 * t + 1] >= f ? pairs[2 * t + 1] - f : -1;
     }
     std::vector<double> v, pv;
-    const int rc = dense  ? dense_path(g, var != nullptr, v, pi, pj, pv)
-                   : band ? band_path(g, var != nullptr, v, pi, pj, pv)
+    const int rc = dense  ? dense_path(g, want_var, v, pi, pj, pv, var_dev)
+                   : band ? band_path(g, want_var, v, pi, pj, pv, var_dev)
                           : pcg_pairs(g, pi, pj, pv);
     if (rc != IROTAVG_OK) return rc;
     double num = 0.0, cnt = 0.0;

@@ -45,7 +45,8 @@ struct DenseInverse {
 };
 int dense_inverse(Graph &g, DenseInverse &Dn, DevBuf<int> &dead);
 
-// edgediag.hip: irotavg_graph_edge_diagnostics (arguments checked by the caller; outputs written only on success)
-int edge_diagnostics(Graph &g, double *edge_var, double *leverage, double *chi2, double *scale);
+// edgediag.hip: irotavg_graph_edge_diagnostics (arguments checked by the caller; outputs written only on success).
+// dev_out: the three arrays are DEVICE pointers (irotavg_graph_edge_diagnostics_dev); scale stays a host pointer
+int edge_diagnostics(Graph &g, double *edge_var, double *leverage, double *chi2, double *scale, bool dev_out = false);
 
 }  // namespace irh

@@ -248,7 +248,7 @@ int resident_prologue(Resident &r, long n_views, long view_lo, long n_edges, lon
     // ---- the solver's handle, built on the device from the resident records
     DevEdgeSrc src;
     src.I = r.I.p;
-    src.QQ = r.QQ.p;
+    src.qq = reinterpret_cast<const double *>(r.QQ.p);  // one double4 per edge: strides 4, 1
     src.relabel = r.v2i.p;
     const int rc = graph_create(h, ne_solve, n_views, f, nullptr, nullptr, 0, &opt, &src, sw);
     if (rc != IROTAVG_OK) return rc;

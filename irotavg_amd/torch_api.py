@@ -1,0 +1,153 @@
+"""torch front-end of the device-pointer handle API (irotavg_graph_*_dev of include/irotavg_hip.h,
+docs/device_api.md): tensors on the ROCm device go in and come out, nothing passes through the host, and every call
+runs on torch's current stream -- no synchronise before or after. Plumbing only: all numerics live in
+libirotavg_hip.so (irotavg_amd/csrc/devapi.hip and the kernels behind the host-pointer API)."""
+import ctypes as C
+
+import torch
+
+from . import capi
+
+INT32_MAX = 2 ** 31 - 1
+
+
+def matrix_strides(t):
+    """(row_stride, col_stride) in elements of a 2-D tensor, as the C ABI takes a strided matrix."""
+    if t.dim() != 2:
+        raise ValueError("a 2-D tensor is needed, got %d-D" % t.dim())
+    return int(t.stride(0)), int(t.stride(1))
+
+
+def _check(t, name, dtypes, shape, device=None, placed=True):
+    """dtype, then shape, then (placed) placement: TypeError / ValueError before anything reaches the C library."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype not in dtypes:
+        raise TypeError("%s must be %s, got %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+    if t.dim() != len(shape) or any(s is not None and int(t.shape[k]) != s for k, s in enumerate(shape)):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple("*" if s is None else s for s in shape),
+                                                            tuple(t.shape)))
+    if not placed:
+        return t
+    if not t.is_cuda:
+        raise TypeError("%s must live on the ROCm device, got a %s tensor" % (name, t.device.type))
+    if device is not None and t.device != device:
+        raise ValueError("%s is on %s, the handle on %s" % (name, t.device, device))
+    return t
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+class TorchGraph(capi.Graph):
+    """A graph handle built from tensors on the device (irotavg_graph_create_dev). edge_index: (m, 2) int32 or int64
+    (narrowed on the device; a value outside int32 range makes the build reject the graph), QQ: (m, 4) float64 with
+    any strides, columns [x, y, z, w]. The handle copies both; the tensors are only read. Everything a capi.Graph
+    offers through host arrays (irls, l1ra, stats, fingerprint, ...) works on this handle too."""
+
+    def __init__(self, edge_index, QQ, n_total, f, **opts):
+        self._h = C.c_void_p()
+        _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), placed=False)
+        _check(QQ, "QQ", (torch.float64,), (int(edge_index.shape[0]), 4), placed=False)  # dtypes and shapes of both first
+        _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
+        _check(QQ, "QQ", (torch.float64,), (int(edge_index.shape[0]), 4), edge_index.device)
+        self.device = QQ.device
+        self.m, self.n_total, self.f = int(edge_index.shape[0]), int(n_total), int(f)
+        self.nu = self.n_total - self.f
+        with torch.cuda.device(self.device):
+            ei = edge_index
+            if ei.dtype == torch.int64:  # narrowed on the device: what does not fit becomes an index the build rejects
+                ei = torch.where((ei < 0) | (ei > INT32_MAX), torch.full_like(ei, -1), ei).to(torch.int32)
+            ei = ei.contiguous()
+            o = capi.default_options(**opts)
+            if o.device < 0:
+                o.device = self.device.index
+            rs, cs = matrix_strides(QQ)
+            rc = capi.lib().irotavg_graph_create_dev(C.byref(self._h), self.m, self.n_total, self.f, _ptr(ei), _ptr(QQ),
+                                                     rs, cs, C.byref(o), _stream(self.device))
+        if rc != capi.OK:
+            self._h = C.c_void_p()
+            if rc == capi.ERR_BAD_ARG:
+                raise ValueError("irotavg_graph_create_dev: bad argument (sizes, strides that alias, or an edge index "
+                                 "outside [0, n_total) / outside int32 range)")
+            raise capi.IrotavgError(rc, "irotavg_graph_create_dev")
+
+    def _call(self, name, *args):
+        with torch.cuda.device(self.device):
+            return getattr(capi.lib(), name)(self._h, *args, _stream(self.device))
+
+    def _new(self, *shape):
+        return torch.empty(shape, dtype=torch.float64, device=self.device)
+
+    # ---- copies: asynchronous, ordered on the current stream -----------------------------------------------------------
+    def set_rotations(self, Q):
+        _check(Q, "Q", (torch.float64,), (self.n_total, 4), self.device)
+        capi.check(self._call("irotavg_graph_set_rotations_dev", _ptr(Q), *matrix_strides(Q)), "set_rotations_dev")
+
+    def rotations(self, out=None):
+        out = self._new(self.n_total, 4) if out is None else _check(out, "out", (torch.float64,), (self.n_total, 4),
+                                                                    self.device)
+        capi.check(self._call("irotavg_graph_get_rotations_dev", _ptr(out), *matrix_strides(out)), "get_rotations_dev")
+        return out
+
+    def set_weights(self, w):
+        _check(w, "w", (torch.float64,), (self.m,), self.device)
+        w = w.contiguous()
+        capi.check(self._call("irotavg_graph_set_weights_dev", _ptr(w)), "set_weights_dev")
+
+    def weights(self, out=None):
+        out = self._new(self.m) if out is None else _check(out, "out", (torch.float64,), (self.m,), self.device)
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+        capi.check(self._call("irotavg_graph_get_weights_dev", _ptr(out)), "get_weights_dev")
+        return out
+
+    def residuals(self, out=None):
+        """(m, 3) residuals of the last edge_residual(); a new tensor is three planes (the handle's own layout)."""
+        out = self._new(3, self.m).t() if out is None else _check(out, "out", (torch.float64,), (self.m, 3), self.device)
+        capi.check(self._call("irotavg_graph_get_residuals_dev", _ptr(out), *matrix_strides(out)), "get_residuals_dev")
+        return out
+
+    # ---- queries ---------------------------------------------------------------------------------------------------------
+    def variance(self, out=None, allow_rc=()):
+        """irotavg_graph_rotation_variance_dev: dict(rc, var (n_total, on the device), scale). var is written only on
+        success (pass `out` to see that)."""
+        var = self._new(self.n_total) if out is None else _check(out, "out", (torch.float64,), (self.n_total,), self.device)
+        if not var.is_contiguous():
+            raise ValueError("out must be contiguous")
+        scale = C.c_double(float("nan"))
+        rc = self._call("irotavg_graph_rotation_variance_dev", _ptr(var), C.byref(scale))
+        if rc != capi.OK and rc not in allow_rc:
+            raise capi.IrotavgError(rc, "irotavg_graph_rotation_variance_dev")
+        return dict(rc=rc, var=var, scale=scale.value)
+
+    def edge_diagnostics(self, edge_var=True, leverage=True, chi2=True, allow_rc=()):
+        """irotavg_graph_edge_diagnostics_dev: dict(rc, edge_var, leverage, chi2 (m each on the device, or None), scale).
+        Each argument is True (a new tensor), False (not computed) or a contiguous float64 tensor of m entries to fill."""
+        outs = []
+        for name, want in (("edge_var", edge_var), ("leverage", leverage), ("chi2", chi2)):
+            if want is True:
+                outs.append(self._new(self.m))
+            elif want is False or want is None:
+                outs.append(None)
+            else:
+                _check(want, name, (torch.float64,), (self.m,), self.device)
+                if not want.is_contiguous():
+                    raise ValueError("%s must be contiguous" % name)
+                outs.append(want)
+        scale = C.c_double(float("nan"))
+        rc = self._call("irotavg_graph_edge_diagnostics_dev", *[None if t is None else _ptr(t) for t in outs],
+                        C.byref(scale))
+        if rc != capi.OK and rc not in allow_rc:
+            raise capi.IrotavgError(rc, "irotavg_graph_edge_diagnostics_dev")
+        return dict(rc=rc, edge_var=outs[0], leverage=outs[1], chi2=outs[2], scale=scale.value)
+
+    # the host-array forms of the parent stay reachable under their own names
+    host_set_rotations = capi.Graph.set_rotations
+    host_set_weights = capi.Graph.set_weights
+    host_edge_diagnostics = capi.Graph.edge_diagnostics
