@@ -149,13 +149,6 @@ struct BcrState {
 
 void BcrDeleter::operator()(BcrState *p) const { delete p; }
 
-__device__ __forceinline__ double bcr_readlane(double v, int lane) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, lane);
-    hi = __builtin_amdgcn_readlane(hi, lane);
-    return __hiloint2double(hi, lo);
-}
-
 // Sum over aligned groups of sixteen lanes, every lane gets it: the butterfly of __shfl_xor(1, 2, 4, 8) -- the same
 // additions, bit for bit -- by DPP moves (quad permutes, then the mirrors of half a row and of a row: after two steps all
 // four lanes of a quad hold the quad's sum, so WHICH lane of the other quad / half a lane adds does not matter) instead
@@ -209,12 +202,12 @@ __device__ __forceinline__ void bcr_invert(double *Dm, int lane, int *dead = nul
     auto pivot_inverse = [&](double tk, int k, int kh) {
         // reciprocal by v_rcp_f64 + two Newton steps (the IEEE division sequence is three times as long and sits on
         // the chain from pivot to pivot)
-        const double p0 = bcr_readlane(tk, k + 32 * kh);
-        const bool alive = p0 > bcr_readlane(dgt, k);
+        const double p0 = readlane_d(tk, k + 32 * kh);
+        const bool alive = p0 > readlane_d(dgt, k);
         ndead += alive ? 0 : 1;
         double p = p0;
         if (reg && !alive) {
-            const double ref = bcr_readlane(dg, k);
+            const double ref = readlane_d(dg, k);
             p = ref > 0.0 ? ref : 1.0;
         }
         double x = __builtin_amdgcn_rcp(p);

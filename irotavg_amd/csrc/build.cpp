@@ -186,16 +186,7 @@ int build_graph_host(Graph &g, const int32_t *I, const double *QQ, int64_t ldqq)
             }
             ei[k] = i;
             ej[k] = j;
-            uint8_t fl = 0;
-            if (j >= f) {
-                if (i >= f && i == j) {
-                    fl = EF_CI;  // self loop: the -1 overwrites the +1
-                } else {
-                    fl |= EF_CJ;
-                    if (i >= f) fl |= EF_CI;
-                }
-            }
-            eflag[k] = fl;
+            eflag[k] = edge_flags(i, j, f);
         }
     });
     if (bad) return IROTAVG_ERR_BAD_ARG;

@@ -375,11 +375,19 @@ constexpr double kDeadTol = 1e-13;
 constexpr int kSellUnroll = 8;  // slice widths are multiples of this (batch size of the row loops)
 constexpr int kBandMax = 4;     // coarsest operators up to this half-bandwidth are inverted by the banded kernels (dense.hip)
 
-// per-edge flag bits (host-built; see build.cpp)
+// per-edge flag bits
 enum : uint8_t {
     EF_CJ = 1,  // A(k, j-f) = +1 present   (ral/l1_irls.cpp:770-772)
     EF_CI = 2,  // A(k, i-f) = -1 present   (ral/l1_irls.cpp:774-776)
 };
+// make_A's coefficient rule for the edge (i, j), views below f fixed (ral/l1_irls.cpp:764-777): j free -> +1 at j - f;
+// i free as well -> -1 at i - f; j fixed -> the row is zero. The one statement of the rule: the builds store its byte,
+// the edge passes that have i, j and f in registers evaluate it instead of loading the byte.
+__host__ __device__ inline uint8_t edge_flags(int i, int j, int f) {
+    const bool cj = j >= f && i != j;  // self loop: the -1 overwrites the +1
+    const bool ci = j >= f && i >= f;
+    return (uint8_t)((cj ? EF_CJ : 0) | (ci ? EF_CI : 0));  // two independent bits: a test of one folds to its condition
+}
 // boundary-slot flag bits
 enum : uint8_t {
     BF_IRLS = 1,  // contributes to A'D^2A (the make_A matrix has a coefficient for this row)

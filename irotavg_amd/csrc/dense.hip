@@ -30,14 +30,6 @@ namespace irh {
 constexpr int GJB = 32;   // block size of the Gauss-Jordan sweep
 constexpr int GJT = 64;   // tile edge of the update kernel
 
-// broadcast of lane `lane` (wave-uniform, here a compile-time constant) through SGPRs
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, lane);
-    hi = __builtin_amdgcn_readlane(hi, lane);
-    return __hiloint2double(hi, lo);
-}
-
 // In-register Gauss-Jordan inversion of a 32 x 32 SPD block: lane l (and its mirror l + 32) holds
 // row l in d[0..31]; pivot rows are broadcast by lane reads. Per pivot and column: two v_readlane
 // and ONE fma (the pivot scaling is folded into the lane's multiplier and into a per-lane row

@@ -65,13 +65,8 @@ __global__ __launch_bounds__(kT) void k_gb_edges(long long m, long long mpad, in
         if (i < 0 || j < 0 || i >= n_total || j >= n_total) {
             atomicOr(info, 1);
             i = j = 0;
-        } else if (j >= f) {
-            if (i >= f && i == j) {
-                fl = EF_CI;  // self loop: the -1 overwrites the +1
-            } else {
-                fl |= EF_CJ;
-                if (i >= f) fl |= EF_CI;
-            }
+        } else {
+            fl = edge_flags(i, j, f);
         }
     }
     ei[k] = i;

@@ -29,6 +29,24 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;  // lane 0
 }
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+    return v;
+}
+
+// broadcast of lane `lane` (wave-uniform) through SGPRs: two v_readlane
+__device__ __forceinline__ double readlane_d(double v, int lane) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_readlane(lo, lane);
+    hi = __builtin_amdgcn_readlane(hi, lane);
+    return __hiloint2double(hi, lo);
+}
 
 // sum over aligned groups of `g` consecutive lanes (g a power of two <= 64); every lane gets it
 __device__ __forceinline__ double seg_sum(double v, int g) {
@@ -316,7 +334,7 @@ __device__ __forceinline__ double4 qmul(const double4 a, const double4 b) {
 #define IRH_EPS 2.2204e-16  // ral/l1_irls.hpp:40
 
 // K1's residual of one edge: delta_rel + log_map (ral/l1_irls.cpp:109-127, 498-532). The one copy every kernel that needs
-// "the residual K1 computes" uses (solver.hip's edge passes, wincov.hip).
+// "the residual K1 computes" uses (solver.hip's edge passes, both window kernels, wincov.hip).
 __device__ __forceinline__ void edge_log(const double4 qi, double4 qj, const double4 qq,
                                          double &ox, double &oy, double &oz) {
     qj.w = -qj.w;  // the reference's "inverse": only w negated (ral/l1_irls.cpp:114-115)
@@ -338,11 +356,71 @@ __device__ __forceinline__ void edge_log(const double4 qi, double4 qj, const dou
     }
 }
 
-// One view's share of K6 (ral/l1_irls.cpp:729-737, exp_map :471-492): returns ||x|| (the view's term of the score, taken
-// BEFORE the exp map), Q[idx] <- Q[idx] (x) exp(x) (right-multiply, no renormalisation; every non-finite entry of the
-// exponential -> 0, :491). A step that is not finite leaves its rotation alone (the score turns non-finite instead).
-__device__ __forceinline__ double step_apply(double x0, double x1, double x2, double4 *__restrict__ Q, int idx, bool write) {
-    const double th = sqrt(x0 * x0 + x1 * x1 + x2 * x2);
+// K2's 14 robust weights (ral/l1_irls.cpp:617-727): the weight of an edge from e2 = |E_k|^2 and its previous weight
+__device__ __forceinline__ double robust_weight(int cost, double sigma, double e2, double prev) {
+    switch (cost) {
+    case IROTAVG_L2:
+        return prev;
+    case IROTAVG_L05: {
+        double w = 1.0 / pow(e2, 3. / 8.);
+        return w > 1e4 ? 1e4 : w;
+    }
+    case IROTAVG_L1: {
+        double w = 1.0 / sqrt(sqrt(e2));
+        return w > 1e4 ? 1e4 : w;
+    }
+    case IROTAVG_L15: {
+        double w = 1.0 / sqrt(sqrt(sqrt(e2)));
+        return w > 1e4 ? 1e4 : w;
+    }
+    case IROTAVG_GEMAN_MCCLURE:
+        return 1.0 / (e2 + sigma * sigma);
+    case IROTAVG_HUBER: {  // weights of inliers keep their previous value (:647-649)
+        const double e = sqrt(e2) / (1.345 * sigma);
+        return e >= 1 ? sqrt(1. / e) : prev;
+    }
+    case IROTAVG_PSEUDO_HUBER:
+        return 1.0 / sqrt(sqrt(1.0 + e2 / (sigma * sigma)));
+    case IROTAVG_ANDREWS: {
+        const double e = sqrt(e2) / (1.339 * sigma);
+        double w = sqrt(sin(e) / e);
+        if (e >= IRH_PI)
+            w = 0;
+        else if (e < .0001)
+            w = 1;
+        if (w < 0.0001) w = 0.0001;
+        return w;
+    }
+    case IROTAVG_BISQUARE: {
+        const double t = 4.685 * sigma;
+        double w = 1.0 - e2 / (t * t);
+        return w < 0.0001 ? 0.0001 : w;
+    }
+    case IROTAVG_CAUCHY: {
+        const double t = 2.385 * sigma;
+        return 1.0 / sqrt(1.0 + e2 / (t * t));
+    }
+    case IROTAVG_FAIR:
+        return 1.0 / sqrt(1.0 + sqrt(e2) / (1.400 * sigma));
+    case IROTAVG_LOGISTIC: {
+        const double e = sqrt(e2) / (1.205 * sigma);
+        return e < 0.0001 ? 1.0 : sqrt(tanh(e) / e);
+    }
+    case IROTAVG_TALWAR: {
+        const double t = 2.795 * sigma;
+        return e2 < t * t ? 1.0001 : 0.0;
+    }
+    default: {  // IROTAVG_WELSCH
+        const double t = 2.985 * sigma;
+        double w = exp(-.5 * e2 / (t * t));
+        return w < 0.0001 ? 0.0001 : w;
+    }
+    }
+}
+
+// exp_map of one step (ral/l1_irls.cpp:471-492): the quaternion of x, every non-finite entry -> 0 (:491); th = ||x||
+__device__ __forceinline__ double4 step_quat(double x0, double x1, double x2, double &th) {
+    th = sqrt(x0 * x0 + x1 * x1 + x2 * x2);
     double sn, cs;
     sincos(th / 2.0, &sn, &cs);
     const double coef = sn / th;
@@ -351,6 +429,15 @@ __device__ __forceinline__ double step_apply(double x0, double x1, double x2, do
     if (!isfinite(w.y)) w.y = 0.0;
     if (!isfinite(w.z)) w.z = 0.0;
     if (!isfinite(w.w)) w.w = 0.0;
+    return w;
+}
+
+// One view's share of K6 (ral/l1_irls.cpp:729-737): returns ||x|| (the view's term of the score, taken BEFORE the exp
+// map), Q[idx] <- Q[idx] (x) exp(x) (right-multiply, no renormalisation). A step that is not finite leaves its rotation
+// alone (the score turns non-finite instead).
+__device__ __forceinline__ double step_apply(double x0, double x1, double x2, double4 *__restrict__ Q, int idx, bool write) {
+    double th;
+    const double4 w = step_quat(x0, x1, x2, th);
     const double4 q = qmul(Q[idx], w);
     if (write && isfinite(th)) Q[idx] = q;
     return th;

@@ -42,16 +42,6 @@ static void pd_prepare(Graph &g) {
     g.pd_ready = true;
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-    return v;
-}
 // workgroup min/max -> part[0]
 template <bool MAX>
 __device__ __forceinline__ void block_ext_store(double v, double *part) {
@@ -350,8 +340,8 @@ __device__ __forceinline__ void pd_direction(double adx, double g1, double g2, d
     d2 -= itau * if2;
 }
 
-// :324-381 -- Adx, the operand of A' (Atdv), and the four guarded step bounds. (The make_A coefficients of an edge follow
-// from its endpoints and f -- the rule of the builds, build.cpp / gbuild.hip -- so the flag byte is not read.)
+// :324-381 -- Adx, the operand of A' (Atdv), and the four guarded step bounds. (The make_A coefficients of an edge are
+// edge_flags of its endpoints and f, which the thread holds anyway: the flag byte is not read.)
 __global__ __launch_bounds__(kRowBlock) void k_pd_dir(
     long long m, int f, const int *__restrict__ ei, const int *__restrict__ ej,
     const uint8_t *__restrict__ eflag, const double4 *__restrict__ DX,
@@ -368,8 +358,9 @@ __global__ __launch_bounds__(kRowBlock) void k_pd_dir(
         for (int h = 0; h < 2; h++) {
             const int i = h ? ii.y : ii.x, j = h ? jj.y : jj.x;
             double adx = 0.0;
-            if (j >= f && i != j) adx += DX[j - f].x;   // EF_CJ
-            if (j >= f && i >= f) adx -= DX[i - f].x;   // EF_CI
+            const uint8_t fl = edge_flags(i, j, f);
+            if (fl & EF_CJ) adx += DX[j - f].x;
+            if (fl & EF_CI) adx -= DX[i - f].x;
             const double g1 = h ? g1v.y : g1v.x, g2 = h ? g2v.y : g2v.x, m1 = h ? m1v.y : m1v.x, m2 = h ? m2v.y : m2v.x;
             double d_u, d1, d2;
             pd_direction(adx, g1, g2, m1, m2, itau, d_u, d1, d2);

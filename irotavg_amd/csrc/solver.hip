@@ -13,7 +13,7 @@
 
 namespace irh {
 
-// (IRH_PI, IRH_EPS and K1's edge_log: kernels.hpp)
+// (K1's edge_log, K2's robust_weight and K6's step_quat / step_apply: kernels.hpp, shared with window.hip)
 
 // =============================================================================================
 // K1 -- edge residual. Two edges per thread so every SoA stream moves as 16 B per lane.
@@ -53,81 +53,21 @@ void launch_edge_residual(Graph &g, bool weights_to_one) {
 // =============================================================================================
 // K2 -- residual of the linearised system and robust weight update (two edges per thread).
 // =============================================================================================
-__device__ __forceinline__ double robust_weight(int cost, double sigma, double e2, double prev) {
-    switch (cost) {
-    case IROTAVG_L2:
-        return prev;
-    case IROTAVG_L05: {
-        double w = 1.0 / pow(e2, 3. / 8.);
-        return w > 1e4 ? 1e4 : w;
-    }
-    case IROTAVG_L1: {
-        double w = 1.0 / sqrt(sqrt(e2));
-        return w > 1e4 ? 1e4 : w;
-    }
-    case IROTAVG_L15: {
-        double w = 1.0 / sqrt(sqrt(sqrt(e2)));
-        return w > 1e4 ? 1e4 : w;
-    }
-    case IROTAVG_GEMAN_MCCLURE:
-        return 1.0 / (e2 + sigma * sigma);
-    case IROTAVG_HUBER: {  // weights of inliers keep their previous value (:647-649)
-        const double e = sqrt(e2) / (1.345 * sigma);
-        return e >= 1 ? sqrt(1. / e) : prev;
-    }
-    case IROTAVG_PSEUDO_HUBER:
-        return 1.0 / sqrt(sqrt(1.0 + e2 / (sigma * sigma)));
-    case IROTAVG_ANDREWS: {
-        const double e = sqrt(e2) / (1.339 * sigma);
-        double w = sqrt(sin(e) / e);
-        if (e >= IRH_PI)
-            w = 0;
-        else if (e < .0001)
-            w = 1;
-        if (w < 0.0001) w = 0.0001;
-        return w;
-    }
-    case IROTAVG_BISQUARE: {
-        const double t = 4.685 * sigma;
-        double w = 1.0 - e2 / (t * t);
-        return w < 0.0001 ? 0.0001 : w;
-    }
-    case IROTAVG_CAUCHY: {
-        const double t = 2.385 * sigma;
-        return 1.0 / sqrt(1.0 + e2 / (t * t));
-    }
-    case IROTAVG_FAIR:
-        return 1.0 / sqrt(1.0 + sqrt(e2) / (1.400 * sigma));
-    case IROTAVG_LOGISTIC: {
-        const double e = sqrt(e2) / (1.205 * sigma);
-        return e < 0.0001 ? 1.0 : sqrt(tanh(e) / e);
-    }
-    case IROTAVG_TALWAR: {
-        const double t = 2.795 * sigma;
-        return e2 < t * t ? 1.0001 : 0.0;
-    }
-    default: {  // IROTAVG_WELSCH
-        const double t = 2.985 * sigma;
-        double w = exp(-.5 * e2 / (t * t));
-        return w < 0.0001 ? 0.0001 : w;
-    }
-    }
-}
-
 // Two edges per thread, as K1: index pairs, residual planes and weights move as 8 / 16 B per lane. What the kernel does
-// NOT read: the per-edge flag byte (EF_CJ / EF_CI follow from the endpoints and f -- the rule of the builds, build.cpp /
-// gbuild.hip: j free -> +X_j; i free as well -> -X_i; a self loop keeps the -1 only) and, unless the cost keeps previous
-// values (L2, Huber: PREV), the old weight. Algorithmic traffic: 8 B indices + 24 B residual + 8 B weight per edge.
+// NOT read: the per-edge flag byte (edge_flags, common.hpp, is evaluated on the endpoints and f the thread holds anyway)
+// and, unless the cost keeps previous values (L2, Huber: PREV), the old weight. Algorithmic traffic: 8 B indices + 24 B
+// residual + 8 B weight per edge.
 __device__ __forceinline__ double step_residual2(int i, int j, int f, double r0, double r1, double r2,
                                                  const double4 *__restrict__ X) {
     double e0 = 0.0, e1 = 0.0, e2c = 0.0;
-    if (j >= f && !(i == j)) {  // EF_CJ
+    const uint8_t fl = edge_flags(i, j, f);
+    if (fl & EF_CJ) {
         const double4 xj = X[j - f];
         e0 += xj.x;
         e1 += xj.y;
         e2c += xj.z;
     }
-    if (j >= f && i >= f) {  // EF_CI
+    if (fl & EF_CI) {
         const double4 xi = X[i - f];
         e0 -= xi.x;
         e1 -= xi.y;

@@ -128,18 +128,17 @@ __global__ __launch_bounds__(WC_THREADS) void k_window_cov(unsigned char *__rest
         sR[k] = make_double4(rx, ry, rz, 1.0 / (rx * rx + ry * ry + rz * rz + sg2));
     }
     __syncthreads();
-    // ---- M: row r belongs to thread r. Row k of A (make_A, ral/l1_irls.cpp:755-780): +1 at j - f unless j is fixed
-    // (then the row is zero), -1 at i - f when i is free too
+    // ---- M: row r belongs to thread r. Row k of A (make_A: edge_flags, common.hpp): +1 at a, -1 at b (-1: none)
     if (t < nu) {
         double *row = M + t * WC_LD;
         for (int k = 0; k < ne; k++) {
             const int2 e = sI[k];
-            if (e.y < f) continue;
-            const int a = e.y - f, b = (e.x >= f && e.x != e.y) ? e.x - f : -1;
+            const uint8_t fl = edge_flags(e.x, e.y, f);
+            const int a = (fl & EF_CJ) ? e.y - f : -1, b = (fl & EF_CI) ? e.x - f : -1;
             if (a != t && b != t) continue;
             const double d = sR[k].w, w = d * d;
             row[t] += w;
-            if (b >= 0) row[a == t ? b : a] -= w;
+            if (a >= 0 && b >= 0) row[a == t ? b : a] -= w;
         }
     }
     __syncthreads();
@@ -216,7 +215,8 @@ __global__ __launch_bounds__(WC_THREADS) void k_window_cov(unsigned char *__rest
     for (int k = t; k < (P.first ? ne : 0); k += WC_THREADS) {
         const int2 e = sI[k];
         const double4 rr = sR[k];
-        const int a = e.y >= f ? e.y - f : -1, b = (e.y >= f && e.x >= f && e.x != e.y) ? e.x - f : -1;
+        const uint8_t fl = edge_flags(e.x, e.y, f);
+        const int a = (fl & EF_CJ) ? e.y - f : -1, b = (fl & EF_CI) ? e.x - f : -1;
         const double v = wc_usu(M, a, b), w = rr.w * rr.w, l = w * v;
         if (!(fabs(v) < INFINITY)) sDead = 1;
         ev[k] = v;

@@ -5,9 +5,10 @@
 // multi-kernel path (one l1ra + irls there is ~150 launches and ~40 host round trips, ~6 ms),
 // so the complete pipeline -- l1ra (primal-dual LP per coordinate, ral/l1_irls.cpp:228-468,
 // 851-912) followed by irls (:559-752) -- runs inside a single workgroup with every vector and
-// the dense normal matrix in LDS: one H2D, one launch, one D2H. The arithmetic follows the same
-// reference statements as solver.hip / l1pd.hip; the linear solves are exact (dense Gauss-Jordan
-// in LDS, dead pivots -> 0 like the oracle).
+// the dense normal matrix in LDS: one H2D, one launch, one D2H. The per-edge math is the code the
+// multi-kernel path runs (kernels.hpp: edge_log, robust_weight, step_quat; common.hpp: edge_flags);
+// the primal-dual LP follows the same reference statements as l1pd.hip; the linear solves are exact
+// (dense Gauss-Jordan in LDS, dead pivots -> 0 like the oracle).
 #include "graph.hpp"
 #include "kernels.hpp"
 
@@ -29,9 +30,6 @@ struct WinResult {
     double l1_score, irls_score;
     long long stamp[8];  // development aid (IROTAVG_WINDOW_STAMPS=1 prints them): s_memtime at the phase boundaries of k_window_wave
 };
-
-#define W_PI 3.141592653589793238462643383279502884
-#define W_EPS 2.2204e-16
 
 struct WinShared {
     double4 *Q;       // nv
@@ -57,7 +55,7 @@ __device__ __forceinline__ double wg_sum(double v, double *red) {
     return s;
 }
 __device__ __forceinline__ double wg_min(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
+    v = wave_min(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     const double s = fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
@@ -65,7 +63,7 @@ __device__ __forceinline__ double wg_min(double v, double *red) {
     return s;
 }
 __device__ __forceinline__ double wg_max(double v, double *red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+    v = wave_max(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     const double s = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
@@ -120,21 +118,11 @@ __device__ bool dense_solve(double *H, int n, double *B, int nrhs, double *red) 
     return wg_sum(bad, red) == 0.0;
 }
 
-// ---- K1 on the window: r_k = log(Qinv_j (x) QQ_k (x) Q_i)  (ral/l1_irls.cpp:109-127,498-532) --
+// ---- K1 on the window: r_k = log(Qinv_j (x) QQ_k (x) Q_i) -------------------------------------
 __device__ void win_residual(const WinParams &P, const WinShared &S, const double4 *__restrict__ QQ) {
     for (int k = threadIdx.x; k < P.ne; k += blockDim.x) {
-        double4 qj = S.Q[S.I[k].y];
-        qj.w = -qj.w;
-        const double4 d = qmul(qj, qmul(QQ[k], S.Q[S.I[k].x]));
-        const double s2 = sqrt(d.x * d.x + d.y * d.y + d.z * d.z);
-        double th = 2.0 * atan2(s2, d.w);
-        if (th < -W_PI)
-            th += 2.0 * W_PI;
-        else if (th >= W_PI)
-            th -= 2.0 * W_PI;
-        const double aux = th / s2;
-        double ox = d.x * aux, oy = d.y * aux, oz = d.z * aux;
-        if (s2 < W_EPS) ox = oy = oz = 0.0;
+        double ox, oy, oz;
+        edge_log(S.Q[S.I[k].x], S.Q[S.I[k].y], QQ[k], ox, oy, oz);
         S.r[k] = ox;
         S.r[P.ne + k] = oy;
         S.r[2 * P.ne + k] = oz;
@@ -154,21 +142,14 @@ __device__ __forceinline__ double at_dot(const WinParams &P, const WinShared &S,
 }
 
 // score = mean ||W row|| (before the exp map), exp map, Q_{f+i} <- Q_{f+i} (x) W_i
-// (ral/l1_irls.cpp:729-737 / :894-902, :471-492)
+// (ral/l1_irls.cpp:729-737 / :894-902)
 __device__ double win_apply_step(const WinParams &P, const WinShared &S) {
     const int nu = P.nv - P.f;
     double acc = 0.0;
     for (int i = threadIdx.x; i < nu; i += blockDim.x) {
-        const double x = S.W[i], y = S.W[nu + i], z = S.W[2 * nu + i];
-        const double th = sqrt(x * x + y * y + z * z);
+        double th;
+        const double4 w = step_quat(S.W[i], S.W[nu + i], S.W[2 * nu + i], th);
         acc += th;
-        const double sn = sin(th / 2.0), cs = cos(th / 2.0);
-        const double coef = sn / th;
-        double4 w = make_double4(x * coef, y * coef, z * coef, cs);
-        if (!isfinite(w.x)) w.x = 0.0;
-        if (!isfinite(w.y)) w.y = 0.0;
-        if (!isfinite(w.z)) w.z = 0.0;
-        if (!isfinite(w.w)) w.w = 0.0;
         S.Q[i + P.f] = qmul(S.Q[i + P.f], w);
     }
     const double s = wg_sum(acc, S.red);
@@ -370,8 +351,6 @@ __device__ int win_l1decode(const WinParams &P, const WinShared &S, const double
     return 0;
 }
 
-__device__ __forceinline__ double win_weight(int cost, double sigma, double e2, double prev);
-
 __global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const int2 *__restrict__ Ig,
                                                               const double4 *__restrict__ QQ,
                                                               double4 *__restrict__ Qg,
@@ -397,16 +376,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const
     for (int k = tid; k < ne; k += nt) {
         const int2 e = Ig[k];
         S.I[k] = e;
-        unsigned char fl = 0;  // make_A coefficients (ral/l1_irls.cpp:764-777)
-        if (e.y >= f) {
-            if (e.x >= f && e.x == e.y) {
-                fl = EF_CI;
-            } else {
-                fl |= EF_CJ;
-                if (e.x >= f) fl |= EF_CI;
-            }
-        }
-        S.fl[k] = fl;
+        S.fl[k] = edge_flags(e.x, e.y, f);
     }
     __syncthreads();
     int status = 0;
@@ -493,7 +463,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const
             e0 -= S.r[k];
             e1 -= S.r[ne + k];
             e2c -= S.r[2 * ne + k];
-            S.d[k] = win_weight(P.cost, P.sigma, e0 * e0 + e1 * e1 + e2c * e2c, S.d[k]);
+            S.d[k] = robust_weight(P.cost, P.sigma, e0 * e0 + e1 * e1 + e2c * e2c, S.d[k]);
         }
         __syncthreads();
         score = win_apply_step(P, S);
@@ -509,31 +479,6 @@ __global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const
         out->status = status;
         out->l1_score = l1_score;
         out->irls_score = score;
-    }
-}
-
-// the 14 robust weights (ral/l1_irls.cpp:617-727); same statements as robust_weight() in solver.hip
-__device__ __forceinline__ double win_weight(int cost, double sigma, double e2, double prev) {
-    switch (cost) {
-    case IROTAVG_L2: return prev;
-    case IROTAVG_L05: { double w = 1.0 / pow(e2, 3. / 8.); return w > 1e4 ? 1e4 : w; }
-    case IROTAVG_L1: { double w = 1.0 / sqrt(sqrt(e2)); return w > 1e4 ? 1e4 : w; }
-    case IROTAVG_L15: { double w = 1.0 / sqrt(sqrt(sqrt(e2))); return w > 1e4 ? 1e4 : w; }
-    case IROTAVG_GEMAN_MCCLURE: return 1.0 / (e2 + sigma * sigma);
-    case IROTAVG_HUBER: { const double e = sqrt(e2) / (1.345 * sigma); return e >= 1 ? sqrt(1. / e) : prev; }
-    case IROTAVG_PSEUDO_HUBER: return 1.0 / sqrt(sqrt(1.0 + e2 / (sigma * sigma)));
-    case IROTAVG_ANDREWS: {
-        const double e = sqrt(e2) / (1.339 * sigma);
-        double w = sqrt(sin(e) / e);
-        if (e >= W_PI) w = 0; else if (e < .0001) w = 1;
-        return w < 0.0001 ? 0.0001 : w;
-    }
-    case IROTAVG_BISQUARE: { const double t = 4.685 * sigma; double w = 1.0 - e2 / (t * t); return w < 0.0001 ? 0.0001 : w; }
-    case IROTAVG_CAUCHY: { const double t = 2.385 * sigma; return 1.0 / sqrt(1.0 + e2 / (t * t)); }
-    case IROTAVG_FAIR: return 1.0 / sqrt(1.0 + sqrt(e2) / (1.400 * sigma));
-    case IROTAVG_LOGISTIC: { const double e = sqrt(e2) / (1.205 * sigma); return e < 0.0001 ? 1.0 : sqrt(tanh(e) / e); }
-    case IROTAVG_TALWAR: { const double t = 2.795 * sigma; return e2 < t * t ? 1.0001 : 0.0; }
-    default: { const double t = 2.985 * sigma; double w = exp(-.5 * e2 / (t * t)); return w < 0.0001 ? 0.0001 : w; }
     }
 }
 
@@ -554,11 +499,6 @@ constexpr int SM_THREADS = 192;
 constexpr unsigned ADJ_NEG = 1u << 16;   // the edge enters the view's row with coefficient -1
 constexpr unsigned ADJ_SELF = 1u << 17;  // make_AtA self-loop entry
 
-__device__ __forceinline__ double rl_d(double x, int k) {  // k wave-uniform
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), k);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), k);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ int rl_i(int x, int k) { return __builtin_amdgcn_readlane(x, k); }
 
 // wave64 reductions on the DPP network (no LDS traffic): four steps inside each row of 16 lanes,
@@ -589,7 +529,7 @@ __device__ __forceinline__ double wv_reduce(double v) {
     v = Op::f(v, dpp_d<0x128, 0xf>(Op::id(), v));  // row_ror 8
     v = Op::f(v, dpp_d<0x142, 0xa>(Op::id(), v));  // row_bcast 15 -> rows 1, 3
     v = Op::f(v, dpp_d<0x143, 0xc>(Op::id(), v));  // row_bcast 31 -> rows 2, 3
-    return rl_d(v, 63);
+    return readlane_d(v, 63);
 }
 __device__ __forceinline__ double wv_sum(double v) { return wv_reduce<OpSum>(v); }
 __device__ __forceinline__ double wv_min(double v) { return wv_reduce<OpMin>(v); }
@@ -646,7 +586,7 @@ __device__ __forceinline__ void sm_solve_t(double (&h)[SM_MAX_NU], double &b, do
     for (int k = 0; k < NUP; k++) {
         // the reciprocal -- the only chain from pivot to pivot -- by v_rcp_f64 + two Newton steps (a third of the IEEE
         // division's dependent instructions)
-        const double piv = rl_d(h[k], k);
+        const double piv = readlane_d(h[k], k);
         double ip = __builtin_amdgcn_rcp(piv);
         ip = fma(fma(-piv, ip, 1.0), ip, ip);
         ip = fma(fma(-piv, ip, 1.0), ip, ip);
@@ -655,8 +595,8 @@ __device__ __forceinline__ void sm_solve_t(double (&h)[SM_MAX_NU], double &b, do
         if (me) myip = ip;
         const double mult = me ? 0.0 : -(h[k] * ip);
 #pragma unroll
-        for (int c = k + 1; c < NUP; c++) h[c] = fma(mult, rl_d(h[c], k), h[c]);
-        b = fma(mult, rl_d(b, k), b);
+        for (int c = k + 1; c < NUP; c++) h[c] = fma(mult, readlane_d(h[c], k), h[c]);
+        b = fma(mult, readlane_d(b, k), b);
     }
 }
 __device__ __forceinline__ bool sm_solve(double (&h)[SM_MAX_NU], double &b, int nu, int lane) {
@@ -900,14 +840,9 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const 
         ey = e.y;
         ai = e.x - f;
         aj = e.y - f;
-        if (e.y >= f) {  // make_A coefficients (ral/l1_irls.cpp:764-777)
-            if (e.x >= f && e.x == e.y) {
-                E.ci = e.x - f;
-            } else {
-                E.cj = e.y - f;
-                if (e.x >= f) E.ci = e.x - f;
-            }
-        }
+        const uint8_t fl = edge_flags(e.x, e.y, f);
+        if (fl & EF_CJ) E.cj = e.y - f;
+        if (fl & EF_CI) E.ci = e.x - f;
     }
     const bool ek = lane < ne, vk = lane < nu;
     if (wave == 0) {
@@ -971,42 +906,15 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const 
     E.maxH = (int)wv_max((double)E.degH);
     E.Hrow = sH[wave][vk ? lane : 0];
     double r[3] = {0, 0, 0};
-    auto residual = [&]() {  // K1 on lane k (ral/l1_irls.cpp:109-127,498-532)
-        if (ek) {
-            double4 qj = sQ[ey];
-            qj.w = -qj.w;
-            const double4 d = qmul(qj, qmul(qq, sQ[ex]));
-            const double s2 = sqrt(d.x * d.x + d.y * d.y + d.z * d.z);
-            double th = 2.0 * atan2(s2, d.w);
-            if (th < -W_PI)
-                th += 2.0 * W_PI;
-            else if (th >= W_PI)
-                th -= 2.0 * W_PI;
-            const double aux = th / s2;
-            r[0] = d.x * aux;
-            r[1] = d.y * aux;
-            r[2] = d.z * aux;
-            if (s2 < W_EPS) r[0] = r[1] = r[2] = 0.0;
-        }
+    auto residual = [&]() {  // K1 on lane k
+        if (ek) edge_log(sQ[ex], sQ[ey], qq, r[0], r[1], r[2]);
     };
-    // score = mean ||W row|| before the exp map; wave 0 updates Q (:729-737 / :894-902, :471-492)
+    // score = mean ||W row|| before the exp map; wave 0 updates Q (:729-737 / :894-902)
     auto apply_step = [&]() -> double {
         double acc = 0.0;
         if (vk) {
-            const double x = sW[0][lane], y = sW[1][lane], z = sW[2][lane];
-            const double th = sqrt(x * x + y * y + z * z);
-            acc = th;
-            if (wave == 0) {
-                double sn, cs;
-                sincos(th / 2.0, &sn, &cs);  // (one argument reduction for both; k_apply_step of solver.hip does the same)
-                const double coef = sn / th;
-                double4 w = make_double4(x * coef, y * coef, z * coef, cs);
-                if (!isfinite(w.x)) w.x = 0.0;
-                if (!isfinite(w.y)) w.y = 0.0;
-                if (!isfinite(w.z)) w.z = 0.0;
-                if (!isfinite(w.w)) w.w = 0.0;
-                sQ[lane + f] = qmul(sQ[lane + f], w);
-            }
+            const double4 w = step_quat(sW[0][lane], sW[1][lane], sW[2][lane], acc);
+            if (wave == 0) sQ[lane + f] = qmul(sQ[lane + f], w);
         }
         const double s = wv_sum(acc) / (double)nu;
         __syncthreads();
@@ -1097,7 +1005,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const 
             e0 -= r[0];
             e1 -= r[1];
             e2c -= r[2];
-            d = win_weight(P.cost, P.sigma, e0 * e0 + e1 * e1 + e2c * e2c, d);
+            d = robust_weight(P.cost, P.sigma, e0 * e0 + e1 * e1 + e2c * e2c, d);
         }
         score = apply_step();
         iter++;

@@ -1,10 +1,11 @@
 """The window kernels (irotavg_amd/csrc/window.hip) at their size limits and in every branch of their per-edge math.
 
-The kernels carry their own copies of the log map (win_residual, and again inside k_window_wave), of the 14 robust
-weights (win_weight), of the exp map / step, of the primal-dual LP and of the dense solve; test_gpu_window.py compares
-whole pipelines on small random graphs, which reach neither the limits (64 free views, 320 views, 640 edges; 16 / 64
-for the wave kernel) nor the branches. The cases come from tests/window_cases.py; what they rely on is asserted from
-the reference alone in test_window_cases_cpu.py.
+The log map (edge_log), the 14 robust weights (robust_weight), the exp map of a step (step_quat) and the edge flags
+(edge_flags) are one function each (kernels.hpp, common.hpp), inlined into both window kernels and into the kernels of
+the handle: these tests guard the single copy through every path that inlines it. The primal-dual LP and the dense solve
+are the window kernels' own. test_gpu_window.py compares whole pipelines on small random graphs, which reach neither the
+limits (64 free views, 320 views, 640 edges; 16 / 64 for the wave kernel) nor the branches. The cases come from
+tests/window_cases.py; what they rely on is asserted from the reference alone in test_window_cases_cpu.py.
 
 kernel = 1 is the general LDS kernel, 2 the wave-resident kernel, 0 the automatic choice.
 """
@@ -69,9 +70,11 @@ def test_planted_branches(cost, kernel):
 
 @pytest.mark.parametrize("cost", range(14))
 def test_planted_kernels_agree(cost):
-    """Both kernels evaluate the same expressions on the same residual: they differ at most in libm inlining."""
+    """Both kernels inline the same edge_log and robust_weight: the same expressions on the same residual."""
     c = WC.planted(cost)
     g, w = one_pass(c, cost, 1), one_pass(c, cost, 2)
+    print("planted cost %d, kernel 1 vs kernel 2: max diff of the planted weights %.3e"
+          % (cost, np.abs(w["weights"][c["planted"]] - g["weights"][c["planted"]]).max()))
     np.testing.assert_allclose(w["weights"][c["planted"]], g["weights"][c["planted"]], rtol=1e-13, atol=0)
 
 
@@ -89,6 +92,17 @@ def test_star_log_and_exp_map(kernel):
         assert r["Q"][v].tobytes() == s["Q0"][v].tobytes(), v
     assert r["Q"][:s["f"]].tobytes() == s["Q0"][:s["f"]].tobytes()
     np.testing.assert_allclose(r["weights"], b["weights"], rtol=1e-7)
+
+
+def test_star_kernels_agree():
+    """At unit weights the star's normal matrix is the identity: both kernels apply the same residual (edge_log) through
+    the same exp map (step_quat), so the rotations of the planted rows are compared componentwise between them."""
+    s = WC.star()
+    g, w = one_pass(s, 4, 1), one_pass(s, 4, 2)
+    rows = list(s["rows"].values())
+    print("star, kernel 1 vs kernel 2: max componentwise diff %.3e" % np.abs(g["Q"][rows] - w["Q"][rows]).max())
+    for name, v in s["rows"].items():
+        np.testing.assert_allclose(w["Q"][v], g["Q"][v], rtol=1e-13, atol=0, err_msg=name)
 
 
 def pipeline_vs_oracle(c, kernel, cost=4, l1=100, irls=100, ang_tol=1e-9, w_tol=dict(rtol=1e-7)):
@@ -157,8 +171,8 @@ def test_largest_accepted_next_to_the_refused():
 
 @pytest.mark.parametrize("cost", range(14))
 def test_planted_table_through_the_handle(cost):
-    """The same planted table through robust_weight (solver.hip): the stage entry points, then the fused weight pass
-    of irls. Holds robust_weight and win_weight to one table."""
+    """The same planted table through the handle's kernels: the stage entry points, then the fused weight pass of
+    irls. One robust_weight (kernels.hpp), reached through three kernels, held to one table."""
     c = WC.planted(cost)
     with capi.Graph(c["I"], c["QQ"], c["nv"], c["f"]) as G:
         G.set_rotations(c["Q0"])
