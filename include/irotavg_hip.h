@@ -361,6 +361,31 @@ int irotavg_graph_rotation_variance_dev(irotavg_graph *g, double *var_dev, doubl
 int irotavg_graph_edge_diagnostics_dev(irotavg_graph *g, double *edge_var_dev, double *leverage_dev, double *chi2_dev,
                                        double *scale, void *stream);
 
+/* Many small problems in one call, on arrays that live on the device (docs/window_batch.md): nb independent problems,
+ * each l1ra(l1_iters) then irls(cost, sigma, irls_iters) as irotavg_window_solve runs them, one workgroup per problem.
+ * Problem b has sizes[3b .. 3b+2] = (n_total, f, m) and must fit the window kernels (<= 64 free views, <= 320 views,
+ * <= 640 edges). The problems are packed: problem b's edges are the rows sum_{a<b} m_a .. of I_dev / QQ_dev /
+ * weights_dev, its views the rows sum_{a<b} n_total_a .. of Q_dev; the ids of I_dev are LOCAL to their problem
+ * (0 .. n_total_b - 1). DATA pointers are DEVICE pointers on the calling thread's current device and follow the rules
+ * above (strided matrices, 8-byte alignment, lowest / highest element); `sizes` and `results` are HOST pointers.
+ *   kernel      0: per problem what irotavg_window_solve chooses, 1: the general LDS kernel for all, 2: the wave-resident
+ *               kernel for all (a problem it does not take: IROTAVG_ERR_BAD_ARG)
+ *   Q_dev       in and out; the rows of fixed views (< f of their problem) are never written
+ *   weights_dev sum(m) contiguous doubles, or NULL
+ *   results     4 per problem: status, l1ra iterations, irls iterations, kernel used (1 / 2); or NULL
+ * IROTAVG_ERR_BAD_ARG before any device work: nb <= 0 or above 262144, NULL sizes, a problem with f outside
+ * [0, n_total) or beyond the limits, kernel outside 0..2, a pointer / stride / alignment the rules refuse; a cost outside
+ * the enum is IROTAVG_ERR_UNKNOWN_COST; no HIP device: IROTAVG_ERR_NO_DEVICE. The edge ids are read on the device alone:
+ * the workgroup of a problem with an id outside [0, n_total) reports IROTAVG_ERR_BAD_ARG with zero iterations in
+ * `results` and leaves that problem's rows of Q_dev and weights_dev as they are; the other problems are solved.
+ * At most two launches go on `stream` itself; inputs may still be in flight there, Q_dev and weights_dev are ready for
+ * whatever is enqueued on it next. The call blocks until every result record has arrived and returns the first
+ * non-zero status in problem order. Results are bitwise those of irotavg_window_solve_kernel on each problem alone. */
+int irotavg_window_solve_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                   int64_t qq_rs, int64_t qq_cs, double *Q_dev, int64_t q_rs, int64_t q_cs, int cost,
+                                   double sigma, int l1_iters, int irls_iters, double change_th, double *weights_dev,
+                                   int32_t *results, int kernel, void *stream);
+
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash
  * each, followed by the scalars that choose kernels (level shapes, far-entry count, fused-assembly / two-launch

@@ -47,7 +47,7 @@ SYMBOLS = [
     "irotavg_viewgraph_edge_diagnostics", "irotavg_viewgraph_gate_connections",
     "irotavg_graph_create_dev", "irotavg_graph_set_rotations_dev", "irotavg_graph_get_rotations_dev",
     "irotavg_graph_set_weights_dev", "irotavg_graph_get_weights_dev", "irotavg_graph_get_residuals_dev",
-    "irotavg_graph_rotation_variance_dev", "irotavg_graph_edge_diagnostics_dev",
+    "irotavg_graph_rotation_variance_dev", "irotavg_graph_edge_diagnostics_dev", "irotavg_window_solve_batch_dev",
 ]
 
 
@@ -166,6 +166,9 @@ def lib():
     L.irotavg_graph_get_residuals_dev.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
     L.irotavg_graph_rotation_variance_dev.argtypes = [vp, vp, _dp, vp]
     L.irotavg_graph_edge_diagnostics_dev.argtypes = [vp, vp, vp, vp, _dp, vp]
+    L.irotavg_window_solve_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp, C.c_int64,
+                                                 C.c_int64, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, vp,
+                                                 C.POINTER(C.c_int32), C.c_int, vp]
     L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
     L.irotavg_viewgraph_num_connections.restype = C.c_int64

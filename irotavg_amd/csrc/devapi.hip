@@ -21,6 +21,7 @@
 #include "graph.hpp"
 #include "kernels.hpp"
 #include "marginals.hpp"
+#include "winbatch.hpp"  // strides_ok, matrix_span, the plan of irotavg_window_solve_batch_dev
 
 namespace irh {
 namespace {
@@ -138,14 +139,7 @@ __global__ __launch_bounds__(kT) void k_residuals_out(long long m, long long mpa
 }
 
 // ---- argument checks (before any device work) ----------------------------------------------------------------------------
-// A strided rows x cols matrix does not alias itself when its rows do not overlap (|rs| >= cols |cs|) or its columns
-// do not (|cs| >= rows |rs|), both strides non-zero: the rule include/irotavg_hip.h states.
-bool strides_ok(int64_t rows, int cols, int64_t rs, int64_t cs) {
-    const int64_t a = std::llabs(rs), b = std::llabs(cs), lim = (int64_t)1 << 31;
-    if (a == 0 || b == 0 || a > lim || b > lim || rows <= 0) return false;
-    return a >= (int64_t)cols * b || b >= rows * a;
-}
-
+// (the stride rule itself -- strides_ok -- and the span of a strided matrix are host arithmetic: winbatch.hpp)
 bool dev_ptr_ok(const void *p, int device) {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
@@ -157,8 +151,8 @@ bool dev_ptr_ok(const void *p, int device) {
 // the lowest and the highest element of the matrix (negative strides reach below ptr)
 bool dev_matrix_ok(const double *p, int64_t rows, int cols, int64_t rs, int64_t cs, int device) {
     if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return false;
-    const int64_t r = (rows - 1) * rs, c = (int64_t)(cols - 1) * cs;
-    const int64_t lo = std::min<int64_t>(0, r) + std::min<int64_t>(0, c), hi = std::max<int64_t>(0, r) + std::max<int64_t>(0, c);
+    int64_t lo, hi;
+    matrix_span(rows, cols, rs, cs, lo, hi);
     return dev_ptr_ok(p + lo, device) && dev_ptr_ok(p + hi, device);
 }
 bool dev_vector_ok(const double *p, int64_t n, int device) { return dev_matrix_ok(p, n, 1, 1, 1, device); }
@@ -351,6 +345,36 @@ int irotavg_graph_edge_diagnostics_dev(irotavg_graph *h, double *edge_var_dev, d
         const int rc = edge_diagnostics(g, edge_var_dev, leverage_dev, chi2_dev, scale, true);
         o.done();
         return rc;
+    });
+}
+
+// Many small problems on packed device arrays, one workgroup each (docs/window_batch.md). Handle-free: the device is
+// the calling thread's current one. The launches go on the caller's stream itself, so there is no event to wait for.
+int irotavg_window_solve_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                                   int64_t qq_cs, double *Q_dev, int64_t q_rs, int64_t q_cs, int cost, double sigma,
+                                   int l1_iters, int irls_iters, double change_th, double *weights_dev, int32_t *results,
+                                   int kernel, void *stream) {
+    if (!I_dev || !QQ_dev || !Q_dev) return IROTAVG_ERR_BAD_ARG;
+    if (cost < IROTAVG_L2 || cost > IROTAVG_WELSCH) return IROTAVG_ERR_UNKNOWN_COST;
+    return guarded([&]() -> int {
+        WinBatchPlan plan;
+        if (!winbatch_plan(nb, sizes, kernel, plan)) return IROTAVG_ERR_BAD_ARG;
+        if ((reinterpret_cast<uintptr_t>(I_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(QQ_dev) & 7) != 0 ||
+            (reinterpret_cast<uintptr_t>(Q_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(weights_dev) & 7) != 0 ||
+            !strides_ok(plan.sum_m, 4, qq_rs, qq_cs) || !strides_ok(plan.sum_n, 4, q_rs, q_cs))
+            return IROTAVG_ERR_BAD_ARG;
+        if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!dev_ptr_ok(I_dev, device) || !dev_ptr_ok(I_dev + 2 * plan.sum_m - 1, device) ||
+            !dev_matrix_ok(QQ_dev, plan.sum_m, 4, qq_rs, qq_cs, device) ||
+            !dev_matrix_ok(Q_dev, plan.sum_n, 4, q_rs, q_cs, device) ||
+            (weights_dev && !dev_vector_ok(weights_dev, plan.sum_m, device)))
+            return IROTAVG_ERR_BAD_ARG;
+        const WinBatchArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
+                               weights_dev};
+        return window_solve_batch_dev(plan, device, A, cost, sigma, l1_iters, irls_iters, change_th, results,
+                                      static_cast<hipStream_t>(stream));
     });
 }
 

@@ -305,6 +305,19 @@ struct WinBatchItem {  // one problem of a batched launch: inputs as window_solv
 };
 int window_solve_batch(WindowSolver &ws, int nb, WinBatchItem *items, int l1_max, int irls_max, int cost, double sigma,
                        double change_th);
+// the batched form on the caller's DEVICE arrays (irotavg_window_solve_batch_dev; plan: winbatch.hpp): problems packed one
+// after the other, I = sum(m) pairs of ids local to their problem, QQ / Q strided matrices, weights sum(m) doubles or nullptr
+struct WinBatchPlan;
+struct WinBatchArrays {
+    const int32_t *I;
+    const double *QQ;
+    long long qq_rs, qq_cs;
+    double *Q;
+    long long q_rs, q_cs;
+    double *weights;
+};
+int window_solve_batch_dev(const WinBatchPlan &plan, int device, const WinBatchArrays &A, int cost, double sigma,
+                           int l1_max, int irls_max, double change_th, int32_t *results, hipStream_t stream);
 // wincov.hip: the uncertainty queries of a window-size problem in one kernel launch (docs/viewgraph_uncertainty.md)
 struct WinCov;
 WinCov *wincov_new();

@@ -1,0 +1,101 @@
+// winbatch.hpp -- the host arithmetic of the window kernels and of irotavg_window_solve_batch_dev: size limits, the
+// stride rule of the `_dev` API, and the plan of a batch (offsets and descriptors from `sizes`). Plain C++ with no HIP
+// type in it, so that a stand-alone program can run all of it under a sanitizer on a machine without a device
+// (tools/winbatch_host_check.cpp).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace irh {
+
+constexpr int WIN_MAX_NU = 64;    // free views
+constexpr int WIN_MAX_NV = 320;   // all views of the sub-problem
+constexpr int WIN_MAX_NE = 640;   // edges
+constexpr int SM_MAX_NE = 64;     // the wave-resident kernel
+constexpr int SM_MAX_NU = 16;
+constexpr size_t WIN_MAX_LDS = 160 * 1024;
+constexpr int64_t WIN_BATCH_MAX = 262144;  // problems of one irotavg_window_solve_batch_dev call
+
+// dynamic LDS of the general kernel (32 = sizeof(double4), 8 = sizeof(int2): window.hip asserts both)
+constexpr size_t win_lds_bytes(int nv, int ne, int nu) {
+    return 32 * (size_t)nv +
+           sizeof(double) * ((size_t)4 * ne + ne + 3 * nu + (size_t)nu * (nu + 1) + 3 * nu + 12 * (size_t)ne +
+                             5 * nu + 16) +
+           8 * (size_t)ne + (size_t)ne + 64;
+}
+// the batched general kernel also keeps the problem's measurements in LDS, one double4 per edge (see WinIoUser)
+constexpr size_t win_lds_bytes_user(int nv, int ne, int nu) { return win_lds_bytes(nv, ne, nu) + 32 * (size_t)ne; }
+static_assert(win_lds_bytes_user(WIN_MAX_NV, WIN_MAX_NE, WIN_MAX_NU) <= WIN_MAX_LDS,
+              "every term grows with its size: a problem inside the limits fits");
+inline bool win_fits_wave(int nv, int f, int ne) {
+    const int64_t nu = (int64_t)nv - f;
+    return nu >= 1 && nu <= SM_MAX_NU && nv <= WIN_MAX_NV && ne >= 1 && ne <= SM_MAX_NE;
+}
+inline bool win_fits(int nv, int f, int ne) {
+    const int64_t nu = (int64_t)nv - f;
+    return nu >= 1 && nu <= WIN_MAX_NU && nv <= WIN_MAX_NV && ne >= 1 && ne <= WIN_MAX_NE &&
+           win_lds_bytes(nv, ne, (int)nu) <= WIN_MAX_LDS;
+}
+
+// A strided rows x cols matrix does not alias itself when its rows do not overlap (|rs| >= cols |cs|) or its columns
+// do not (|cs| >= rows |rs|), both strides non-zero and at most 2^31: the rule include/irotavg_hip.h states.
+inline bool strides_ok(int64_t rows, int cols, int64_t rs, int64_t cs) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (rs == 0 || cs == 0 || rs > lim || rs < -lim || cs > lim || cs < -lim || rows <= 0 || rows > lim) return false;
+    const int64_t a = rs < 0 ? -rs : rs, b = cs < 0 ? -cs : cs;
+    return a >= (int64_t)cols * b || b >= rows * a;
+}
+// element offsets of the lowest and the highest element of such a matrix (negative strides reach below the pointer)
+inline void matrix_span(int64_t rows, int cols, int64_t rs, int64_t cs, int64_t &lo, int64_t &hi) {
+    const int64_t r = (rows - 1) * rs, c = (int64_t)(cols - 1) * cs;
+    lo = (r < 0 ? r : 0) + (c < 0 ? c : 0);
+    hi = (r > 0 ? r : 0) + (c > 0 ? c : 0);
+}
+
+// one problem of a batch as its workgroup reads it: sizes, first row of its edges / views in the packed arrays, and its
+// place in the caller's order (the row of `results`)
+struct WinDesc {
+    int nv, f, ne, idx;
+    long long eoff, voff;
+};
+struct WinBatchPlan {
+    std::vector<WinDesc> desc;  // the wave kernel's list, then the general kernel's, each in the caller's order
+    int64_t nwave = 0;          // length of the first list
+    int64_t sum_m = 0, sum_n = 0;
+    size_t lds = 0;             // largest win_lds_bytes_user of the general list
+};
+// sizes = (n_total, f, m) per problem. kernel: 0 per problem as window_solve chooses, 1 / 2 one kernel for all.
+// false: a bad count, a problem the kernels (or the forced kernel) do not take, or a kernel outside 0..2.
+inline bool winbatch_plan(int64_t nb, const int32_t *sizes, int kernel, WinBatchPlan &out) {
+    if (nb <= 0 || nb > WIN_BATCH_MAX || !sizes || kernel < 0 || kernel > 2) return false;
+    int64_t nwave = 0;
+    for (int64_t b = 0; b < nb; b++) {
+        const int nv = sizes[3 * b], f = sizes[3 * b + 1], ne = sizes[3 * b + 2];
+        if (nv <= 0 || f < 0 || f >= nv || !win_fits(nv, f, ne)) return false;
+        const bool fw = win_fits_wave(nv, f, ne);
+        if (kernel == 2 && !fw) return false;
+        if (kernel == 2 || (kernel == 0 && fw)) nwave++;
+    }
+    out.desc.assign((size_t)nb, WinDesc{});
+    out.nwave = nwave;
+    out.lds = 0;
+    int64_t iw = 0, ig = nwave, eoff = 0, voff = 0;
+    for (int64_t b = 0; b < nb; b++) {
+        const int nv = sizes[3 * b], f = sizes[3 * b + 1], ne = sizes[3 * b + 2];
+        const bool wave = kernel == 2 || (kernel == 0 && win_fits_wave(nv, f, ne));
+        WinDesc &d = out.desc[(size_t)(wave ? iw++ : ig++)];
+        d = WinDesc{nv, f, ne, (int)b, (long long)eoff, (long long)voff};
+        if (!wave) {
+            const size_t l = win_lds_bytes_user(nv, ne, nv - f);
+            if (l > out.lds) out.lds = l;
+        }
+        eoff += ne;
+        voff += nv;
+    }
+    out.sum_m = eoff;
+    out.sum_n = voff;
+    return true;
+}
+
+}  // namespace irh

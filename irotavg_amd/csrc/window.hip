@@ -9,15 +9,16 @@
 // multi-kernel path runs (kernels.hpp: edge_log, robust_weight, step_quat; common.hpp: edge_flags);
 // the primal-dual LP follows the same reference statements as l1pd.hip; the linear solves are exact
 // (dense Gauss-Jordan in LDS, dead pivots -> 0 like the oracle).
+#include <mutex>
+
 #include "graph.hpp"
 #include "kernels.hpp"
+#include "winbatch.hpp"  // the size limits (WIN_MAX_*, SM_MAX_*), win_lds_bytes, the plan of a batch
 
 namespace irh {
 
-constexpr int WIN_MAX_NU = 64;    // free views
-constexpr int WIN_MAX_NV = 320;   // all views of the sub-problem
-constexpr int WIN_MAX_NE = 640;   // edges
 constexpr int WIN_THREADS = 256;
+static_assert(sizeof(double4) == 32 && sizeof(int2) == 8, "win_lds_bytes (winbatch.hpp) counts with these");
 
 struct WinParams {
     int nv, f, ne;
@@ -44,6 +45,94 @@ struct WinShared {
     int2 *I;          // ne
     unsigned char *fl;  // ne
 };
+
+// ---- where a problem's arrays live --------------------------------------------------------------
+// The two kernel bodies below are written once; what differs between the single-problem entry points and the batched
+// form on caller arrays (irotavg_window_solve_batch_dev) is how a row is fetched and stored, and whether the edge
+// endpoints have been checked by the host (kGuard = false) or must be checked by the workgroup (kGuard = true).
+struct WinIoOwn {  // the library's own staging block: one double4 per row, every row stored
+    static constexpr bool kGuard = false;  // capi checked the endpoints
+    static constexpr bool kSeq = false;    // the general kernel's result goes home by a copy command, no sequence number
+    static constexpr bool kStage = false;  // the general kernel reads the measurements where they are
+    const int2 *I;
+    const double4 *QQ;
+    double4 *Q;
+    double *w;
+    __device__ __forceinline__ int2 edge(int k) const { return I[k]; }
+    __device__ __forceinline__ double4 qq(int k) const { return QQ[k]; }
+    __device__ __forceinline__ const double4 *measurements(double4 *, int) const { return QQ; }
+    __device__ __forceinline__ double4 q(int i) const { return Q[i]; }
+    __device__ __forceinline__ int store_from(int) const { return 0; }
+    __device__ __forceinline__ void put_q(int i, const double4 &v) const { Q[i] = v; }
+    __device__ __forceinline__ void put_w(int k, double v) const { w[k] = v; }
+};
+// 8-byte accesses through (rs, cs); 16-byte ones only for contiguous rows behind a 16-byte aligned pointer (aos). Never
+// a double4 access: packed offsets and tensor views give no 32-byte alignment.
+__device__ __forceinline__ double4 ld_row(const double *p, long long rs, long long cs, long long row, bool aos) {
+    if (aos) {
+        const double2 *h = reinterpret_cast<const double2 *>(p + 4 * row);
+        const double2 a = h[0], b = h[1];
+        return make_double4(a.x, a.y, b.x, b.y);
+    }
+    const double *r = p + row * rs;
+    return make_double4(r[0], r[cs], r[2 * cs], r[3 * cs]);
+}
+__device__ __forceinline__ void st_row(double *p, long long rs, long long cs, long long row, bool aos, const double4 &v) {
+    if (aos) {
+        double2 *h = reinterpret_cast<double2 *>(p + 4 * row);
+        h[0] = make_double2(v.x, v.y);
+        h[1] = make_double2(v.z, v.w);
+        return;
+    }
+    double *r = p + row * rs;
+    r[0] = v.x;
+    r[cs] = v.y;
+    r[2 * cs] = v.z;
+    r[3 * cs] = v.w;
+}
+struct WinUser {  // the caller's packed arrays of a batch (kernel argument)
+    const int2 *I;
+    const double *QQ;
+    long long qq_rs, qq_cs;
+    double *Q;
+    long long q_rs, q_cs;
+    double *w;  // or nullptr
+    int qq_aos, q_aos;
+};
+struct WinIoUser {  // one problem of them: rows eoff.. of I / QQ / w, rows voff.. of Q; fixed rows of Q are not stored
+    static constexpr bool kGuard = true;
+    static constexpr bool kSeq = true;
+    static constexpr bool kStage = true;  // the general kernel keeps the measurements in LDS (measurements() below)
+    WinUser U;
+    long long eoff, voff;
+    __device__ __forceinline__ int2 edge(int k) const { return U.I[eoff + k]; }
+    __device__ __forceinline__ double4 qq(int k) const { return ld_row(U.QQ, U.qq_rs, U.qq_cs, eoff + k, U.qq_aos != 0); }
+    __device__ __forceinline__ double4 q(int i) const { return ld_row(U.Q, U.q_rs, U.q_cs, voff + i, U.q_aos != 0); }
+    // The general kernel reads every measurement once per outer iteration. The compiler contracts edge_log's quaternion
+    // products into fma chains, and which product of a sum stays a plain multiplication depends on the form the
+    // measurement arrives in: after four 8-byte loads it chose another one than after the double4 load of the staging
+    // block, and the batched results differed from the single-problem ones in the last bits. So the rows are brought
+    // into LDS once (ne double4 behind the poses: win_lds_bytes_user) and the iterations load them as double4, as
+    // k_window_solve does: the same expression, the same rounding. (Visible to the workgroup after its next barrier.)
+    __device__ __forceinline__ const double4 *measurements(double4 *lds, int ne) const {
+        for (int k = threadIdx.x; k < ne; k += blockDim.x) lds[k] = qq(k);
+        return lds;
+    }
+    __device__ __forceinline__ int store_from(int f) const { return f; }
+    __device__ __forceinline__ void put_q(int i, const double4 &v) const { st_row(U.Q, U.q_rs, U.q_cs, voff + i, U.q_aos != 0, v); }
+    __device__ __forceinline__ void put_w(int k, double v) const {
+        if (U.w) U.w[eoff + k] = v;
+    }
+};
+// what a workgroup of the batched form leaves when an endpoint of its problem is outside [0, nv): nothing else is written
+__device__ __forceinline__ void win_refuse(WinResult *out, int seq) {
+    out->l1_iters = 0;
+    out->irls_iters = 0;
+    out->status = IROTAVG_ERR_BAD_ARG;
+    out->l1_score = 0.0;
+    out->irls_score = 0.0;
+    __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // ---- workgroup reductions (result to every thread) -------------------------------------------
 __device__ __forceinline__ double wg_sum(double v, double *red) {
@@ -119,7 +208,7 @@ __device__ bool dense_solve(double *H, int n, double *B, int nrhs, double *red) 
 }
 
 // ---- K1 on the window: r_k = log(Qinv_j (x) QQ_k (x) Q_i) -------------------------------------
-__device__ void win_residual(const WinParams &P, const WinShared &S, const double4 *__restrict__ QQ) {
+__device__ __forceinline__ void win_residual(const WinParams &P, const WinShared &S, const double4 *QQ) {
     for (int k = threadIdx.x; k < P.ne; k += blockDim.x) {
         double ox, oy, oz;
         edge_log(S.Q[S.I[k].x], S.Q[S.I[k].y], QQ[k], ox, oy, oz);
@@ -351,16 +440,15 @@ __device__ int win_l1decode(const WinParams &P, const WinShared &S, const double
     return 0;
 }
 
-__global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const int2 *__restrict__ Ig,
-                                                              const double4 *__restrict__ QQ,
-                                                              double4 *__restrict__ Qg,
-                                                              double *__restrict__ weights,
-                                                              WinResult *__restrict__ out) {
+// The general kernel's body: one workgroup, one problem (every entry kernel below runs exactly this).
+template <class IO>
+__device__ __forceinline__ void win_solve_body(const WinParams &P, const IO &io, WinResult *__restrict__ out) {
     extern __shared__ double4 smem4[];
     const int nv = P.nv, ne = P.ne, f = P.f, nu = nv - f;
     WinShared S;
     S.Q = smem4;
-    double *p = reinterpret_cast<double *>(S.Q + nv);
+    double4 *const stage = S.Q + nv;  // ne rows where IO::kStage
+    double *p = reinterpret_cast<double *>(stage + (IO::kStage ? ne : 0));
     S.r = p;          p += 4 * ne;
     S.d = p;          p += ne;
     S.W = p;          p += 3 * nu;
@@ -372,11 +460,27 @@ __global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const
     S.I = reinterpret_cast<int2 *>(p);
     S.fl = reinterpret_cast<unsigned char *>(S.I + ne);
     const int tid = threadIdx.x, nt = blockDim.x;
-    for (int i = tid; i < nv; i += nt) S.Q[i] = Qg[i];
+    if (IO::kGuard && tid == 0) *reinterpret_cast<int *>(S.red) = 0;
+    if (IO::kGuard) __syncthreads();
+    for (int i = tid; i < nv; i += nt) S.Q[i] = io.q(i);
+    const double4 *QQ = io.measurements(stage, ne);
+    bool outside = false;
     for (int k = tid; k < ne; k += nt) {
-        const int2 e = Ig[k];
+        const int2 e = io.edge(k);
         S.I[k] = e;
         S.fl[k] = edge_flags(e.x, e.y, f);
+        outside = outside || (unsigned)e.x >= (unsigned)nv || (unsigned)e.y >= (unsigned)nv;
+    }
+    if (IO::kGuard) {
+        // The endpoints come from the device here and no host has seen them: a workgroup-wide OR before anything is
+        // indexed with one (so far LDS and the arrays were indexed with i < nv and k < ne alone).
+        if (outside) *reinterpret_cast<volatile int *>(S.red) = 1;
+        __syncthreads();
+        const bool refuse = *reinterpret_cast<volatile int *>(S.red) != 0;
+        if (refuse) {
+            if (tid == 0) win_refuse(out, P.seq);
+            return;
+        }
     }
     __syncthreads();
     int status = 0;
@@ -471,15 +575,40 @@ __global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const
     }
     if (status == 1) status = IROTAVG_ERR_SOLVER;
     __syncthreads();
-    for (int i = tid; i < nv; i += nt) Qg[i] = S.Q[i];
-    for (int k = tid; k < ne; k += nt) weights[k] = S.d[k];
+    for (int i = io.store_from(f) + tid; i < nv; i += nt) io.put_q(i, S.Q[i]);
+    for (int k = tid; k < ne; k += nt) io.put_w(k, S.d[k]);
+    if (IO::kSeq) {  // the record is polled by the host: the sequence number goes out last (see k_window_wave)
+        __threadfence_system();
+        __syncthreads();
+    }
     if (tid == 0) {
         out->l1_iters = l1_iters;
         out->irls_iters = iter;
         out->status = status;
         out->l1_score = l1_score;
         out->irls_score = score;
+        if (IO::kSeq) __hip_atomic_store(&out->seq, P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+__global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const int2 *__restrict__ Ig,
+                                                              const double4 *__restrict__ QQ,
+                                                              double4 *__restrict__ Qg,
+                                                              double *__restrict__ weights,
+                                                              WinResult *__restrict__ out) {
+    win_solve_body(P, WinIoOwn{Ig, QQ, Qg, weights}, out);
+}
+
+// Workgroup b solves the problem of descriptor b on the caller's packed arrays (irotavg_window_solve_batch_dev): sizes
+// and offsets from D[b], iteration limits and cost from Pk, the result to R[D[b].idx].
+__global__ __launch_bounds__(WIN_THREADS) void k_window_solve_user(WinParams Pk, const WinDesc *__restrict__ D, WinUser U,
+                                                                   WinResult *__restrict__ R) {
+    const WinDesc d = D[blockIdx.x];
+    WinParams P = Pk;
+    P.nv = d.nv;
+    P.f = d.f;
+    P.ne = d.ne;
+    win_solve_body(P, WinIoUser{U, d.eoff, d.voff}, R + d.idx);
 }
 
 // =================================================================================================
@@ -493,8 +622,6 @@ __global__ __launch_bounds__(WIN_THREADS) void k_window_solve(WinParams P, const
 // Statement order inside the sums follows the general kernel (k ascending), so both give the same
 // normal matrices bit for bit; only the order of the wave reductions differs.
 // =================================================================================================
-constexpr int SM_MAX_NE = 64;
-constexpr int SM_MAX_NU = 16;
 constexpr int SM_THREADS = 192;
 constexpr unsigned ADJ_NEG = 1u << 16;   // the edge enters the view's row with coefficient -1
 constexpr unsigned ADJ_SELF = 1u << 17;  // make_AtA self-loop entry
@@ -795,25 +922,9 @@ __device__ int sm_l1decode(const SmLane &E, const double y, const int pdmaxiter,
     return 0;
 }
 
-// BATCH: workgroup b solves the b-th of several INDEPENDENT windows (one per view-graph of a multi-session
-// server: irotavg_viewgraph_rot_avg_batch) -- its parameters come from Pb[b] and its arrays lie b * stride bytes
-// behind the first problem's. A single window is the kernel-argument form (no extra round trip for P).
-template <bool BATCH>
-__global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const WinParams *__restrict__ Pb,
-                                                           size_t stride, const int2 *__restrict__ Ig,
-                                                           const double4 *__restrict__ QQ,
-                                                           double4 *__restrict__ Qg,
-                                                           double *__restrict__ weights,
-                                                           WinResult *__restrict__ out) {
-    const WinParams P = BATCH ? *reinterpret_cast<const WinParams *>(reinterpret_cast<const unsigned char *>(Pb) + stride * blockIdx.x) : Pk;
-    if (BATCH) {
-        const size_t off = stride * blockIdx.x;
-        Ig = reinterpret_cast<const int2 *>(reinterpret_cast<const unsigned char *>(Ig) + off);
-        QQ = reinterpret_cast<const double4 *>(reinterpret_cast<const unsigned char *>(QQ) + off);
-        Qg = reinterpret_cast<double4 *>(reinterpret_cast<unsigned char *>(Qg) + off);
-        weights = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(weights) + off);
-        out = reinterpret_cast<WinResult *>(reinterpret_cast<unsigned char *>(out) + off);
-    }
+// The wave kernel's body: one workgroup of three waves, one problem (every entry kernel below runs exactly this).
+template <class IO>
+__device__ __forceinline__ void win_wave_body(const WinParams &P, const IO &io, WinResult *__restrict__ out) {
     __shared__ double4 sQ[WIN_MAX_NV];
     __shared__ double sW[3][SM_MAX_NU];
     __shared__ double sH[3][SM_MAX_NU][SM_MAX_NU + 1];
@@ -824,7 +935,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     long long stamp[6];
     stamp[0] = (long long)__builtin_amdgcn_s_memtime();
-    for (int i = tid; i < nv; i += SM_THREADS) sQ[i] = Qg[i];
+    for (int i = tid; i < nv; i += SM_THREADS) sQ[i] = io.q(i);
     SmLane E;
     E.m = ne;
     E.nu = nu;
@@ -832,10 +943,17 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const 
     E.cj = E.ci = -1;
     int ai = -1, aj = -2;  // make_AtA endpoints i - f, j - f (negative = fixed)
     int ex = 0, ey = 0;
+    bool outside = false;
     double4 qq = make_double4(0, 0, 0, 1);
     if (lane < ne) {
-        const int2 e = Ig[lane];
-        qq = QQ[lane];
+        const int2 e = io.edge(lane);
+        if (IO::kGuard) {
+            // The endpoints come from the device here and no host has seen them. Every wave loads every edge, so the
+            // ballot below is the same in all three: the workgroup leaves as one, before anything is indexed with an
+            // endpoint (so far LDS and the arrays were indexed with i < nv and lane < ne alone).
+            outside = (unsigned)e.x >= (unsigned)nv || (unsigned)e.y >= (unsigned)nv;
+        }
+        qq = io.qq(lane);
         ex = e.x;
         ey = e.y;
         ai = e.x - f;
@@ -843,6 +961,10 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const 
         const uint8_t fl = edge_flags(e.x, e.y, f);
         if (fl & EF_CJ) E.cj = e.y - f;
         if (fl & EF_CI) E.ci = e.x - f;
+    }
+    if (IO::kGuard && __ballot(outside) != 0ull) {
+        if (tid == 0) win_refuse(out, P.seq);
+        return;
     }
     const bool ek = lane < ne, vk = lane < nu;
     if (wave == 0) {
@@ -1013,8 +1135,8 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const 
     if (status) status = IROTAVG_ERR_SOLVER;
     __syncthreads();
     stamp[3] = (long long)__builtin_amdgcn_s_memtime();
-    for (int i = tid; i < nv; i += SM_THREADS) Qg[i] = sQ[i];
-    if (wave == 0 && ek) weights[lane] = d;
+    for (int i = io.store_from(f) + tid; i < nv; i += SM_THREADS) io.put_q(i, sQ[i]);
+    if (wave == 0 && ek) io.put_w(lane, d);
     // The outputs live in pinned host memory; the sequence number goes out last, after a system-scope fence
     // of every thread: a host that sees it sees everything (window_solve polls it instead of waiting for
     // the runtime's completion signal)
@@ -1030,6 +1152,39 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const 
         out->irls_score = score;
         __hip_atomic_store(&out->seq, P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+// BATCH: workgroup b solves the b-th of several INDEPENDENT windows (one per view-graph of a multi-session
+// server: irotavg_viewgraph_rot_avg_batch) -- its parameters come from Pb[b] and its arrays lie b * stride bytes
+// behind the first problem's. A single window is the kernel-argument form (no extra round trip for P).
+template <bool BATCH>
+__global__ __launch_bounds__(SM_THREADS) void k_window_wave(WinParams Pk, const WinParams *__restrict__ Pb,
+                                                           size_t stride, const int2 *__restrict__ Ig,
+                                                           const double4 *__restrict__ QQ,
+                                                           double4 *__restrict__ Qg,
+                                                           double *__restrict__ weights,
+                                                           WinResult *__restrict__ out) {
+    const WinParams P = BATCH ? *reinterpret_cast<const WinParams *>(reinterpret_cast<const unsigned char *>(Pb) + stride * blockIdx.x) : Pk;
+    if (BATCH) {
+        const size_t off = stride * blockIdx.x;
+        Ig = reinterpret_cast<const int2 *>(reinterpret_cast<const unsigned char *>(Ig) + off);
+        QQ = reinterpret_cast<const double4 *>(reinterpret_cast<const unsigned char *>(QQ) + off);
+        Qg = reinterpret_cast<double4 *>(reinterpret_cast<unsigned char *>(Qg) + off);
+        weights = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(weights) + off);
+        out = reinterpret_cast<WinResult *>(reinterpret_cast<unsigned char *>(out) + off);
+    }
+    win_wave_body(P, WinIoOwn{Ig, QQ, Qg, weights}, out);
+}
+
+// The batched form on the caller's packed arrays, as k_window_solve_user
+__global__ __launch_bounds__(SM_THREADS) void k_window_wave_user(WinParams Pk, const WinDesc *__restrict__ D, WinUser U,
+                                                                 WinResult *__restrict__ R) {
+    const WinDesc d = D[blockIdx.x];
+    WinParams P = Pk;
+    P.nv = d.nv;
+    P.f = d.f;
+    P.ne = d.ne;
+    win_wave_body(P, WinIoUser{U, d.eoff, d.voff}, R + d.idx);
 }
 
 // ---- host side: persistent staging, one H2D / launch / D2H per solve ---------------------------
@@ -1051,23 +1206,9 @@ struct WindowSolver {
     }
 };
 
-static size_t win_lds_bytes(int nv, int ne, int nu) {
-    return sizeof(double4) * (size_t)nv +
-           sizeof(double) * ((size_t)4 * ne + ne + 3 * nu + (size_t)nu * (nu + 1) + 3 * nu + 12 * (size_t)ne +
-                             5 * nu + 16) +
-           sizeof(int2) * (size_t)ne + (size_t)ne + 64;
-}
+bool window_fits_wave(int nv, int f, int ne) { return win_fits_wave(nv, f, ne); }
 
-bool window_fits_wave(int nv, int f, int ne) {
-    const int nu = nv - f;
-    return nu >= 1 && nu <= SM_MAX_NU && nv <= WIN_MAX_NV && ne >= 1 && ne <= SM_MAX_NE;
-}
-
-bool window_fits(int nv, int f, int ne) {
-    const int nu = nv - f;
-    return nu >= 1 && nu <= WIN_MAX_NU && nv <= WIN_MAX_NV && ne >= 1 && ne <= WIN_MAX_NE &&
-           win_lds_bytes(nv, ne, nu) <= 160 * 1024;
-}
+bool window_fits(int nv, int f, int ne) { return win_fits(nv, f, ne); }
 
 int window_solve(WindowSolver &ws, int nv, int f, int ne, const int32_t *I, const double *QQ_aos,
                  double *Q_aos, double *weights, int l1_max, int irls_max, int cost, double sigma,
@@ -1208,6 +1349,95 @@ int window_solve_batch(WindowSolver &ws, int nb, WinBatchItem *items, int l1_max
         it.status = R.status;
         if (R.status != IROTAVG_OK && rc == IROTAVG_OK) rc = R.status;
     }
+    return rc;
+}
+
+// ---- irotavg_window_solve_batch_dev: many problems on the caller's device arrays ------------------------------------
+// One object per process: the pinned, device-visible block [nb result records | nb descriptors] that the kernels read
+// their problem from and leave their result in, and the sequence number of the last call. A mutex serialises the calls.
+struct WinBatchDev {
+    std::mutex mu;
+    unsigned char *host = nullptr, *hdev = nullptr;
+    size_t cap = 0;
+    int seq = 0;
+    int attr_device = -1;  // k_window_solve_user may use 160 KB of dynamic LDS on this device
+};
+static WinBatchDev &win_batch_dev() {
+    static WinBatchDev *w = new WinBatchDev();  // (never destroyed: no HIP call at process exit)
+    return *w;
+}
+
+// the arguments have been checked (devapi.hip) and `plan` made from the caller's sizes (winbatch.hpp)
+int window_solve_batch_dev(const WinBatchPlan &plan, int device, const WinBatchArrays &A, int cost, double sigma,
+                           int l1_max, int irls_max, double change_th, int32_t *results, hipStream_t stream) {
+    WinBatchDev &wb = win_batch_dev();
+    std::lock_guard<std::mutex> lock(wb.mu);
+    const size_t nb = plan.desc.size(), nw = (size_t)plan.nwave, ng = nb - nw;
+    const size_t oD = sizeof(WinResult) * nb, total = oD + sizeof(WinDesc) * nb;
+    if (wb.cap < total) {
+        if (wb.host) (void)hipHostFree(wb.host);
+        wb.host = nullptr;
+        wb.cap = 0;
+        const size_t want = total + total / 2;
+        IRH_CHECK(hipHostMalloc((void **)&wb.host, want, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable));
+        wb.cap = want;
+    }
+    IRH_CHECK(hipHostGetDevicePointer((void **)&wb.hdev, wb.host, 0));
+    WinResult *R = reinterpret_cast<WinResult *>(wb.host);
+    std::memcpy(wb.host + oD, plan.desc.data(), sizeof(WinDesc) * nb);
+    wb.seq = ++wb.seq == 0 ? ++wb.seq : wb.seq;  // never 0, which is what the host leaves in every record
+    for (size_t b = 0; b < nb; b++) R[b].seq = 0;
+    const WinParams P{0, 0, 0, l1_max, irls_max, cost, change_th, sigma, wb.seq};
+    WinUser U;
+    U.I = reinterpret_cast<const int2 *>(A.I);
+    U.QQ = A.QQ;
+    U.qq_rs = A.qq_rs;
+    U.qq_cs = A.qq_cs;
+    U.Q = A.Q;
+    U.q_rs = A.q_rs;
+    U.q_cs = A.q_cs;
+    U.w = A.weights;
+    U.qq_aos = A.qq_rs == 4 && A.qq_cs == 1 && (reinterpret_cast<uintptr_t>(A.QQ) & 15) == 0;
+    U.q_aos = A.q_rs == 4 && A.q_cs == 1 && (reinterpret_cast<uintptr_t>(A.Q) & 15) == 0;
+    const WinDesc *D = reinterpret_cast<const WinDesc *>(wb.hdev + oD);
+    WinResult *Rd = reinterpret_cast<WinResult *>(wb.hdev);
+    if (nw) {
+        hipLaunchKernelGGL(k_window_wave_user, dim3((unsigned)nw), dim3(SM_THREADS), 0, stream, P, D, U, Rd);
+        IRH_CHECK(hipGetLastError());
+    }
+    if (ng) {
+        if (wb.attr_device != device) {
+            IRH_CHECK(hipFuncSetAttribute((const void *)k_window_solve_user, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)WIN_MAX_LDS));
+            wb.attr_device = device;
+        }
+        hipLaunchKernelGGL(k_window_solve_user, dim3((unsigned)ng), dim3(WIN_THREADS), plan.lds, stream, P, D + nw, U, Rd);
+        IRH_CHECK(hipGetLastError());
+    }
+    // completion: every workgroup stores the call's sequence number last (see window_solve); the stream is synchronised
+    // once the poll has taken 5 ms (long batches, inputs still in flight on the caller's stream, a kernel that died)
+    const double t0 = now_seconds();
+    size_t next = 0;
+    while (next < nb) {
+        while (next < nb && __atomic_load_n(&R[next].seq, __ATOMIC_ACQUIRE) == wb.seq) next++;
+        if (next == nb || now_seconds() - t0 > 5e-3) break;
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    if (next < nb) IRH_CHECK(hipStreamSynchronize(stream));
+    int rc = IROTAVG_OK;
+    for (size_t b = 0; b < nb; b++) {
+        const int status = R[b].status;
+        if (results) {
+            results[4 * b] = status;
+            results[4 * b + 1] = R[b].l1_iters;
+            results[4 * b + 2] = R[b].irls_iters;
+        }
+        if (status != IROTAVG_OK && rc == IROTAVG_OK) rc = status;
+    }
+    if (results)
+        for (size_t i = 0; i < nb; i++) results[4 * (size_t)plan.desc[i].idx + 3] = i < nw ? 2 : 1;
     return rc;
 }
 

@@ -151,3 +151,69 @@ class TorchGraph(capi.Graph):
     host_set_rotations = capi.Graph.set_rotations
     host_set_weights = capi.Graph.set_weights
     host_edge_diagnostics = capi.Graph.edge_diagnostics
+
+
+# ---- many small problems in one call (irotavg_window_solve_batch_dev, docs/window_batch.md) ------------------------------
+def batch_offsets(sizes):
+    """sizes: host (nb, 3) integers (n_total, f, m) per problem -> (sizes as contiguous int32, first edge row of every
+    problem, first view row of every problem, sum m, sum n_total): the packing the C call assumes."""
+    import numpy as np
+    if isinstance(sizes, torch.Tensor):
+        if sizes.is_cuda:
+            raise TypeError("sizes must be a host array, got a tensor on %s" % sizes.device)
+        sizes = sizes.numpy()
+    s = np.asarray(sizes)
+    if s.dtype.kind not in "iu":
+        raise TypeError("sizes must be integers, got %s" % s.dtype)
+    if s.ndim != 2 or s.shape[1] != 3:
+        raise ValueError("sizes must have shape (nb, 3), got %s" % (s.shape,))
+    if s.size and (s.min() < -INT32_MAX or s.max() > INT32_MAX):
+        raise ValueError("sizes outside int32 range")
+    s64 = s.astype(np.int64)
+    eoff = np.concatenate([[0], np.cumsum(s64[:, 2])[:-1]]) if len(s) else np.zeros(0, dtype=np.int64)
+    voff = np.concatenate([[0], np.cumsum(s64[:, 0])[:-1]]) if len(s) else np.zeros(0, dtype=np.int64)
+    return np.ascontiguousarray(s, dtype=np.int32), eoff, voff, int(s64[:, 2].sum()), int(s64[:, 0].sum())
+
+
+def window_solve_batch(sizes, edge_index, QQ, Q, cost=4, sigma=5 * 3.141592653589793 / 180, l1_iters=100, irls_iters=100,
+                       change_th=1e-3, kernel=0, weights=True, allow_rc=()):
+    """nb independent window-size problems (<= 64 free views, <= 320 views, <= 640 edges each), every one l1ra + irls as
+    capi.window_solve, one workgroup per problem, in at most two launches on torch's current stream.
+
+    sizes: host (nb, 3) integers (n_total, f, m); edge_index: (sum m, 2) int32 or int64 (narrowed on the device), problem
+    after problem, ids local to their problem; QQ: (sum m, 4) and Q: (sum n_total, 4) float64 with any strides, Q is
+    updated in place (rows of fixed views are never written). weights: True (a new tensor), False / None, or a contiguous
+    float64 tensor of sum m entries. Returns dict(rc, Q, weights, status, l1_iters, irls_iters, kernel); the last four
+    are host numpy arrays of nb entries. rc is the first non-zero status in problem order; anything but OK raises unless
+    listed in allow_rc."""
+    import numpy as np
+    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2), placed=False)
+    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), placed=False)
+    _check(Q, "Q", (torch.float64,), (sum_n, 4), placed=False)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), device)
+    _check(Q, "Q", (torch.float64,), (sum_n, 4), device)
+    w = None
+    if weights is True:
+        w = torch.empty(sum_m, dtype=torch.float64, device=device)
+    elif weights is not False and weights is not None:
+        w = _check(weights, "weights", (torch.float64,), (sum_m,), device)
+        if not w.is_contiguous():
+            raise ValueError("weights must be contiguous")
+    nb = len(s32)
+    res = np.zeros((nb, 4), dtype=np.int32)
+    with torch.cuda.device(device):
+        ei = edge_index
+        if ei.dtype == torch.int64:  # narrowed on the device: what does not fit becomes an id the kernels' guard refuses
+            ei = torch.where((ei < 0) | (ei > INT32_MAX), torch.full_like(ei, -1), ei).to(torch.int32)
+        ei = ei.contiguous()
+        rc = capi.lib().irotavg_window_solve_batch_dev(
+            nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(Q),
+            *matrix_strides(Q), int(cost), float(sigma), int(l1_iters), int(irls_iters), float(change_th),
+            None if w is None else _ptr(w), res.ctypes.data_as(C.POINTER(C.c_int32)), int(kernel), _stream(device))
+    if rc != capi.OK and rc not in allow_rc:
+        raise capi.IrotavgError(rc, "irotavg_window_solve_batch_dev")
+    return dict(rc=rc, Q=Q, weights=w, status=res[:, 0].copy(), l1_iters=res[:, 1].copy(), irls_iters=res[:, 2].copy(),
+                kernel=res[:, 3].copy())

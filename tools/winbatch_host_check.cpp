@@ -1,0 +1,158 @@
+// winbatch_host_check.cpp -- the host arithmetic of irotavg_window_solve_batch_dev (irotavg_amd/csrc/winbatch.hpp: size
+// checks, packing offsets, descriptors, the stride rule and the span of a strided matrix) as a stand-alone program that
+// needs no device, meant to be built with a sanitizer:
+//   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -Iirotavg_amd/csrc
+//       tools/winbatch_host_check.cpp -o winbatch_host_check && ./winbatch_host_check
+// Exit status 0 and "winbatch host check ok" when every expectation holds.
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+
+#include "winbatch.hpp"
+
+using namespace irh;
+
+static int failures = 0;
+#define EXPECT(c)                                                        \
+    do {                                                                 \
+        if (!(c)) {                                                      \
+            std::fprintf(stderr, "line %d: %s\n", __LINE__, #c);         \
+            failures++;                                                  \
+        }                                                                \
+    } while (0)
+
+static void check_plan(const std::vector<int32_t> &sizes, int kernel) {
+    const int64_t nb = (int64_t)sizes.size() / 3;
+    WinBatchPlan P;
+    EXPECT(winbatch_plan(nb, sizes.data(), kernel, P));
+    EXPECT((int64_t)P.desc.size() == nb);
+    std::vector<char> seen((size_t)nb, 0);
+    std::vector<int64_t> eoff((size_t)nb), voff((size_t)nb);
+    int64_t e = 0, v = 0;
+    for (int64_t b = 0; b < nb; b++) {
+        eoff[(size_t)b] = e;
+        voff[(size_t)b] = v;
+        v += sizes[3 * b];
+        e += sizes[3 * b + 2];
+    }
+    EXPECT(P.sum_m == e && P.sum_n == v);
+    size_t lds = 0;
+    int last_w = -1, last_g = -1;
+    for (int64_t i = 0; i < nb; i++) {
+        const WinDesc &d = P.desc[(size_t)i];
+        EXPECT(d.idx >= 0 && d.idx < nb && !seen[(size_t)d.idx]);
+        seen[(size_t)d.idx] = 1;
+        EXPECT(d.nv == sizes[3 * d.idx] && d.f == sizes[3 * d.idx + 1] && d.ne == sizes[3 * d.idx + 2]);
+        EXPECT(d.eoff == eoff[(size_t)d.idx] && d.voff == voff[(size_t)d.idx]);
+        const bool wave = i < P.nwave;
+        if (wave) {
+            EXPECT(win_fits_wave(d.nv, d.f, d.ne) && kernel != 1);
+            EXPECT(d.idx > last_w);  // each list in the caller's order
+            last_w = d.idx;
+        } else {
+            EXPECT(kernel == 1 || !win_fits_wave(d.nv, d.f, d.ne));
+            EXPECT(d.idx > last_g);
+            last_g = d.idx;
+            const size_t l = win_lds_bytes_user(d.nv, d.ne, d.nv - d.f);
+            EXPECT(l <= WIN_MAX_LDS);
+            if (l > lds) lds = l;
+        }
+    }
+    EXPECT(P.lds == lds);
+}
+
+int main() {
+    const int32_t imax = std::numeric_limits<int32_t>::max(), imin = std::numeric_limits<int32_t>::min();
+    const int64_t lmax = std::numeric_limits<int64_t>::max(), lmin = std::numeric_limits<int64_t>::min();
+    WinBatchPlan P;
+    // counts and kernels
+    const int32_t one[3] = {12, 2, 40};
+    EXPECT(!winbatch_plan(0, one, 0, P) && !winbatch_plan(-1, one, 0, P) && !winbatch_plan(lmin, one, 0, P));
+    EXPECT(!winbatch_plan(WIN_BATCH_MAX + 1, one, 0, P) && !winbatch_plan(lmax, one, 0, P));
+    EXPECT(!winbatch_plan(1, nullptr, 0, P) && !winbatch_plan(1, one, 3, P) && !winbatch_plan(1, one, -1, P));
+    EXPECT(winbatch_plan(1, one, 0, P) && P.nwave == 1 && P.lds == 0);
+    EXPECT(winbatch_plan(1, one, 1, P) && P.nwave == 0 && P.lds == win_lds_bytes_user(12, 40, 10));
+    // sizes at and past the limits, and values that overflow int32 arithmetic when subtracted or summed
+    const int32_t bad[][3] = {{66, 1, 100}, {321, 300, 100}, {70, 6, 641}, {20, 20, 30}, {20, 1, 0}, {20, -1, 30},
+                              {0, 0, 5}, {-3, 0, 5}, {20, 21, 30}, {imax, imax - 1, 5}, {imax, 0, imax}, {imin, 0, 5},
+                              {5, imin, 5}, {imin, imax, imin}, {imax, imin, imax}, {5, 1, imin}, {5, 1, imax}};
+    for (const auto &b : bad) {
+        const int32_t s[9] = {12, 2, 40, b[0], b[1], b[2], 2, 1, 1};
+        EXPECT(!winbatch_plan(3, s, 0, P));
+        EXPECT(!winbatch_plan(3, s, 1, P));
+        EXPECT(!winbatch_plan(1, b, 2, P));
+    }
+    EXPECT(!win_fits(imax, imin, 1) && !win_fits_wave(imax, imin, 1) && !win_fits(imin, imax, 1));
+    const int32_t w17[3] = {18, 1, 40}, e65[3] = {12, 2, 65};
+    EXPECT(!winbatch_plan(1, w17, 2, P) && !winbatch_plan(1, e65, 2, P));
+    EXPECT(winbatch_plan(1, w17, 0, P) && P.nwave == 0);
+    // mixed plans, every kernel choice
+    {
+        std::vector<int32_t> s;
+        unsigned r = 12345u;
+        auto rnd = [&](int lo, int hi) {
+            r = r * 1664525u + 1013904223u;
+            return lo + (int)((r >> 8) % (unsigned)(hi - lo + 1));
+        };
+        for (int b = 0; b < 5000; b++) {
+            const int nu = rnd(1, 64), f = rnd(0, 320 - nu);
+            int ne = rnd(1, 640);
+            while (!win_fits(nu + f, f, ne)) ne--;
+            s.insert(s.end(), {nu + f, f, ne});
+        }
+        check_plan(s, 0);
+        check_plan(s, 1);
+        std::vector<int32_t> w;
+        for (size_t b = 0; b < s.size() / 3; b++)
+            if (win_fits_wave(s[3 * b], s[3 * b + 1], s[3 * b + 2])) w.insert(w.end(), {s[3 * b], s[3 * b + 1], s[3 * b + 2]});
+        EXPECT(!w.empty());
+        check_plan(w, 2);
+        check_plan(w, 0);
+    }
+    // nb at the cap, every problem at the limits: a BYTE offset (32 per row) in int32 would overflow
+    {
+        std::vector<int32_t> s;
+        s.reserve(3 * (size_t)WIN_BATCH_MAX);
+        for (int64_t b = 0; b < WIN_BATCH_MAX; b++) s.insert(s.end(), {320, 256, 640});
+        check_plan(s, 0);
+        EXPECT(winbatch_plan(WIN_BATCH_MAX, s.data(), 1, P));
+        EXPECT(P.sum_m == WIN_BATCH_MAX * 640 && P.sum_n == WIN_BATCH_MAX * 320 && 32 * P.sum_m > (int64_t)imax);
+        EXPECT(P.desc.back().eoff == (WIN_BATCH_MAX - 1) * 640 && P.desc.back().voff == (WIN_BATCH_MAX - 1) * 320);
+        int64_t lo, hi;
+        EXPECT(strides_ok(P.sum_m, 4, 4, 1) && strides_ok(P.sum_m, 4, (int64_t)1 << 31, 1));
+        matrix_span(P.sum_m, 4, (int64_t)1 << 31, -1, lo, hi);
+        EXPECT(lo == -3 && hi == (P.sum_m - 1) * ((int64_t)1 << 31));
+        EXPECT(!strides_ok(P.sum_m, 4, 1, P.sum_m - 1) && strides_ok(P.sum_m, 4, 1, P.sum_m) &&
+               strides_ok(P.sum_m, 4, -1, -P.sum_m));
+    }
+    // the stride rule at its edges
+    const int64_t L = (int64_t)1 << 31;
+    EXPECT(strides_ok(100, 4, 4, 1) && strides_ok(100, 4, -4, 1) && strides_ok(100, 4, 4, -1) && strides_ok(100, 4, 1, 100));
+    EXPECT(strides_ok(100, 4, 1, -100) && strides_ok(100, 4, 3, 300) && strides_ok(100, 4, 6, 1) && strides_ok(1, 4, 1, 1));
+    EXPECT(!strides_ok(100, 4, 3, 1) && !strides_ok(100, 4, 1, 99) && !strides_ok(100, 4, 2, 1) && !strides_ok(100, 4, 1, 1));
+    EXPECT(!strides_ok(100, 4, 0, 1) && !strides_ok(100, 4, 4, 0) && !strides_ok(0, 4, 4, 1) && !strides_ok(-5, 4, 4, 1));
+    EXPECT(strides_ok(100, 4, L, 1) && strides_ok(100, 4, -L, 1) && strides_ok(100, 4, 1, L) && strides_ok(L, 4, L, 1));
+    EXPECT(strides_ok(L, 4, 1, L) && !strides_ok(L, 4, 1, L - 1) && !strides_ok(L + 1, 4, 4, 1));
+    EXPECT(!strides_ok(100, 4, L + 1, 1) && !strides_ok(100, 4, 1, -L - 1) && !strides_ok(100, 4, lmax, 1));
+    EXPECT(!strides_ok(100, 4, lmin, 1) && !strides_ok(100, 4, 1, lmin) && !strides_ok(100, 4, lmin, lmin) &&
+           !strides_ok(lmax, 4, 4, 1) && !strides_ok(lmin, 4, 4, 1));
+    {
+        int64_t lo, hi;
+        matrix_span(100, 4, 4, 1, lo, hi);
+        EXPECT(lo == 0 && hi == 399);
+        matrix_span(100, 4, -4, 1, lo, hi);
+        EXPECT(lo == -396 && hi == 3);
+        matrix_span(100, 4, 1, -128, lo, hi);
+        EXPECT(lo == -384 && hi == 99);
+        matrix_span(L, 4, -L, -L, lo, hi);  // the largest accepted magnitudes: no overflow
+        EXPECT(lo == -(L - 1) * L - 3 * L && hi == 0);
+        matrix_span(1, 1, 1, 1, lo, hi);
+        EXPECT(lo == 0 && hi == 0);
+    }
+    if (failures) {
+        std::fprintf(stderr, "%d expectation(s) failed\n", failures);
+        return 1;
+    }
+    std::printf("winbatch host check ok\n");
+    return 0;
+}
