@@ -282,6 +282,32 @@ struct PinPool {
     }
 };
 
+// A pinned host block that a kernel reads and writes directly (mapped) and that the host may poll while the kernel runs
+// (coherent: fine-grained) -- the staging of the kernels that do a whole problem in one launch (window.hip, wincov.hip).
+struct MappedBlock {
+    unsigned char *host = nullptr;
+    unsigned char *hdev = nullptr;  // the same block as the device sees it
+    size_t cap = 0;
+    MappedBlock() = default;
+    MappedBlock(const MappedBlock &) = delete;
+    MappedBlock &operator=(const MappedBlock &) = delete;
+    ~MappedBlock() {
+        if (host) (void)hipHostFree(host);
+    }
+    // at least `bytes`: a smaller block is freed first, then bytes + headroom_bytes allocated; cap is set after success
+    void reserve(size_t bytes, size_t headroom_bytes = 0, unsigned extra_flags = 0) {
+        if (cap >= bytes) return;
+        if (host) (void)hipHostFree(host);
+        host = hdev = nullptr;
+        cap = 0;
+        IRH_CHECK(hipHostMalloc((void **)&host, bytes + headroom_bytes, hipHostMallocMapped | hipHostMallocCoherent | extra_flags));
+        map();
+        cap = bytes + headroom_bytes;
+    }
+    // hdev as the CURRENT device sees the block (a portable block serves callers on different devices)
+    void map() { IRH_CHECK(hipHostGetDevicePointer((void **)&hdev, host, 0)); }
+};
+
 // Device buffer (pooled hipMalloc; sized once per graph, HBM-resident for the handle's life).
 template <typename T>
 struct DevBuf {

@@ -21,7 +21,7 @@
 #include "graph.hpp"
 #include "kernels.hpp"
 #include "marginals.hpp"
-#include "winbatch.hpp"  // strides_ok, matrix_span, the plan of irotavg_window_solve_batch_dev
+#include "winbatch.hpp"  // strides_ok, matrix_span, rows16, the plan of irotavg_window_solve_batch_dev
 
 namespace irh {
 namespace {
@@ -33,7 +33,7 @@ enum Path { kAos = 0, kPlanes = 1, kGeneric = 2 };
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline Path path_of(const double *p, long long rs, long long cs, bool allow_aos) {
-    if (allow_aos && rs == 4 && cs == 1 && aligned16(p)) return kAos;
+    if (allow_aos && rows16(reinterpret_cast<uintptr_t>(p), rs, cs)) return kAos;
     if (rs == 1 && (cs & 1) == 0 && aligned16(p)) return kPlanes;
     return kGeneric;
 }

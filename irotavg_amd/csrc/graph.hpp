@@ -1,10 +1,10 @@
 // graph.hpp -- the device-resident view-graph handle behind the C ABI.
 #pragma once
-#include <chrono>
 #include <functional>
 #include <memory>
 
 #include "common.hpp"
+#include "hostwait.hpp"  // now_seconds; the sequence number and the wait of publish_parts / wait_published
 
 namespace irh {
 
@@ -454,10 +454,5 @@ int resident_rot_avg(Resident &r, long n_views, long view_lo, long n_edges, long
 // the prologue of resident_rot_avg alone (deltas, relabelling, device build, poses): the handle of the global problem
 int resident_build_handle(Resident &r, long n_views, long view_lo, long n_edges, long edge_lo, int f,
                           const irotavg_options &opt, const Switches &sw, irotavg_graph **out);
-
-inline double now_seconds() {
-    using namespace std::chrono;
-    return duration<double>(steady_clock::now().time_since_epoch()).count();
-}
 
 }  // namespace irh

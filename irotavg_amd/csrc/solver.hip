@@ -5,7 +5,6 @@
 //   K4 spmv / V-cycle     PCG with an aggregation-multigrid preconditioner replacing
 //                         SuiteSparseQR (:550) and UMFPACK (:147-169)
 //   K6 apply_step         score, exp_map, Q update       (ral/l1_irls.cpp:729-737, 471-492)
-#include <sched.h>
 #include <cstring>
 
 #include "graph.hpp"
@@ -2282,7 +2281,7 @@ __global__ __launch_bounds__(256) void k_publish(const double *__restrict__ s0, 
 // the host's half of a publication: a new sequence number (g.pub_seq), the pinned copy of it cleared; the kernel that
 // stores it last is launched by the caller (k_publish below, or a kernel that publishes on its way)
 void publish_begin(Graph &g) {
-    g.pub_seq = (g.pub_seq + 1 == 0) ? 1 : g.pub_seq + 1;
+    next_seq(g.pub_seq);
     __atomic_store_n(g.h_seq(), 0, __ATOMIC_RELEASE);
 }
 void publish_parts(Graph &g, const PubPart *parts, int nparts) {
@@ -2299,24 +2298,8 @@ void wait_published(Graph &g) {
     // (a pinned block that is not coherent -- the IROTAVG_PIN_DEFAULT experiment -- cannot be polled: every wait would run
     // into the 2 ms limit; env_no_poll covers both switches. Process-wide, like the pinned pool.)
     static const bool no_poll = env_no_poll();
-    bool seen = false;
-    if (!no_poll) {
-        const double t0 = now_seconds();
-        int spins = 0;
-        while (!(seen = __atomic_load_n(g.h_seq(), __ATOMIC_ACQUIRE) == g.pub_seq)) {
-            if ((++spins & 255) == 0) {
-                const double dt = now_seconds() - t0;
-                if (dt > 2e-3) break;
-                // a wait that outlasts every kernel of a step (l1ra's three polling threads on a host with few cores):
-                // give the core away between looks
-                if (dt > 100e-6) sched_yield();
-            }
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-    }
-    if (!seen) IRH_CHECK(hipStreamSynchronize(g.stream));
+    // (yielding after 100 us: l1ra's three polling threads on a host with few cores)
+    if (no_poll || !wait_seq(g.h_seq(), 0, 1, g.pub_seq, 2e-3, 100e-6)) IRH_CHECK(hipStreamSynchronize(g.stream));
 }
 
 // score, exp map, rotation update: kernel + copy of the score partials into the pinned block (no

@@ -1,5 +1,5 @@
 // winbatch.hpp -- the host arithmetic of the window kernels and of irotavg_window_solve_batch_dev: size limits, the
-// stride rule of the `_dev` API, and the plan of a batch (offsets and descriptors from `sizes`). Plain C++ with no HIP
+// staging layout, the stride rule of the `_dev` API, and the plan of a batch (offsets and descriptors from `sizes`). Plain C++ with no HIP
 // type in it, so that a stand-alone program can run all of it under a sanitizer on a machine without a device
 // (tools/winbatch_host_check.cpp).
 #pragma once
@@ -37,6 +37,39 @@ inline bool win_fits(int nv, int f, int ne) {
     return nu >= 1 && nu <= WIN_MAX_NU && nv <= WIN_MAX_NV && ne >= 1 && ne <= WIN_MAX_NE &&
            win_lds_bytes(nv, ne, (int)nu) <= WIN_MAX_LDS;
 }
+
+// what a workgroup of the window kernels is told and what it leaves (no HIP type: the staging layout below counts them)
+struct WinParams {
+    int nv, f, ne;
+    int l1_max, irls_max, cost;
+    double change_th, sigma;
+    int seq;  // k_window_wave stores it into WinResult::seq LAST (system scope): the host polls for it
+};
+struct WinResult {
+    int l1_iters, irls_iters, status, seq;
+    double l1_score, irls_score;
+    long long stamp[8];  // development aid (IROTAVG_WINDOW_STAMPS=1 prints them): s_memtime at the phase boundaries of k_window_wave
+};
+// The library's own staging of one problem, [I | QQ | Q | weights | result | params], for max_ne edges and WIN_MAX_NV
+// views. window_solve: one problem, the block ends at oP (the parameters are a kernel argument); window_solve_batch: slots
+// of `stride` bytes.
+struct WinStage {
+    size_t oI, oQQ, oQ, oW, oR, oP, stride;
+};
+constexpr WinStage win_stage(int max_ne) {
+    const size_t oQQ = 8 * (size_t)max_ne, oQ = oQQ + 32 * (size_t)max_ne, oW = oQ + 32 * (size_t)WIN_MAX_NV;
+    const size_t oR = oW + sizeof(double) * (size_t)max_ne, oP = oR + sizeof(WinResult);
+    return WinStage{0, oQQ, oQ, oW, oR, oP, (oP + sizeof(WinParams) + 255) & ~(size_t)255};
+}
+constexpr WinStage kStageOwn = win_stage(WIN_MAX_NE), kStageBatch = win_stage(SM_MAX_NE);
+static_assert(kStageOwn.oQQ == 5120 && kStageOwn.oQ == 25600 && kStageOwn.oW == 35840 && kStageOwn.oR == 40960 &&
+                  kStageOwn.oP == 41056 && kStageBatch.oQQ == 512 && kStageBatch.oQ == 2560 && kStageBatch.oW == 12800 &&
+                  kStageBatch.oR == 13312 && kStageBatch.oP == 13408 && kStageBatch.stride == 13568,
+              "the byte offsets the kernels of both forms have always been given");
+
+// Rows of four contiguous doubles behind a 16-byte aligned pointer: the one case in which the kernels of the `_dev` API
+// move a row with 16-byte accesses (window.hip: ld_row / st_row, devapi.hip: the AoS path).
+inline bool rows16(uintptr_t p, int64_t rs, int64_t cs) { return rs == 4 && cs == 1 && (p & 15) == 0; }
 
 // A strided rows x cols matrix does not alias itself when its rows do not overlap (|rs| >= cols |cs|) or its columns
 // do not (|cs| >= rows |rs|), both strides non-zero and at most 2^31: the rule include/irotavg_hip.h states.

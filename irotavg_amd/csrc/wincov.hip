@@ -12,7 +12,7 @@
 //   4. from the resident Sigma: the diagonal, s^2 (fixed-order tree), edge_var / leverage / chi2 of every edge, the
 //      pairs, the candidates of the closure gate
 // Staging follows window_solve's wave kernel: one pinned, device-visible block that the kernel reads and writes
-// directly; one launch, one wait (the sequence number the kernel stores last).
+// directly; one launch, one wait (the sequence number the kernel stores last: hostwait.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -259,12 +259,10 @@ __global__ __launch_bounds__(WC_THREADS) void k_window_cov(unsigned char *__rest
 
 struct WinCov {
     hipStream_t stream = nullptr;
-    unsigned char *host = nullptr;  // pinned, device-visible: one slot
-    unsigned char *hdev = nullptr;  // the same block as the device sees it
+    MappedBlock blk;  // one slot
     int seq = 0;
     bool attr_set = false;
     ~WinCov() {
-        if (host) (void)hipHostFree(host);
         if (stream) StreamPool::get().give(stream);
     }
 };
@@ -277,15 +275,12 @@ int wincov_query(WinCov &wc, WinCovQuery &q) {
     static_assert(sizeof(WinCovParams) <= oI, "the parameter record outgrew its place in the slot");
     static_assert(kLds <= 160 * 1024, "LDS of a gfx950 workgroup");
     if (!wc.stream) wc.stream = StreamPool::get().take();
-    if (!wc.host) {
-        IRH_CHECK(hipHostMalloc((void **)&wc.host, kSlot, hipHostMallocMapped | hipHostMallocCoherent));
-        IRH_CHECK(hipHostGetDevicePointer((void **)&wc.hdev, wc.host, 0));
-    }
+    wc.blk.reserve(kSlot);
     if (!wc.attr_set) {
         IRH_CHECK(hipFuncSetAttribute((const void *)k_window_cov, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
         wc.attr_set = true;
     }
-    unsigned char *h = wc.host;
+    unsigned char *h = wc.blk.host;
     std::memcpy(h + oI, q.I, sizeof(int32_t) * 2 * (size_t)q.ne);
     std::memcpy(h + oQQ, q.qq_aos, sizeof(double) * 4 * (size_t)q.ne);
     std::memcpy(h + oQ, q.Q_aos, sizeof(double) * 4 * (size_t)q.nv);
@@ -297,7 +292,7 @@ int wincov_query(WinCov &wc, WinCovQuery &q) {
     while (first || p0 < q.np || c0 < q.nc) {
         const int np = std::min(WC_MAX_P, q.np - p0), nc = std::min(WC_MAX_C, q.nc - c0);
         WinCovParams P{q.nv, q.f, q.ne, np, nc, 0, first ? 1 : 0, q.sigma};
-        P.seq = ++wc.seq == 0 ? ++wc.seq : wc.seq;  // never 0, which is what the host leaves in the result
+        P.seq = next_seq(wc.seq);
         std::memcpy(h + oP, &P, sizeof(P));
         if (np > 0) std::memcpy(h + oPR, q.prow + 2 * (size_t)p0, sizeof(int32_t) * 2 * (size_t)np);
         if (nc > 0) {
@@ -306,18 +301,9 @@ int wincov_query(WinCov &wc, WinCovQuery &q) {
         }
         WinCovResult *res = reinterpret_cast<WinCovResult *>(h + oRes);
         res->seq = 0;
-        hipLaunchKernelGGL(k_window_cov, dim3(1), dim3(WC_THREADS), kLds, wc.stream, wc.hdev, kSlot);
+        hipLaunchKernelGGL(k_window_cov, dim3(1), dim3(WC_THREADS), kLds, wc.stream, wc.blk.hdev, kSlot);
         IRH_CHECK(hipGetLastError());
-        // completion as in window_solve: poll the sequence number the kernel stores last; after 2 ms the stream is waited on
-        const double t0 = now_seconds();
-        bool seen = false;
-        while (!(seen = __atomic_load_n(&res->seq, __ATOMIC_ACQUIRE) == P.seq)) {
-            if (now_seconds() - t0 > 2e-3) break;
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-        if (!seen) IRH_CHECK(hipStreamSynchronize(wc.stream));
+        if (!wait_seq(&res->seq, 0, 1, P.seq, 2e-3)) IRH_CHECK(hipStreamSynchronize(wc.stream));
         if (res->status != IROTAVG_OK) return res->status;  // outputs untouched
         if (first) q.s2 = res->s2;
         if (np > 0) std::memcpy(q.pair_var + p0, h + oPv, sizeof(double) * (size_t)np);

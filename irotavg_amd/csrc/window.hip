@@ -13,24 +13,12 @@
 
 #include "graph.hpp"
 #include "kernels.hpp"
-#include "winbatch.hpp"  // the size limits (WIN_MAX_*, SM_MAX_*), win_lds_bytes, the plan of a batch
+#include "winbatch.hpp"  // the size limits (WIN_MAX_*, SM_MAX_*), win_lds_bytes, WinParams / WinResult, the staging layout, the plan of a batch
 
 namespace irh {
 
 constexpr int WIN_THREADS = 256;
 static_assert(sizeof(double4) == 32 && sizeof(int2) == 8, "win_lds_bytes (winbatch.hpp) counts with these");
-
-struct WinParams {
-    int nv, f, ne;
-    int l1_max, irls_max, cost;
-    double change_th, sigma;
-    int seq;  // k_window_wave stores it into WinResult::seq LAST (system scope): the host polls for it
-};
-struct WinResult {
-    int l1_iters, irls_iters, status, seq;
-    double l1_score, irls_score;
-    long long stamp[8];  // development aid (IROTAVG_WINDOW_STAMPS=1 prints them): s_memtime at the phase boundaries of k_window_wave
-};
 
 struct WinShared {
     double4 *Q;       // nv
@@ -1188,20 +1176,16 @@ __global__ __launch_bounds__(SM_THREADS) void k_window_wave_user(WinParams Pk, c
 }
 
 // ---- host side: persistent staging, one H2D / launch / D2H per solve ---------------------------
+// Completion of the kernels that store a sequence number last (k_window_wave, the _user kernels): hostwait.hpp.
 struct WindowSolver {
     hipStream_t stream = nullptr;
-    DevBuf<unsigned char> dev;   // [I | QQ | Q | weights | result]
-    unsigned char *host = nullptr;   // pinned, device-visible
-    unsigned char *hdev = nullptr;   // the same block as the device sees it
-    size_t cap = 0;
+    DevBuf<unsigned char> dev;   // the general kernel's device copy of `own`
+    MappedBlock own;             // window_solve: one problem (kStageOwn)
+    MappedBlock batch;           // window_solve_batch: slots of kStageBatch
     int seq = 0;       // sequence number of the last wave-kernel launch
     bool attr_set = false;
     bool stamps = false;  // Switches::window_stamps of whoever made the solver: print the wave kernel's phase stamps
-    unsigned char *bhost = nullptr, *bhdev = nullptr;  // pinned block of the batched form (window_solve_batch)
-    size_t bcap = 0;
     ~WindowSolver() {
-        if (bhost) (void)hipHostFree(bhost);
-        if (host) (void)hipHostFree(host);
         if (stream) StreamPool::get().give(stream);
     }
 };
@@ -1210,6 +1194,21 @@ bool window_fits_wave(int nv, int f, int ne) { return win_fits_wave(nv, f, ne); 
 
 bool window_fits(int nv, int f, int ne) { return win_fits(nv, f, ne); }
 
+// a problem into its slot `h` of a staging block; the record's sequence number is 0 until the kernel stores the launch's
+static void stage_problem(unsigned char *h, const WinStage &L, int nv, int ne, const int32_t *I, const double *QQ_aos,
+                          const double *Q_aos) {
+    std::memcpy(h + L.oI, I, sizeof(int32_t) * 2 * (size_t)ne);
+    std::memcpy(h + L.oQQ, QQ_aos, sizeof(double) * 4 * (size_t)ne);
+    std::memcpy(h + L.oQ, Q_aos, sizeof(double) * 4 * (size_t)nv);
+    reinterpret_cast<WinResult *>(h + L.oR)->seq = 0;
+}
+// the record a workgroup left; rc becomes the first status that is not OK
+static const WinResult &take_result(const void *rec, int &rc) {
+    const WinResult &R = *static_cast<const WinResult *>(rec);  // (every oR and the slot stride are multiples of 8)
+    if (R.status != IROTAVG_OK && rc == IROTAVG_OK) rc = R.status;
+    return R;
+}
+
 int window_solve(WindowSolver &ws, int nv, int f, int ne, const int32_t *I, const double *QQ_aos,
                  double *Q_aos, double *weights, int l1_max, int irls_max, int cost, double sigma,
                  double change_th, int *l1_iters, int *irls_iters, int kernel) {
@@ -1217,47 +1216,27 @@ int window_solve(WindowSolver &ws, int nv, int f, int ne, const int32_t *I, cons
     if (kernel == 2 && !window_fits_wave(nv, f, ne)) return IROTAVG_ERR_BAD_ARG;
     const bool wave = kernel == 2 || (kernel == 0 && window_fits_wave(nv, f, ne));
     if (!ws.stream) ws.stream = StreamPool::get().take();
-    const size_t oI = 0, oQQ = oI + sizeof(int2) * (size_t)WIN_MAX_NE;
-    const size_t oQ = oQQ + sizeof(double4) * (size_t)WIN_MAX_NE;
-    const size_t oW = oQ + sizeof(double4) * (size_t)WIN_MAX_NV;
-    const size_t oR = oW + sizeof(double) * (size_t)WIN_MAX_NE;
-    const size_t total = oR + sizeof(WinResult);
-    if (ws.cap < total) {
-        ws.dev.alloc(total);
-        if (ws.host) (void)hipHostFree(ws.host);
-        IRH_CHECK(hipHostMalloc((void **)&ws.host, total, hipHostMallocMapped | hipHostMallocCoherent));  // fine-grained: the kernel's stores are visible to the polling host while it runs
-        IRH_CHECK(hipHostGetDevicePointer((void **)&ws.hdev, ws.host, 0));
-        ws.cap = total;
-    }
-    std::memcpy(ws.host + oI, I, sizeof(int32_t) * 2 * (size_t)ne);
-    std::memcpy(ws.host + oQQ, QQ_aos, sizeof(double) * 4 * (size_t)ne);
-    std::memcpy(ws.host + oQ, Q_aos, sizeof(double) * 4 * (size_t)nv);
+    constexpr WinStage L = kStageOwn;
+    constexpr size_t total = L.oP;  // sized exactly: every problem takes the same block
+    if (ws.own.cap < total) ws.dev.alloc(total);
+    ws.own.reserve(total);
+    unsigned char *const host = ws.own.host, *const hdev = ws.own.hdev;
+    stage_problem(host, L, nv, ne, I, QQ_aos, Q_aos);
     WinParams P{nv, f, ne, l1_max, irls_max, cost, change_th, sigma, 0};
     if (wave) {
-        P.seq = ++ws.seq == 0 ? ++ws.seq : ws.seq;  // never 0 ...
-        reinterpret_cast<WinResult *>(ws.host + oR)->seq = 0;  // ... which is what the host leaves there
+        P.seq = next_seq(ws.seq);
         // the wave kernel touches its inputs once and its outputs once: it works directly on the
-        // pinned (device-visible) staging block -- launch + synchronise, no copy commands
+        // pinned (device-visible) staging block -- launch + wait, no copy commands
         hipLaunchKernelGGL((k_window_wave<false>), dim3(1), dim3(SM_THREADS), 0, ws.stream, P,
                            (const WinParams *)nullptr, (size_t)0,
-                           (const int2 *)(ws.hdev + oI), (const double4 *)(ws.hdev + oQQ),
-                           (double4 *)(ws.hdev + oQ), (double *)(ws.hdev + oW),
-                           (WinResult *)(ws.hdev + oR));
+                           (const int2 *)(hdev + L.oI), (const double4 *)(hdev + L.oQQ),
+                           (double4 *)(hdev + L.oQ), (double *)(hdev + L.oW),
+                           (WinResult *)(hdev + L.oR));
         IRH_CHECK(hipGetLastError());
-        // completion: poll the sequence number the kernel stores last into the pinned block (the runtime's
-        // own wait costs 5-10 us of a 60 us call); after 2 ms, or if the kernel died, the stream is synchronised
-        volatile int *seqp = &reinterpret_cast<WinResult *>(ws.host + oR)->seq;
-        const double t0 = now_seconds();
-        bool seen = false;
-        while (!(seen = __atomic_load_n(const_cast<int *>(seqp), __ATOMIC_ACQUIRE) == P.seq)) {
-            if (now_seconds() - t0 > 2e-3) break;
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-        if (!seen) IRH_CHECK(hipStreamSynchronize(ws.stream));
+        if (!wait_seq(&reinterpret_cast<const WinResult *>(host + L.oR)->seq, 0, 1, P.seq, 2e-3))
+            IRH_CHECK(hipStreamSynchronize(ws.stream));
     } else {
-        IRH_CHECK(hipMemcpyAsync(ws.dev.p, ws.host, oW, hipMemcpyHostToDevice, ws.stream));
+        IRH_CHECK(hipMemcpyAsync(ws.dev.p, host, L.oW, hipMemcpyHostToDevice, ws.stream));
         const size_t shm = win_lds_bytes(nv, ne, nv - f);
         if (!ws.attr_set) {
             IRH_CHECK(hipFuncSetAttribute((const void *)k_window_solve,
@@ -1265,89 +1244,61 @@ int window_solve(WindowSolver &ws, int nv, int f, int ne, const int32_t *I, cons
             ws.attr_set = true;
         }
         hipLaunchKernelGGL(k_window_solve, dim3(1), dim3(WIN_THREADS), shm, ws.stream, P,
-                           (const int2 *)(ws.dev.p + oI), (const double4 *)(ws.dev.p + oQQ),
-                           (double4 *)(ws.dev.p + oQ), (double *)(ws.dev.p + oW),
-                           (WinResult *)(ws.dev.p + oR));
-        IRH_CHECK(hipMemcpyAsync(ws.host + oQ, ws.dev.p + oQ, total - oQ, hipMemcpyDeviceToHost, ws.stream));
+                           (const int2 *)(ws.dev.p + L.oI), (const double4 *)(ws.dev.p + L.oQQ),
+                           (double4 *)(ws.dev.p + L.oQ), (double *)(ws.dev.p + L.oW),
+                           (WinResult *)(ws.dev.p + L.oR));
+        IRH_CHECK(hipMemcpyAsync(host + L.oQ, ws.dev.p + L.oQ, total - L.oQ, hipMemcpyDeviceToHost, ws.stream));
         IRH_CHECK(hipStreamSynchronize(ws.stream));
     }
-    WinResult R;
-    std::memcpy(&R, ws.host + oR, sizeof(R));
+    int rc = IROTAVG_OK;
+    const WinResult &R = take_result(host + L.oR, rc);
     if (ws.stamps && wave)  // s_memtime counts at 100 MHz
         std::fprintf(stderr, "[window] nv %d f %d ne %d l1 %d irls %d: load+lists %.2f us, l1ra %.2f us, irls %.2f us, store %.2f us\n", nv,
                      f, ne, R.l1_iters, R.irls_iters, (R.stamp[1] - R.stamp[0]) * 1e-2, (R.stamp[2] - R.stamp[1]) * 1e-2,
                      (R.stamp[3] - R.stamp[2]) * 1e-2, (R.stamp[4] - R.stamp[3]) * 1e-2);
-    std::memcpy(Q_aos, ws.host + oQ, sizeof(double) * 4 * (size_t)nv);
-    if (weights) std::memcpy(weights, ws.host + oW, sizeof(double) * (size_t)ne);
+    std::memcpy(Q_aos, host + L.oQ, sizeof(double) * 4 * (size_t)nv);
+    if (weights) std::memcpy(weights, host + L.oW, sizeof(double) * (size_t)ne);
     if (l1_iters) *l1_iters = R.l1_iters;
     if (irls_iters) *irls_iters = R.irls_iters;
-    return R.status;
+    return rc;
 }
 
 // Several independent window problems in ONE launch (one workgroup each): every problem must fit the
-// wave-resident kernel. Layout of the pinned block: nb slots of `stride` bytes [I | QQ | Q | weights | result | params].
+// wave-resident kernel. The pinned block holds nb slots of kStageBatch, parameters included.
 int window_solve_batch(WindowSolver &ws, int nb, WinBatchItem *items, int l1_max, int irls_max, int cost, double sigma,
                        double change_th) {
     if (nb <= 0) return IROTAVG_OK;
     for (int b = 0; b < nb; b++)
         if (!window_fits_wave(items[b].nv, items[b].f, items[b].ne)) return IROTAVG_ERR_BAD_ARG;
     if (!ws.stream) ws.stream = StreamPool::get().take();
-    const size_t oI = 0, oQQ = oI + sizeof(int2) * (size_t)SM_MAX_NE;
-    const size_t oQ = oQQ + sizeof(double4) * (size_t)SM_MAX_NE;
-    const size_t oW = oQ + sizeof(double4) * (size_t)WIN_MAX_NV;
-    const size_t oR = oW + sizeof(double) * (size_t)SM_MAX_NE;
-    const size_t oP = oR + sizeof(WinResult);
-    const size_t stride = (oP + sizeof(WinParams) + 255) & ~(size_t)255;
-    const size_t total = stride * (size_t)nb;
-    if (ws.bcap < total) {
-        if (ws.bhost) (void)hipHostFree(ws.bhost);
-        ws.bhost = nullptr;
-        IRH_CHECK(hipHostMalloc((void **)&ws.bhost, total + total / 2, hipHostMallocMapped | hipHostMallocCoherent));
-        IRH_CHECK(hipHostGetDevicePointer((void **)&ws.bhdev, ws.bhost, 0));
-        ws.bcap = total + total / 2;
-    }
-    ws.seq = ++ws.seq == 0 ? ++ws.seq : ws.seq;
+    constexpr WinStage L = kStageBatch;
+    const size_t total = L.stride * (size_t)nb;
+    ws.batch.reserve(total, total / 2);
+    unsigned char *const host = ws.batch.host, *const hdev = ws.batch.hdev;
+    const int seq = next_seq(ws.seq);
     for (int b = 0; b < nb; b++) {
-        unsigned char *h = ws.bhost + stride * (size_t)b;
+        unsigned char *h = host + L.stride * (size_t)b;
         const WinBatchItem &it = items[b];
-        std::memcpy(h + oI, it.I, sizeof(int32_t) * 2 * (size_t)it.ne);
-        std::memcpy(h + oQQ, it.QQ_aos, sizeof(double) * 4 * (size_t)it.ne);
-        std::memcpy(h + oQ, it.Q_aos, sizeof(double) * 4 * (size_t)it.nv);
-        WinParams P{it.nv, it.f, it.ne, l1_max, irls_max, cost, change_th, sigma, ws.seq};
-        std::memcpy(h + oP, &P, sizeof(P));
-        reinterpret_cast<WinResult *>(h + oR)->seq = 0;
+        stage_problem(h, L, it.nv, it.ne, it.I, it.QQ_aos, it.Q_aos);
+        WinParams P{it.nv, it.f, it.ne, l1_max, irls_max, cost, change_th, sigma, seq};
+        std::memcpy(h + L.oP, &P, sizeof(P));
     }
     hipLaunchKernelGGL((k_window_wave<true>), dim3(nb), dim3(SM_THREADS), 0, ws.stream, WinParams{},
-                       (const WinParams *)(ws.bhdev + oP), stride, (const int2 *)(ws.bhdev + oI),
-                       (const double4 *)(ws.bhdev + oQQ), (double4 *)(ws.bhdev + oQ), (double *)(ws.bhdev + oW),
-                       (WinResult *)(ws.bhdev + oR));
+                       (const WinParams *)(hdev + L.oP), L.stride, (const int2 *)(hdev + L.oI),
+                       (const double4 *)(hdev + L.oQQ), (double4 *)(hdev + L.oQ), (double *)(hdev + L.oW),
+                       (WinResult *)(hdev + L.oR));
     IRH_CHECK(hipGetLastError());
-    // completion: every workgroup stores the launch's sequence number last (see window_solve)
-    const double t0 = now_seconds();
-    bool all = false;
-    int next = 0;
-    while (!all) {
-        while (next < nb && __atomic_load_n(&reinterpret_cast<WinResult *>(ws.bhost + stride * (size_t)next + oR)->seq,
-                                            __ATOMIC_ACQUIRE) == ws.seq)
-            next++;
-        all = next == nb;
-        if (!all && now_seconds() - t0 > 5e-3) break;
-#if defined(__x86_64__)
-        if (!all) __builtin_ia32_pause();
-#endif
-    }
-    if (!all) IRH_CHECK(hipStreamSynchronize(ws.stream));
+    if (!wait_seq(&reinterpret_cast<const WinResult *>(host + L.oR)->seq, L.stride, (size_t)nb, seq, 5e-3))
+        IRH_CHECK(hipStreamSynchronize(ws.stream));
     int rc = IROTAVG_OK;
     for (int b = 0; b < nb; b++) {
-        unsigned char *h = ws.bhost + stride * (size_t)b;
+        const unsigned char *h = host + L.stride * (size_t)b;
         WinBatchItem &it = items[b];
-        WinResult R;
-        std::memcpy(&R, h + oR, sizeof(R));
-        std::memcpy(it.Q_aos, h + oQ, sizeof(double) * 4 * (size_t)it.nv);
+        const WinResult &R = take_result(h + L.oR, rc);
+        std::memcpy(it.Q_aos, h + L.oQ, sizeof(double) * 4 * (size_t)it.nv);
         it.l1_iters = R.l1_iters;
         it.irls_iters = R.irls_iters;
         it.status = R.status;
-        if (R.status != IROTAVG_OK && rc == IROTAVG_OK) rc = R.status;
     }
     return rc;
 }
@@ -1357,8 +1308,7 @@ int window_solve_batch(WindowSolver &ws, int nb, WinBatchItem *items, int l1_max
 // their problem from and leave their result in, and the sequence number of the last call. A mutex serialises the calls.
 struct WinBatchDev {
     std::mutex mu;
-    unsigned char *host = nullptr, *hdev = nullptr;
-    size_t cap = 0;
+    MappedBlock blk;  // portable: the callers' current devices may differ
     int seq = 0;
     int attr_device = -1;  // k_window_solve_user may use 160 KB of dynamic LDS on this device
 };
@@ -1374,33 +1324,17 @@ int window_solve_batch_dev(const WinBatchPlan &plan, int device, const WinBatchA
     std::lock_guard<std::mutex> lock(wb.mu);
     const size_t nb = plan.desc.size(), nw = (size_t)plan.nwave, ng = nb - nw;
     const size_t oD = sizeof(WinResult) * nb, total = oD + sizeof(WinDesc) * nb;
-    if (wb.cap < total) {
-        if (wb.host) (void)hipHostFree(wb.host);
-        wb.host = nullptr;
-        wb.cap = 0;
-        const size_t want = total + total / 2;
-        IRH_CHECK(hipHostMalloc((void **)&wb.host, want, hipHostMallocMapped | hipHostMallocCoherent | hipHostMallocPortable));
-        wb.cap = want;
-    }
-    IRH_CHECK(hipHostGetDevicePointer((void **)&wb.hdev, wb.host, 0));
-    WinResult *R = reinterpret_cast<WinResult *>(wb.host);
-    std::memcpy(wb.host + oD, plan.desc.data(), sizeof(WinDesc) * nb);
-    wb.seq = ++wb.seq == 0 ? ++wb.seq : wb.seq;  // never 0, which is what the host leaves in every record
+    wb.blk.reserve(total, total / 2, hipHostMallocPortable);
+    wb.blk.map();  // on every call: the current device can differ from the last call's
+    WinResult *R = reinterpret_cast<WinResult *>(wb.blk.host);
+    std::memcpy(wb.blk.host + oD, plan.desc.data(), sizeof(WinDesc) * nb);
     for (size_t b = 0; b < nb; b++) R[b].seq = 0;
-    const WinParams P{0, 0, 0, l1_max, irls_max, cost, change_th, sigma, wb.seq};
-    WinUser U;
-    U.I = reinterpret_cast<const int2 *>(A.I);
-    U.QQ = A.QQ;
-    U.qq_rs = A.qq_rs;
-    U.qq_cs = A.qq_cs;
-    U.Q = A.Q;
-    U.q_rs = A.q_rs;
-    U.q_cs = A.q_cs;
-    U.w = A.weights;
-    U.qq_aos = A.qq_rs == 4 && A.qq_cs == 1 && (reinterpret_cast<uintptr_t>(A.QQ) & 15) == 0;
-    U.q_aos = A.q_rs == 4 && A.q_cs == 1 && (reinterpret_cast<uintptr_t>(A.Q) & 15) == 0;
-    const WinDesc *D = reinterpret_cast<const WinDesc *>(wb.hdev + oD);
-    WinResult *Rd = reinterpret_cast<WinResult *>(wb.hdev);
+    const WinParams P{0, 0, 0, l1_max, irls_max, cost, change_th, sigma, next_seq(wb.seq)};
+    const WinUser U{reinterpret_cast<const int2 *>(A.I), A.QQ, A.qq_rs, A.qq_cs, A.Q, A.q_rs, A.q_cs, A.weights,
+                    rows16(reinterpret_cast<uintptr_t>(A.QQ), A.qq_rs, A.qq_cs),
+                    rows16(reinterpret_cast<uintptr_t>(A.Q), A.q_rs, A.q_cs)};
+    const WinDesc *D = reinterpret_cast<const WinDesc *>(wb.blk.hdev + oD);
+    WinResult *Rd = reinterpret_cast<WinResult *>(wb.blk.hdev);
     if (nw) {
         hipLaunchKernelGGL(k_window_wave_user, dim3((unsigned)nw), dim3(SM_THREADS), 0, stream, P, D, U, Rd);
         IRH_CHECK(hipGetLastError());
@@ -1414,27 +1348,16 @@ int window_solve_batch_dev(const WinBatchPlan &plan, int device, const WinBatchA
         hipLaunchKernelGGL(k_window_solve_user, dim3((unsigned)ng), dim3(WIN_THREADS), plan.lds, stream, P, D + nw, U, Rd);
         IRH_CHECK(hipGetLastError());
     }
-    // completion: every workgroup stores the call's sequence number last (see window_solve); the stream is synchronised
-    // once the poll has taken 5 ms (long batches, inputs still in flight on the caller's stream, a kernel that died)
-    const double t0 = now_seconds();
-    size_t next = 0;
-    while (next < nb) {
-        while (next < nb && __atomic_load_n(&R[next].seq, __ATOMIC_ACQUIRE) == wb.seq) next++;
-        if (next == nb || now_seconds() - t0 > 5e-3) break;
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    if (next < nb) IRH_CHECK(hipStreamSynchronize(stream));
+    // 5 ms: long batches, inputs still in flight on the caller's stream, a kernel that died
+    if (!wait_seq(&R[0].seq, sizeof(WinResult), nb, P.seq, 5e-3)) IRH_CHECK(hipStreamSynchronize(stream));
     int rc = IROTAVG_OK;
     for (size_t b = 0; b < nb; b++) {
-        const int status = R[b].status;
+        const WinResult &r = take_result(R + b, rc);
         if (results) {
-            results[4 * b] = status;
-            results[4 * b + 1] = R[b].l1_iters;
-            results[4 * b + 2] = R[b].irls_iters;
+            results[4 * b] = r.status;
+            results[4 * b + 1] = r.l1_iters;
+            results[4 * b + 2] = r.irls_iters;
         }
-        if (status != IROTAVG_OK && rc == IROTAVG_OK) rc = status;
     }
     if (results)
         for (size_t i = 0; i < nb; i++) results[4 * (size_t)plan.desc[i].idx + 3] = i < nw ? 2 : 1;

@@ -112,6 +112,21 @@ def assert_bitwise(cases, r, cost=4, l1=100, irls=100, only=None):
         assert r["Qh"][vo[b]:vo[b] + c["f"]].tobytes() == np.ascontiguousarray(c["Q0"][:c["f"]]).tobytes(), c["name"]
 
 
+# ---- 0. the pinned block grows and is reused (first in the file: the block is process-wide and never shrinks) -----------------
+GROW = [named("grow-%d" % b, WC.size_case(2, 3, 3, seed=100 + b)) for b in range(40)]  # 3 views, 1 fixed, 3 edges, 0.01 rad
+
+
+def test_a_block_that_grew_is_reused():
+    """1 problem, then 40, then the 1 again: the second call replaces the block of result records and descriptors by a
+    larger one (40 need 5120 bytes, the first call reserved 192), the third finds it larger than it needs."""
+    first, many, third = run(GROW[:1]), run(GROW), run(GROW[:1])
+    assert (first["rc"], many["rc"], third["rc"]) == (0, 0, 0)
+    for k in ("Qh", "wh", "status", "l1_iters", "irls_iters", "kernel"):
+        assert np.asarray(first[k]).tobytes() == np.asarray(third[k]).tobytes(), k
+    assert_bitwise(GROW[:1], first)
+    assert_bitwise(GROW, many)
+
+
 # ---- 1. mixed batch ------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def mixed():

@@ -414,6 +414,50 @@ def test_batched_rotavg_over_independent_graphs_equals_separate_calls():
 
 
 @pytest.mark.gpu
+def test_batched_rotavg_staging_grows_and_is_reused():
+    """irotavg_viewgraph_rot_avg_batch with 2, then 5, then the first 2 sessions again (three views, the first fixed, three
+    connections with 0.01 rad of noise; the poses put back before every call): the staging of the first session's window
+    solver is replaced by a larger block for the second call and reused by the third. The first and the third call give
+    the same bits, and each of the five sessions of the second the bits of its own rotAvg(10)."""
+    from irotavg_amd.viewgraph import rotAvgBatch
+    S = 5
+    seqs = [build_sequence(3, seed=70 + s, n_loops=0) for s in range(S)]
+    rng = np.random.default_rng(3)
+    R0 = [[rot(synth.qmul(synth.qexp(rng.normal(scale=0.05, size=(1, 3)))[0], Qgt[v])) if v else rot(Qgt[0])
+           for v in range(3)] for Qgt, _ in seqs]
+
+    def session(s):
+        G = ViewGraph()
+        for v in range(3):
+            G.addView(R0[s][v])
+        for (i, j), R in seqs[s][1].items():
+            assert G.connect(i, j, R)
+        G.fixPose(0, R0[s][0])
+        return G
+
+    def batch(graphs):
+        for s, G in enumerate(graphs):
+            for v in (1, 2):
+                G.setR(v, R0[s][v])
+        infos = rotAvgBatch(graphs, 10)
+        for i in infos:
+            assert (i["skipped"], i["n_views"], i["n_edges"], i["n_fixed"]) == (0, 3, 3, 1), i
+        return ([(i["l1_iters"], i["irls_iters"]) for i in infos],
+                np.stack([G.R(v) for G in graphs for v in range(3)]))
+
+    A = [session(s) for s in range(S)]
+    first, many, third = batch(A[:2]), batch(A), batch(A[:2])
+    assert first[0] == third[0] and first[1].tobytes() == third[1].tobytes()
+    assert many[0][:2] == first[0] and many[1][:6].tobytes() == first[1].tobytes()
+    for s in range(S):
+        B = session(s)
+        ib = B.rotAvg(10)
+        assert (ib["skipped"], ib["n_views"], ib["n_edges"], ib["n_fixed"]) == (0, 3, 3, 1), ib
+        assert many[0][s] == (ib["l1_iters"], ib["irls_iters"])
+        assert many[1][3 * s:3 * s + 3].tobytes() == np.stack([B.R(v) for v in range(3)]).tobytes()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", [3000, 6000])
 def test_global_rotavg_falls_back_to_the_iterative_solver_when_the_direct_one_gives_up(n, monkeypatch):
     """ViewGraph::rotAvg has one code path for every graph (src/ViewGraph.cpp:1400-1417 over ral/l1_irls.cpp:536-556).

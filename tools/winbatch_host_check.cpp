@@ -1,6 +1,6 @@
 // winbatch_host_check.cpp -- the host arithmetic of irotavg_window_solve_batch_dev (irotavg_amd/csrc/winbatch.hpp: size
-// checks, packing offsets, descriptors, the stride rule and the span of a strided matrix) as a stand-alone program that
-// needs no device, meant to be built with a sanitizer:
+// checks, packing offsets, descriptors, the stride rule, the span of a strided matrix and the 16-byte row rule) as a
+// stand-alone program that needs no device, meant to be built with a sanitizer:
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -Iirotavg_amd/csrc
 //       tools/winbatch_host_check.cpp -o winbatch_host_check && ./winbatch_host_check
 // Exit status 0 and "winbatch host check ok" when every expectation holds.
@@ -149,6 +149,11 @@ int main() {
         matrix_span(1, 1, 1, 1, lo, hi);
         EXPECT(lo == 0 && hi == 0);
     }
+    // 16-byte row accesses: contiguous rows behind a 16-byte aligned pointer, nothing else
+    EXPECT(rows16(0x1000, 4, 1) && rows16(0x1010, 4, 1) && !rows16(0x1008, 4, 1) && !rows16(0x1004, 4, 1));
+    EXPECT(!rows16(0x1000, 1, 4) && !rows16(0x1000, 8, 1) && !rows16(0x1000, 4, 2) && !rows16(0x1000, -4, 1) &&
+           !rows16(0x1000, 4, -1) && !rows16(0x1000, 1, 1000) && !rows16(0x1000, lmin, 1) && !rows16(0x1000, 4, lmax));
+    EXPECT(rows16(~(uintptr_t)15, 4, 1) && !rows16(~(uintptr_t)7, 4, 1));
     if (failures) {
         std::fprintf(stderr, "%d expectation(s) failed\n", failures);
         return 1;
