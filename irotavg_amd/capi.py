@@ -445,6 +445,18 @@ class Graph:
             raise IrotavgError(n, "fingerprint")
         return [int(out[i]) for i in range(n)]
 
+    # the scalars that close the fingerprint, in the order irotavg_graph_fingerprint (capi.cpp) appends them
+    FINGERPRINT_TAIL = ("l0_far_entries", "asm_windowed", "asm_l1_fused", "l1_fused", "cg2", "ndense", "ndense_pad",
+                        "dense_bw", "mg_dense_max", "mg_kc_x1000", "additive_top")
+
+    def fingerprint_scalars(self):
+        """The kernel-choosing scalars at the end of fingerprint(), by name."""
+        fp = self.fingerprint()
+        k = len(self.FINGERPRINT_TAIL)
+        if not k <= len(fp) < 512:
+            raise ValueError("fingerprint truncated: %d words" % len(fp))
+        return dict(zip(self.FINGERPRINT_TAIL, fp[-k:]))
+
     def time_kernel(self, which, reps=20):
         ms = C.c_double(0)
         check(lib().irotavg_graph_time_kernel(self._h, which, reps, C.byref(ms)), "time_kernel")

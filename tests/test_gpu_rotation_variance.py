@@ -72,6 +72,10 @@ def test_dense_path_fixture(fixture_graph):
     I, QQ, n, f, Q0 = fixture_state(fixture_graph)
     with solved_handle(I, QQ, n, f, Q0) as G:
         P = pick_pairs(n, f, np.random.default_rng(0), I)
+        # the seams of the sweep's 64 x 64 tiles: rows 64 k - 1 and 64 k, each pair across its own seam and one across
+        # the whole matrix (entries of tiles next to and far off the diagonal)
+        k = 64 * np.arange(1, (n - f + 63) // 64)
+        P = np.concatenate([P, np.stack([f + k - 1, f + k], 1), np.stack([f + k, f + k[::-1] - 1], 1)]).astype(np.int32)
         r = G.rotation_variance(P)
         d = G.get_weights()
         G.edge_residual()
