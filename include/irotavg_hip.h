@@ -258,7 +258,10 @@ int irotavg_graph_time_kernel(irotavg_graph *g, int which, int reps, double *ms_
  * handle's systems run through the PCG -- nothing else is written), info[1] = levels L, then per level l < L three
  * values: blocks, chunks of eight blocks (= workgroups of its two launches), blocks that come from the level below
  * (fewer than `blocks` only on a mixed level 1, whose other blocks are level-0 blocks no chunk reduced); after the
- * levels one more value: the long-range edges (loop closures) the solver handles by its Woodbury correction. which of
+ * levels the long-range edges (loop closures) the solver handles by its Woodbury correction, then 1 if the level-0
+ * reduction of the handle's most recent assembly + solve (an IRLS iteration, irotavg_graph_ls_solve) assembled level 0
+ * itself -- one launch instead of K3 and the reduction: a handle without closures whose chunks of eight blocks are whole
+ * 64-row slices (blocks of 8 / 16 / 24 / 32), IROTAVG_BCR_NO_FUSED_ASM=1 not set -- and 0 if it did not. which of
  * irotavg_graph_time_kernel: 19 = a whole solve (2 L launches), 20 + l = the reduction of level l, 40 + l = its way
  * back. Returns the number of values written (<= cap) or a negative error. */
 int irotavg_graph_direct_info(irotavg_graph *g, int64_t *info, int cap);

@@ -27,6 +27,7 @@
 
 #include "graph.hpp"
 #include "kernels.hpp"
+#include "asm0w.hpp"
 
 namespace irh {
 // a direct solve with closures is repeated by conjugate gradients on the full operator when its relative residual is above
@@ -930,21 +931,82 @@ __device__ __forceinline__ void bcr_reduce_body(
     bcr_stamp(stamps, 15);
 }
 
-template <int B, int NR, bool L0, bool TOP, int NW>
+// ASM (level 0 of a plain banded handle, 8 B a multiple of 64: ls_solve): the workgroup ASSEMBLES the slices of its
+// chunk first -- K3's body (asm0w.hpp: MODE 0, no level 1) for the 8 B / 64 slices that are exactly the chunk's rows --
+// and then reduces the chunk. What bcr_gather_row reads (values, diagonal and right-hand side of the chunk's own rows)
+// this very workgroup wrote: a workgroup barrier lies in between, no workgroup waits for another, and the launch of
+// k_assemble0w in front of the solve is gone -- with it the fourth round of K3's workgroups (1568 on 512 slots at 100k
+// views), a launch boundary behind 32 MB of dirty values, and a gather from memory (the values are hot in L2 now). The
+// two phases use the same LDS one after the other. The slices under no chunk (the raw blocks of a mixed level 1) are
+// assembled by extra workgroups behind the chunks', one slice each; the upper levels' launch gathers them. Everything K3
+// writes is written as before (the ways back, the edge diagnostics and the residual read it).
+struct BcrAsmArgs {
+    int nch, nsl;
+    long long m, mpad;
+    const uint32_t *slot_eid;
+    const int *tile_e0;
+    const uint32_t *beid;
+    const uint8_t *bflag;
+    const double *wsrc, *er;
+    double *excess, *idg, *bval;
+};
+// (ASM: the kernel itself writes val / diag / rhs -- they are no read-only arguments of its)
+template <bool ASM>
+struct BcrL0Ptr {
+    typedef const double *__restrict__ d;
+    typedef const double4 *__restrict__ d4;
+};
+template <>
+struct BcrL0Ptr<true> {
+    typedef double *d;
+    typedef double4 *d4;
+};
+
+template <int B, int NR, bool L0, bool TOP, int NW, bool ASM = false>
 __global__ __launch_bounds__(NW * 64, (NW == 4 && B <= 24 && NR == 3 ? 2 : 1)) void k_bcr_reduce(
 
-    int nb, int nred, int n, const int *__restrict__ sl_off, const int *__restrict__ col, const double *__restrict__ val,
-    const double *__restrict__ diag, const double4 *__restrict__ rhs, const double *__restrict__ inD,
+    int nb, int nred, int n, const int *__restrict__ sl_off, const int *__restrict__ col, typename BcrL0Ptr<ASM>::d val,
+    typename BcrL0Ptr<ASM>::d diag, typename BcrL0Ptr<ASM>::d4 rhs, const double *__restrict__ inD,
     const double *__restrict__ inR, const double *__restrict__ inXD, const double *__restrict__ inXR,
     const double *__restrict__ inXG, double *__restrict__ W, double *__restrict__ sepD, double *__restrict__ sepR,
     double *__restrict__ extD, double *__restrict__ extR, double *__restrict__ extG, double *__restrict__ xtop, int dbg,
     int nfar, const int *__restrict__ far_i, const int *__restrict__ far_j, int ext0, const int *__restrict__ bptr,
     const int *__restrict__ bghost, const double *__restrict__ bval, const int *__restrict__ ghost_extcol, int place,
     long long *__restrict__ stamps, double *__restrict__ Dinvg, double *__restrict__ topDinv, int *__restrict__ deadctr,
-    int reg) {
-    __shared__ double sDG[16][B * B];
-    __shared__ double sR[9][B * NR];  // slot 0: contribution to the right-hand side of the separator before the chunk
-    __shared__ double sZ[2];
+    int reg, BcrAsmArgs A) {
+    // one buffer: the reduction's blocks, right-hand sides and two flags -- and, before them, K3's window of a slice
+    constexpr int kRed = 16 * B * B + 9 * B * NR + 2, kAsm = ASM ? Asm0wLds<0, false>::doubles : 0;
+    __shared__ double lds[kRed > kAsm ? kRed : kAsm];
+    double(*sDG)[B * B] = reinterpret_cast<double(*)[B * B]>(lds);
+    double(*sR)[B * NR] = reinterpret_cast<double(*)[B * NR]>(lds + 16 * B * B);  // slot 0: contribution to the right-hand side of the separator before the chunk
+    double *sZ = lds + 16 * B * B + 9 * B * NR;
+    if constexpr (ASM) {
+        static_assert(L0 && NR == 3 && (8 * B) % 64 == 0, "a chunk's rows are whole slices");
+        constexpr int SPC = 8 * B / 64;  // slices per chunk
+#define IRH_BCR_ASM_SLICE(sl_)                                                                                           \
+    asm0w_slice<0, false, NW * 64>(sl_, lds, n, A.m, A.mpad, sl_off, A.slot_eid, (const uint8_t *)nullptr, A.tile_e0, bptr, \
+                                   A.beid, A.bflag, A.wsrc, A.er, val, A.excess, diag, A.idg, rhs, A.bval, 0,            \
+                                   (const int *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr,        \
+                                   (double *)nullptr)
+        if ((int)blockIdx.x >= A.nch) {
+            // a slice under no chunk of this level
+            const int sl = A.nch * SPC + ((int)blockIdx.x - A.nch);
+            if (sl < A.nsl) IRH_BCR_ASM_SLICE(sl);
+            return;
+        }
+        for (int k = 0; k < SPC; k++) {
+            const int sl = (int)blockIdx.x * SPC + k;
+            if (sl >= A.nsl) break;
+            IRH_BCR_ASM_SLICE(sl);
+            __syncthreads();  // (the last wave-0 reads of this slice's window and partial sums | the next use of the LDS)
+        }
+#undef IRH_BCR_ASM_SLICE
+        // the chunk's rows are in memory as far as THIS workgroup is concerned (its waves share one L1; a device-scope
+        // release would write back the whole L2): stores issued and complete, then the barrier
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
     bcr_reduce_body<B, NR, L0, TOP, NW, false>(blockIdx.x, sDG, sR, sZ, nb, nred, n, sl_off, col, val, diag, rhs, inD, inR, inXD, inXR,
                                                inXG, W, sepD, sepR, extD, extR, extG, xtop, dbg, nfar, far_i, far_j, ext0, bptr,
                                                bghost, bval, ghost_extcol, place, stamps, Dinvg, topDinv, deadctr, reg);
@@ -2685,9 +2747,33 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
         F ? F->sepR.p : nullptr, F ? F->extD.p : nullptr, F ? F->extR.p : nullptr, F ? F->extG.p : nullptr, L.W.p, \
         L.sepD.p, L.sepR.p, L.extD.p, L.extR.p, L.extG.p, S.xtop.p, dbg, nfar, fi, fj, S.ext0, g.bptr.p, g.bghost.p,  \
         g.bval.p, S.ghost_extcol.p, (int)g.bcr_shard, stamps, S.nfar > 0 ? S.Dinv[(size_t)l].p : (double *)nullptr,         \
-        S.nfar > 0 ? S.topDinv.p : (double *)nullptr, S.nfar > 0 ? S.dead.p : (int *)nullptr, (int)g.bcr_guard
+        S.nfar > 0 ? S.topDinv.p : (double *)nullptr, S.nfar > 0 ? S.dead.p : (int *)nullptr, (int)g.bcr_guard, asmA
         // eight waves per chunk when every chunk has a CU to itself (see k_bcr_reduce)
         const bool wide = L.nch <= 256;
+        // level 0 assembles its own slices first (ls_solve asked): the chunks' workgroups, then one per slice under no chunk
+        BcrAsmArgs asmA{};
+        bool asm0 = false;
+        if constexpr (NR == 3 && (8 * B) % 64 == 0) {
+            asm0 = l == 0 && g.bcr_asm_fused && only < 0 && phase == 0 && !open_top && S.nfar == 0 && !g.bcr_shard;
+            if (asm0) {
+                asmA = BcrAsmArgs{L.nch,   L0.nsl,    (long long)g.m, (long long)g.mpad, g.slot_eid.p, g.tile_e0.p, g.beid.p,
+                                  g.bflag.p, g.bcr_wsrc, g.er.p,         L0.excess.p,       L0.idg.p,     g.bval.p};
+                const int extra = std::max(0, L0.nsl - L.nch * (8 * B / 64));
+#define IRH_BCR_LAUNCH_ASM(TOP_)                                                                                          \
+    if (B <= 24 && wide)                                                                                                  \
+        hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, TOP_, (B <= 24 ? 8 : 4), true>), dim3(L.nch + extra),               \
+                           dim3(B <= 24 ? 512 : 256), 0, st, IRH_BCR_ARGS);                                               \
+    else                                                                                                                  \
+        hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, TOP_, 4, true>), dim3(L.nch + extra), dim3(256), 0, st, IRH_BCR_ARGS);
+                if (top) {
+                    IRH_BCR_LAUNCH_ASM(true)
+                } else {
+                    IRH_BCR_LAUNCH_ASM(false)
+                }
+#undef IRH_BCR_LAUNCH_ASM
+            }
+        }
+        if (asm0) continue;
 #define IRH_BCR_LAUNCH(L0_, TOP_)                                                                                   \
     if constexpr (B <= 24) {                                                                                        \
         if (wide)                                                                                                   \
@@ -3031,7 +3117,7 @@ static void bcr_top_reduce_launch(Graph &g, BcrTop &T, double *Dinv, double *top
                        buf + 3 * W * BB + W * BR, buf + 2 * W * BB, T.W.p, (double *)nullptr, (double *)nullptr,
                        (double *)nullptr, (double *)nullptr, (double *)nullptr, T.xtop.p, 0, 0, (const int *)nullptr,
                        (const int *)nullptr, 0, (const int *)nullptr, (const int *)nullptr, nul, (const int *)nullptr, 0,
-                       (long long *)nullptr, Dinv, topDinv, dead, reg);
+                       (long long *)nullptr, Dinv, topDinv, dead, reg, BcrAsmArgs{});
 }
 template <int B>
 static void bcr_top_back_launch(Graph &g, BcrTop &T) {
@@ -3310,6 +3396,7 @@ int bcr_info(Graph &g, int64_t *out, int cap) {
         put(L.nred);
     }
     put(g.bcr->nfar);
+    put(g.bcr_asm_fused_last ? 1 : 0);  // the most recent assembly + solve (ls_solve) was ONE launch at level 0
     return k;
 }
 

@@ -142,6 +142,10 @@ struct Graph {
     int bcr_up_held = 0;  // 1/1024ths of the device reserved for k_bcr_reduce_up's workgroups (bcr_up_reserve)
     bool pool_headroom = false;  // allocations made for this handle ask the device pool for half as much again (resident.hip)
     bool bcr_no_fused_up = false;  // a wait inside k_bcr_reduce_up gave up once (bcr_up_failed): level by level from then on
+    // ls_solve on a plain banded handle: the level-0 reduction assembles its own slices first (K3 inside k_bcr_reduce,
+    // bcr_run) instead of a launch of k_assemble0w in front of it. bcr_asm_fused: asked of the solve that follows;
+    // bcr_asm_fused_last: what the most recent ls_solve did (irotavg_graph_direct_info)
+    bool bcr_asm_fused = false, bcr_asm_fused_last = false;
     std::unique_ptr<BcrState, BcrDeleter> bcr;
     std::vector<int> bcr_far_i, bcr_far_j, bcr_far_e;  // long-range edges (rows, edge id): Woodbury correction
     const double *bcr_wsrc = nullptr;                  // per-edge weights of the last assembly and whether the
