@@ -389,6 +389,32 @@ int irotavg_window_solve_batch_dev(int64_t nb, const int32_t *sizes, const int32
                                    double sigma, int l1_iters, int irls_iters, double change_th, double *weights_dev,
                                    int32_t *results, int kernel, void *stream);
 
+/* irotavg_window_uncertainty for many small problems in one call, on arrays that live on the device
+ * (docs/window_uncertainty_batch.md): one workgroup per problem, ONE launch. sizes, packing, limits, the stride rule,
+ * alignment and the lowest / highest-element check are those of irotavg_window_solve_batch_dev, so the Q_dev and
+ * weights_dev it leaves can be passed on as they are; Q_dev is only read.
+ *   weights_dev  sum(m) contiguous doubles, or NULL for the weights of the poses (see irotavg_window_uncertainty)
+ *   var_dev      sum(n_total) contiguous doubles or NULL; 0 for fixed views
+ *   npairs       HOST, nb counts or NULL (no pairs); problem b's pairs are the rows sum_{a<b} npairs_a .. of pairs_dev
+ *                (pairs of int32 view ids LOCAL to the problem, 8-byte aligned) and pair_var_dev
+ *   edge_var_dev / leverage_dev / chi2_dev  sum(m) contiguous doubles each, or NULL
+ *   scale        HOST, nb doubles or NULL; results: HOST, nb statuses or NULL
+ * IROTAVG_ERR_BAD_ARG before any device work: what irotavg_window_solve_batch_dev refuses of nb, sizes, pointers, strides
+ * and alignment, a negative pair count, pairs counted without both pair arrays, or nothing asked for (no output array, no
+ * pairs, no scale); no HIP device: IROTAVG_ERR_NO_DEVICE. Edge and pair ids are read on the device alone: the workgroup
+ * of a problem with an id outside [0, n_total) reports IROTAVG_ERR_BAD_ARG and indexes nothing with it; a singular
+ * problem reports IROTAVG_ERR_SOLVER. A problem that fails leaves its rows of every output array, and its entry of
+ * scale, exactly as they were; the other problems are computed. The launch goes on `stream` itself: inputs may still be
+ * in flight there, outputs are ready for whatever is enqueued on it next. The call blocks until every result record has
+ * arrived and returns the first non-zero status in problem order. Results are bitwise those of
+ * irotavg_window_uncertainty on each problem alone. */
+int irotavg_window_uncertainty_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                         int64_t qq_rs, int64_t qq_cs, const double *Q_dev, int64_t q_rs, int64_t q_cs,
+                                         const double *weights_dev, double sigma, double *var_dev, const int32_t *npairs,
+                                         const int32_t *pairs_dev, double *pair_var_dev, double *edge_var_dev,
+                                         double *leverage_dev, double *chi2_dev, double *scale, int32_t *results,
+                                         void *stream);
+
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash
  * each, followed by the scalars that choose kernels (level shapes, far-entry count, fused-assembly / two-launch
@@ -511,6 +537,25 @@ int irotavg_window_solve_kernel(int64_t m, int64_t n_total, int f, const int32_t
                                 int64_t ldqq, double *Q, int64_t ldq, int cost, double sigma,
                                 int l1_iters, int irls_iters, double change_th, double *weights,
                                 int *l1_out, int *irls_out, int kernel);
+
+/* The uncertainty of one window-size problem on caller data (layout as irotavg_window_solve; host pointers), no handle:
+ * one kernel launch (irotavg_amd/csrc/wincov.hip, docs/window_uncertainty_batch.md). Sigma = (A' diag(d^2) A)^-1 with
+ *   weights != NULL  d_k = weights[k], as irotavg_irls / irotavg_window_solve return them (sigma unused);
+ *   weights == NULL  d_k = 1 / (|r_k|^2 + sigma^2), the Geman-McClure weight of the poses Q at a zero step: what the
+ *                    view-graph queries use.
+ * Residuals r_k are K1's at Q either way (scale and chi2 need them). Outputs, each optional:
+ *   var       n_total entries, 0 for the fixed views, as irotavg_graph_rotation_variance
+ *   pair_var  npairs entries, u' Sigma u of (pairs[2t], pairs[2t+1]) (view ids of the problem): 0 when i == j or both
+ *             are fixed
+ *   edge_var / leverage / chi2  m entries each, scale: as irotavg_graph_edge_diagnostics defines them
+ * IROTAVG_ERR_BAD_ARG before any device work: a problem beyond the limits of irotavg_window_solve, f outside
+ * [0, n_total), an edge or pair id outside [0, n_total), npairs < 0, npairs > 0 without both pair arrays, or nothing
+ * asked for (no output pointer and no pairs). IROTAVG_ERR_SOLVER: A' diag(d^2) A is singular. In both cases no output
+ * is written. Results are deterministic: two identical calls are bitwise equal. */
+int irotavg_window_uncertainty(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq,
+                               const double *Q, int64_t ldq, const double *weights /* m or NULL */, double sigma,
+                               double *var /* n_total or NULL */, int64_t npairs, const int32_t *pairs, double *pair_var,
+                               double *edge_var, double *leverage, double *chi2 /* m each or NULL */, double *scale);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-GPU: the IRLS solve sharded by contiguous ranges of free views; one

@@ -48,6 +48,7 @@ SYMBOLS = [
     "irotavg_graph_create_dev", "irotavg_graph_set_rotations_dev", "irotavg_graph_get_rotations_dev",
     "irotavg_graph_set_weights_dev", "irotavg_graph_get_weights_dev", "irotavg_graph_get_residuals_dev",
     "irotavg_graph_rotation_variance_dev", "irotavg_graph_edge_diagnostics_dev", "irotavg_window_solve_batch_dev",
+    "irotavg_window_uncertainty", "irotavg_window_uncertainty_batch_dev",
 ]
 
 
@@ -169,6 +170,9 @@ def lib():
     L.irotavg_window_solve_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp, C.c_int64,
                                                  C.c_int64, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, vp,
                                                  C.POINTER(C.c_int32), C.c_int, vp]
+    L.irotavg_window_uncertainty_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp,
+                                                       C.c_int64, C.c_int64, vp, C.c_double, vp, C.POINTER(C.c_int32), vp,
+                                                       vp, vp, vp, vp, _dp, C.POINTER(C.c_int32), vp]
     L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
     L.irotavg_viewgraph_num_connections.restype = C.c_int64
@@ -195,6 +199,8 @@ def lib():
     L.irotavg_window_solve_kernel.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64,
                                        C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, _dp,
                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    L.irotavg_window_uncertainty.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
+                                             C.c_double, _dp, C.c_int64, _ip, _dp, _dp, _dp, _dp, _dp]
     L.irotavg_trim_memory.argtypes = []
     L.irotavg_trim_memory.restype = C.c_int64
     L.irotavg_oneshot_cache.argtypes = [C.c_int]
@@ -547,6 +553,33 @@ def window_solve(I, QQ, Q, f, cost=4, sigma=5 * np.pi / 180, l1_iters=100, irls_
     check(rc, "irotavg_window_solve")
     return dict(Q=Q, weights=w, l1_iters=a.value, irls_iters=b.value)
 
+
+def window_uncertainty(I, QQ, Q, f, weights=None, sigma=5 * np.pi / 180, pairs=None, marginals=True, edge_var=True,
+                       leverage=True, chi2=True, allow_rc=()):
+    """irotavg_window_uncertainty: pose variances, pair variances, edge diagnostics and the scale of a window-size
+    problem in one kernel launch, no handle. weights: the m weights irls / window_solve returned, or None for the
+    Geman-McClure weights of the poses Q at `sigma` (the view-graph definition). Returns dict(rc, var (n_total, 0 for
+    fixed views), pair_var, edge_var, leverage, chi2, scale); an output that was not asked for is None. Arrays are
+    preset to NaN and written only on success."""
+    I = edges(I)
+    QQ = fmat(QQ)
+    Q = fmat(Q)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if w is not None and w.shape != (len(I),):
+        raise ValueError("weights must have %d entries" % len(I))
+    P = np.zeros((0, 2), dtype=np.int32) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    n_total = Q.shape[0]
+    var = np.full(n_total, np.nan) if marginals else None
+    pv = np.full(max(len(P), 1), np.nan)
+    out = [np.full(len(I), np.nan) if want else None for want in (edge_var, leverage, chi2)]
+    scale = C.c_double(np.nan)
+    rc = lib().irotavg_window_uncertainty(len(I), n_total, int(f), _i(I), _d(QQ), QQ.shape[0], _d(Q), n_total,
+                                          None if w is None else _d(w), float(sigma), None if var is None else _d(var),
+                                          len(P), _i(P) if len(P) else None, _d(pv) if len(P) else None,
+                                          *[None if a is None else _d(a) for a in out], C.byref(scale))
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_window_uncertainty")
+    return dict(rc=rc, var=var, pair_var=pv[:len(P)], edge_var=out[0], leverage=out[1], chi2=out[2], scale=scale.value)
 
 def plan_host(world, rank, I, n_total, f):
     """Host-only partition plan of one rank (irotavg_dist_plan_host): dict with the owned range,

@@ -4,9 +4,11 @@
 #include <cmath>
 #include <mutex>
 #include <new>
+#include <vector>
 
 #include "graph.hpp"
 #include "marginals.hpp"
+#include "winbatch.hpp"  // the limits and the "nothing asked for" rule of irotavg_window_uncertainty
 
 using namespace irh;
 
@@ -892,6 +894,66 @@ int irotavg_edge_diagnostics(int64_t m, int64_t n_total, int f, const int32_t *I
     // (a handle the query refused is as good as before: it is kept like a successful one)
     oneshot_close(h, key, cached, rc == IROTAVG_ERR_UNSUPPORTED || rc == IROTAVG_ERR_SOLVER ? IROTAVG_OK : rc);
     return rc;
+}
+
+// The uncertainty queries of one window-size problem on caller arrays, no handle: one launch of k_window_cov (wincov.hip),
+// the counterpart of irotavg_window_solve and what irotavg_window_uncertainty_batch_dev is bitwise equal to per problem.
+int irotavg_window_uncertainty(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq,
+                               const double *Q, int64_t ldq, const double *weights, double sigma, double *var, int64_t npairs,
+                               const int32_t *pairs, double *pair_var, double *edge_var, double *leverage, double *chi2,
+                               double *scale) {
+    if (!I || !QQ || !Q || m <= 0 || m > WIN_MAX_NE || n_total <= 0 || n_total > WIN_MAX_NV || ldqq < m || ldq < n_total ||
+        f < 0 || f >= n_total || !window_fits((int)n_total, f, (int)m))
+        return IROTAVG_ERR_BAD_ARG;
+    if (npairs > 0x7fffffffLL || !wincov_asked(var, npairs, pairs && pair_var, edge_var, leverage, chi2, scale))
+        return IROTAVG_ERR_BAD_ARG;
+    // the kernel indexes LDS with the endpoints and the pair rows unguarded on this route
+    for (int64_t k = 0; k < 2 * m; k++)
+        if (I[k] < 0 || I[k] >= n_total) return IROTAVG_ERR_BAD_ARG;
+    for (int64_t k = 0; k < 2 * npairs; k++)
+        if (pairs[k] < 0 || pairs[k] >= n_total) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    API_TRY
+    const int nu = (int)n_total - f;
+    std::vector<double> qa((size_t)4 * m), Qa((size_t)4 * n_total), varl((size_t)nu), pv((size_t)npairs);
+    for (int64_t k = 0; k < m; k++)
+        for (int c = 0; c < 4; c++) qa[(size_t)4 * k + c] = QQ[(size_t)c * ldqq + k];
+    for (int64_t r = 0; r < n_total; r++)
+        for (int c = 0; c < 4; c++) Qa[(size_t)4 * r + c] = Q[(size_t)c * ldq + r];
+    // operator rows of the pairs (-1: a fixed view); i == j is u = 0
+    std::vector<int32_t> prow((size_t)2 * npairs);
+    for (int64_t t = 0; t < npairs; t++) {
+        const int32_t i = pairs[2 * t], j = pairs[2 * t + 1];
+        prow[2 * t] = i == j || i < f ? -1 : i - f;
+        prow[2 * t + 1] = i == j || j < f ? -1 : j - f;
+    }
+    WinCovQuery q{};
+    q.nv = (int)n_total;
+    q.f = f;
+    q.ne = (int)m;
+    q.I = I;
+    q.qq_aos = qa.data();
+    q.Q_aos = Qa.data();
+    q.sigma = sigma;
+    q.weights = weights;
+    q.var = var ? varl.data() : nullptr;
+    q.edge_var = edge_var;
+    q.leverage = leverage;
+    q.chi2 = chi2;
+    q.np = (int)npairs;
+    q.prow = prow.data();
+    q.pair_var = pv.data();
+    struct Owner {
+        WinCov *w = wincov_new();
+        ~Owner() { wincov_delete(w); }
+    } own;
+    const int rc = wincov_query(*own.w, q);
+    if (rc != IROTAVG_OK) return rc;  // outputs untouched
+    for (int64_t r = 0; var && r < n_total; r++) var[r] = r < f ? 0.0 : varl[(size_t)(r - f)];
+    for (int64_t t = 0; t < npairs; t++) pair_var[t] = pv[(size_t)t];
+    if (scale) *scale = q.s2;
+    return IROTAVG_OK;
+    API_CATCH
 }
 
 // replaces irotavg::quat_normalised for host-resident rows: Eigen normalized() per row

@@ -157,6 +157,20 @@ bool dev_matrix_ok(const double *p, int64_t rows, int cols, int64_t rs, int64_t 
 }
 bool dev_vector_ok(const double *p, int64_t n, int device) { return dev_matrix_ok(p, n, 1, 1, 1, device); }
 
+// the checks irotavg_window_solve_batch_dev and irotavg_window_uncertainty_batch_dev make of the packed problem arrays
+// before any device work (alignment, the stride rule), and with a device (the lowest and the highest element of each)
+bool win_arrays_host_ok(const void *I, const double *QQ, int64_t qq_rs, int64_t qq_cs, const double *Q, int64_t q_rs,
+                        int64_t q_cs, const double *w, int64_t sum_m, int64_t sum_n) {
+    return (reinterpret_cast<uintptr_t>(I) & 7) == 0 && (reinterpret_cast<uintptr_t>(QQ) & 7) == 0 &&
+           (reinterpret_cast<uintptr_t>(Q) & 7) == 0 && (reinterpret_cast<uintptr_t>(w) & 7) == 0 &&
+           strides_ok(sum_m, 4, qq_rs, qq_cs) && strides_ok(sum_n, 4, q_rs, q_cs);
+}
+bool win_arrays_dev_ok(const int32_t *I, const double *QQ, int64_t qq_rs, int64_t qq_cs, const double *Q, int64_t q_rs,
+                       int64_t q_cs, const double *w, int64_t sum_m, int64_t sum_n, int device) {
+    return dev_ptr_ok(I, device) && dev_ptr_ok(I + 2 * sum_m - 1, device) && dev_matrix_ok(QQ, sum_m, 4, qq_rs, qq_cs, device) &&
+           dev_matrix_ok(Q, sum_n, 4, q_rs, q_cs, device) && (!w || dev_vector_ok(w, sum_m, device));
+}
+
 // the ordering contract of a call on an existing handle
 struct Ordered {
     Graph &g;
@@ -359,22 +373,56 @@ int irotavg_window_solve_batch_dev(int64_t nb, const int32_t *sizes, const int32
     return guarded([&]() -> int {
         WinBatchPlan plan;
         if (!winbatch_plan(nb, sizes, kernel, plan)) return IROTAVG_ERR_BAD_ARG;
-        if ((reinterpret_cast<uintptr_t>(I_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(QQ_dev) & 7) != 0 ||
-            (reinterpret_cast<uintptr_t>(Q_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(weights_dev) & 7) != 0 ||
-            !strides_ok(plan.sum_m, 4, qq_rs, qq_cs) || !strides_ok(plan.sum_n, 4, q_rs, q_cs))
+        if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n))
             return IROTAVG_ERR_BAD_ARG;
         if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
         int device = 0;
         IRH_CHECK(hipGetDevice(&device));
-        if (!dev_ptr_ok(I_dev, device) || !dev_ptr_ok(I_dev + 2 * plan.sum_m - 1, device) ||
-            !dev_matrix_ok(QQ_dev, plan.sum_m, 4, qq_rs, qq_cs, device) ||
-            !dev_matrix_ok(Q_dev, plan.sum_n, 4, q_rs, q_cs, device) ||
-            (weights_dev && !dev_vector_ok(weights_dev, plan.sum_m, device)))
+        if (!win_arrays_dev_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n, device))
             return IROTAVG_ERR_BAD_ARG;
         const WinBatchArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
                                weights_dev};
         return window_solve_batch_dev(plan, device, A, cost, sigma, l1_iters, irls_iters, change_th, results,
                                       static_cast<hipStream_t>(stream));
+    });
+}
+
+// The uncertainty of many small problems on packed device arrays, one workgroup each, one launch
+// (docs/window_uncertainty_batch.md). Handle-free and on the caller's stream itself, as irotavg_window_solve_batch_dev.
+int irotavg_window_uncertainty_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                         int64_t qq_rs, int64_t qq_cs, const double *Q_dev, int64_t q_rs, int64_t q_cs,
+                                         const double *weights_dev, double sigma, double *var_dev, const int32_t *npairs,
+                                         const int32_t *pairs_dev, double *pair_var_dev, double *edge_var_dev,
+                                         double *leverage_dev, double *chi2_dev, double *scale, int32_t *results, void *stream) {
+    if (!I_dev || !QQ_dev || !Q_dev) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        WinCovPlan plan;
+        if (!wincov_plan(nb, sizes, npairs, plan)) return IROTAVG_ERR_BAD_ARG;
+        if (!wincov_asked(var_dev, plan.sum_p, pairs_dev && pair_var_dev, edge_var_dev, leverage_dev, chi2_dev, scale))
+            return IROTAVG_ERR_BAD_ARG;
+        if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n))
+            return IROTAVG_ERR_BAD_ARG;
+        double *const per_edge[3] = {edge_var_dev, leverage_dev, chi2_dev};
+        for (double *p : per_edge)
+            if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return IROTAVG_ERR_BAD_ARG;
+        if ((reinterpret_cast<uintptr_t>(var_dev) & 7) != 0 ||
+            (plan.sum_p > 0 && ((reinterpret_cast<uintptr_t>(pairs_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(pair_var_dev) & 7) != 0)))
+            return IROTAVG_ERR_BAD_ARG;
+        if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!win_arrays_dev_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n, device))
+            return IROTAVG_ERR_BAD_ARG;
+        for (double *p : per_edge)
+            if (p && !dev_vector_ok(p, plan.sum_m, device)) return IROTAVG_ERR_BAD_ARG;
+        if (var_dev && !dev_vector_ok(var_dev, plan.sum_n, device)) return IROTAVG_ERR_BAD_ARG;
+        if (plan.sum_p > 0 && (!dev_ptr_ok(pairs_dev, device) || !dev_ptr_ok(pairs_dev + 2 * plan.sum_p - 1, device) ||
+                               !dev_vector_ok(pair_var_dev, plan.sum_p, device)))
+            return IROTAVG_ERR_BAD_ARG;
+        const WinCovArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
+                             weights_dev, var_dev, plan.sum_p > 0 ? pairs_dev : nullptr, plan.sum_p > 0 ? pair_var_dev : nullptr,
+                             edge_var_dev, leverage_dev, chi2_dev};
+        return wincov_batch_dev(plan, device, A, sigma, scale, results, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -331,6 +331,7 @@ struct WinCovQuery {
     const int32_t *I;               // ne pairs of rows
     const double *qq_aos, *Q_aos;   // 4 per edge / per view, [x y z w]
     double sigma;
+    const double *weights;          // ne weights d_k as irls returns them, or nullptr: d_k = 1 / (|r_k|^2 + sigma^2)
     double *var;                    // OUT nv - f (or nullptr)
     double *edge_var, *leverage, *chi2;  // OUT ne each (or nullptr)
     int np;
@@ -343,6 +344,23 @@ struct WinCovQuery {
     double s2;                      // OUT
 };
 int wincov_query(WinCov &wc, WinCovQuery &q);  // IROTAVG_ERR_SOLVER: singular, outputs untouched
+// the batched form on the caller's DEVICE arrays (irotavg_window_uncertainty_batch_dev; plan: winbatch.hpp), packed as
+// WinBatchArrays; pairs = sum(npairs) pairs of view ids local to their problem; every output may be nullptr
+struct WinCovPlan;
+struct WinCovArrays {
+    const int32_t *I;
+    const double *QQ;
+    long long qq_rs, qq_cs;
+    const double *Q;
+    long long q_rs, q_cs;
+    const double *weights;  // or nullptr: the weights of the poses
+    double *var;            // OUT sum(n_total), 0 for fixed views
+    const int32_t *pairs;
+    double *pair_var;       // OUT sum(npairs)
+    double *edge_var, *leverage, *chi2;  // OUT sum(m) each
+};
+int wincov_batch_dev(const WinCovPlan &plan, int device, const WinCovArrays &A, double sigma, double *scale /* host */,
+                     int32_t *results /* host */, hipStream_t stream);
 // solver.hip: K1 + the robust weight at a zero step in one pass over the edges (irotavg_graph_pose_weights); the residual
 // norms of free-standing measurements (lower view, higher view, relative rotation: 3 quaternions each)
 void launch_pose_weights(Graph &g, int cost, double sigma);

@@ -1,5 +1,6 @@
-// winbatch.hpp -- the host arithmetic of the window kernels and of irotavg_window_solve_batch_dev: size limits, the
-// staging layout, the stride rule of the `_dev` API, and the plan of a batch (offsets and descriptors from `sizes`). Plain C++ with no HIP
+// winbatch.hpp -- the host arithmetic of the window kernels, of irotavg_window_solve_batch_dev and of
+// irotavg_window_uncertainty_batch_dev: size limits, the staging layout, the stride rule of the `_dev` API, the plan of a
+// batch (offsets and descriptors from `sizes`), the LDS layout and the pair offsets of the uncertainty kernels. Plain C++ with no HIP
 // type in it, so that a stand-alone program can run all of it under a sanitizer on a machine without a device
 // (tools/winbatch_host_check.cpp).
 #pragma once
@@ -129,6 +130,70 @@ inline bool winbatch_plan(int64_t nb, const int32_t *sizes, int kernel, WinBatch
     out.sum_m = eoff;
     out.sum_n = voff;
     return true;
+}
+
+// ---- the uncertainty of such problems: k_window_cov / k_window_cov_user (wincov.hip), irotavg_window_uncertainty[_batch_dev]
+constexpr int WINCOV_THREADS = 256;
+constexpr int WINCOV_LD = WIN_MAX_NU + 1;  // row stride of M in LDS (bank spread), whatever the problem's nu
+// dynamic LDS of one workgroup, in bytes from its base: the quaternions, (stage: the measurements, as WinIoUser keeps
+// them,) per edge the residual and the weight, M, the endpoints, three vectors of nu, the reduction scratch
+struct WinCovLds {
+    size_t oQ, oQQ, oR, oM, oI, oSc, oCol, oRow, oRed, bytes;
+};
+constexpr WinCovLds wincov_lds(int nv, int ne, int nu, bool stage) {
+    const size_t oQQ = 32 * (size_t)nv, oR = oQQ + (stage ? 32 * (size_t)ne : 0), oM = oR + 32 * (size_t)ne;
+    const size_t oI = oM + sizeof(double) * (size_t)nu * WINCOV_LD, oSc = oI + 8 * (size_t)ne;
+    const size_t oCol = oSc + sizeof(double) * (size_t)nu, oRow = oCol + sizeof(double) * (size_t)nu;
+    const size_t oRed = oRow + sizeof(double) * (size_t)nu;
+    return WinCovLds{0, oQQ, oR, oM, oI, oSc, oCol, oRow, oRed, oRed + sizeof(double) * 2 * WINCOV_THREADS};
+}
+static_assert(wincov_lds(WIN_MAX_NV, WIN_MAX_NE, WIN_MAX_NU, true).bytes <= WIN_MAX_LDS,
+              "every term grows with its size: a problem inside the limits fits");
+
+// what a workgroup of the uncertainty kernels leaves: the sequence number last, as WinResult::seq
+struct WinCovResult {
+    int status, seq;
+    double s2;
+};
+// one problem of irotavg_window_uncertainty_batch_dev: the solve's descriptor, then its pairs in the packed pair arrays
+struct WinCovDesc {
+    WinDesc d;
+    long long poff;
+    int np, pad;
+};
+struct WinCovPlan {
+    std::vector<WinCovDesc> desc;  // in the caller's order
+    int64_t sum_m = 0, sum_n = 0, sum_p = 0;
+    size_t lds = 0;  // largest wincov_lds(..., true).bytes of the batch
+};
+// sizes as winbatch_plan takes them (the same limits); npairs: nb counts or nullptr (no pairs anywhere).
+// false: what winbatch_plan refuses, or a negative pair count.
+inline bool wincov_plan(int64_t nb, const int32_t *sizes, const int32_t *npairs, WinCovPlan &out) {
+    WinBatchPlan base;
+    if (!winbatch_plan(nb, sizes, 1, base)) return false;  // kernel 1: one list, in the caller's order
+    for (int64_t b = 0; npairs && b < nb; b++)
+        if (npairs[b] < 0) return false;
+    out.desc.assign((size_t)nb, WinCovDesc{});
+    out.lds = 0;
+    int64_t poff = 0;
+    for (int64_t b = 0; b < nb; b++) {
+        const WinDesc &d = base.desc[(size_t)b];
+        const int np = npairs ? npairs[b] : 0;
+        out.desc[(size_t)b] = WinCovDesc{d, (long long)poff, np, 0};
+        const size_t l = wincov_lds(d.nv, d.ne, d.nv - d.f, true).bytes;
+        if (l > out.lds) out.lds = l;
+        poff += np;
+    }
+    out.sum_m = base.sum_m;
+    out.sum_n = base.sum_n;
+    out.sum_p = poff;
+    return true;
+}
+// A query must ask for something: pose variances, pair variances, an edge output or the scale. (Pairs are asked for by
+// a positive count; the count needs both of its arrays.)
+inline bool wincov_asked(bool var, int64_t pairs, bool pair_arrays, bool edge_var, bool leverage, bool chi2, bool scale) {
+    if (pairs < 0 || (pairs > 0 && !pair_arrays)) return false;
+    return var || pairs > 0 || edge_var || leverage || chi2 || scale;
 }
 
 }  // namespace irh

@@ -14,6 +14,7 @@
 #include "graph.hpp"
 #include "kernels.hpp"
 #include "winbatch.hpp"  // the size limits (WIN_MAX_*, SM_MAX_*), win_lds_bytes, WinParams / WinResult, the staging layout, the plan of a batch
+#include "winio.hpp"     // ld_row / st_row
 
 namespace irh {
 
@@ -54,30 +55,7 @@ struct WinIoOwn {  // the library's own staging block: one double4 per row, ever
     __device__ __forceinline__ void put_q(int i, const double4 &v) const { Q[i] = v; }
     __device__ __forceinline__ void put_w(int k, double v) const { w[k] = v; }
 };
-// 8-byte accesses through (rs, cs); 16-byte ones only for contiguous rows behind a 16-byte aligned pointer (aos). Never
-// a double4 access: packed offsets and tensor views give no 32-byte alignment.
-__device__ __forceinline__ double4 ld_row(const double *p, long long rs, long long cs, long long row, bool aos) {
-    if (aos) {
-        const double2 *h = reinterpret_cast<const double2 *>(p + 4 * row);
-        const double2 a = h[0], b = h[1];
-        return make_double4(a.x, a.y, b.x, b.y);
-    }
-    const double *r = p + row * rs;
-    return make_double4(r[0], r[cs], r[2 * cs], r[3 * cs]);
-}
-__device__ __forceinline__ void st_row(double *p, long long rs, long long cs, long long row, bool aos, const double4 &v) {
-    if (aos) {
-        double2 *h = reinterpret_cast<double2 *>(p + 4 * row);
-        h[0] = make_double2(v.x, v.y);
-        h[1] = make_double2(v.z, v.w);
-        return;
-    }
-    double *r = p + row * rs;
-    r[0] = v.x;
-    r[cs] = v.y;
-    r[2 * cs] = v.z;
-    r[3 * cs] = v.w;
-}
+// (a row of the caller's strided arrays: ld_row / st_row, winio.hpp)
 struct WinUser {  // the caller's packed arrays of a batch (kernel argument)
     const int2 *I;
     const double *QQ;

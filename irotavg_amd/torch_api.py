@@ -44,6 +44,13 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _narrow(ids):
+    """int64 ids narrowed on the device: what does not fit becomes -1, an id the kernels' guard refuses."""
+    if ids.dtype == torch.int64:
+        ids = torch.where((ids < 0) | (ids > INT32_MAX), torch.full_like(ids, -1), ids).to(torch.int32)
+    return ids.contiguous()
+
+
 class TorchGraph(capi.Graph):
     """A graph handle built from tensors on the device (irotavg_graph_create_dev). edge_index: (m, 2) int32 or int64
     (narrowed on the device; a value outside int32 range makes the build reject the graph), QQ: (m, 4) float64 with
@@ -60,10 +67,7 @@ class TorchGraph(capi.Graph):
         self.m, self.n_total, self.f = int(edge_index.shape[0]), int(n_total), int(f)
         self.nu = self.n_total - self.f
         with torch.cuda.device(self.device):
-            ei = edge_index
-            if ei.dtype == torch.int64:  # narrowed on the device: what does not fit becomes an index the build rejects
-                ei = torch.where((ei < 0) | (ei > INT32_MAX), torch.full_like(ei, -1), ei).to(torch.int32)
-            ei = ei.contiguous()
+            ei = _narrow(edge_index)  # what does not fit int32 becomes an index the build rejects
             o = capi.default_options(**opts)
             if o.device < 0:
                 o.device = self.device.index
@@ -205,10 +209,7 @@ def window_solve_batch(sizes, edge_index, QQ, Q, cost=4, sigma=5 * 3.14159265358
     nb = len(s32)
     res = np.zeros((nb, 4), dtype=np.int32)
     with torch.cuda.device(device):
-        ei = edge_index
-        if ei.dtype == torch.int64:  # narrowed on the device: what does not fit becomes an id the kernels' guard refuses
-            ei = torch.where((ei < 0) | (ei > INT32_MAX), torch.full_like(ei, -1), ei).to(torch.int32)
-        ei = ei.contiguous()
+        ei = _narrow(edge_index)
         rc = capi.lib().irotavg_window_solve_batch_dev(
             nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(Q),
             *matrix_strides(Q), int(cost), float(sigma), int(l1_iters), int(irls_iters), float(change_th),
@@ -217,3 +218,88 @@ def window_solve_batch(sizes, edge_index, QQ, Q, cost=4, sigma=5 * 3.14159265358
         raise capi.IrotavgError(rc, "irotavg_window_solve_batch_dev")
     return dict(rc=rc, Q=Q, weights=w, status=res[:, 0].copy(), l1_iters=res[:, 1].copy(), irls_iters=res[:, 2].copy(),
                 kernel=res[:, 3].copy())
+
+
+# ---- their uncertainty in one call (irotavg_window_uncertainty_batch_dev, docs/window_uncertainty_batch.md) --------------
+def pair_offsets(npairs, nb):
+    """npairs: host integers, one count per problem (or None: no pairs) -> (counts as contiguous int32, first pair row of
+    every problem, sum): the packing the C call assumes, formed in 64 bits."""
+    import numpy as np
+    if npairs is None:
+        return None, np.zeros(nb, dtype=np.int64), 0
+    if isinstance(npairs, torch.Tensor):
+        if npairs.is_cuda:
+            raise TypeError("npairs must be a host array, got a tensor on %s" % npairs.device)
+        npairs = npairs.numpy()
+    c = np.asarray(npairs)
+    if c.dtype.kind not in "iu":
+        raise TypeError("npairs must be integers, got %s" % c.dtype)
+    if c.shape != (nb,):
+        raise ValueError("npairs must have shape (%d,), got %s" % (nb, c.shape))
+    if c.size and (c.min() < 0 or c.max() > INT32_MAX):
+        raise ValueError("npairs must be counts in int32 range")
+    c64 = c.astype(np.int64)
+    return np.ascontiguousarray(c, dtype=np.int32), np.cumsum(c64) - c64, int(c64.sum())
+
+
+def window_uncertainty_batch(sizes, edge_index, QQ, Q, weights=None, sigma=5 * 3.141592653589793 / 180, pairs=None,
+                             npairs=None, var=True, edge_var=True, leverage=True, chi2=True, allow_rc=()):
+    """The uncertainty of nb independent window-size problems, each as capi.window_uncertainty, one workgroup per problem,
+    in one launch on torch's current stream. sizes, edge_index, QQ, Q: as window_solve_batch takes them (Q is only read).
+
+    weights: a contiguous float64 tensor of sum m entries (what window_solve_batch returned), or None for the
+    Geman-McClure weights of the poses at `sigma`. pairs: (sum npairs, 2) int32 or int64 view ids local to their problem,
+    with npairs the host counts per problem; or None. var / edge_var / leverage / chi2: True (a new tensor, preset to
+    NaN), False / None (not computed), or a contiguous float64 tensor to fill (sum n_total entries for var, sum m for the
+    others). Returns dict(rc, var, pair_var, edge_var, leverage, chi2, scale, status); scale and status are host numpy
+    arrays of nb entries (scale NaN where the problem failed). rc is the first non-zero status in problem order; anything
+    but OK raises unless listed in allow_rc. A problem that fails leaves its rows of every output as they were."""
+    import numpy as np
+    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
+    nb = len(s32)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2), placed=False)
+    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), placed=False)
+    _check(Q, "Q", (torch.float64,), (sum_n, 4), placed=False)
+    if (pairs is None) != (npairs is None):
+        raise ValueError("pairs and npairs go together")
+    np32, _, sum_p = pair_offsets(npairs, nb)
+    if pairs is not None:
+        _check(pairs, "pairs", (torch.int32, torch.int64), (sum_p, 2), placed=False)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), device)
+    _check(Q, "Q", (torch.float64,), (sum_n, 4), device)
+    if pairs is not None:
+        _check(pairs, "pairs", (torch.int32, torch.int64), (sum_p, 2), device)
+
+    def vector(t, name, n):
+        _check(t, name, (torch.float64,), (n,), device)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        return t
+    w = None if weights is None else vector(weights, "weights", sum_m)
+    outs = {}
+    for name, want, n in (("var", var, sum_n), ("edge_var", edge_var, sum_m), ("leverage", leverage, sum_m),
+                          ("chi2", chi2, sum_m)):
+        if want is True:
+            outs[name] = torch.full((n,), float("nan"), dtype=torch.float64, device=device)
+        elif want is False or want is None:
+            outs[name] = None
+        else:
+            outs[name] = vector(want, name, n)
+    pv = torch.full((sum_p,), float("nan"), dtype=torch.float64, device=device) if sum_p else None
+    scale = np.full(nb, np.nan)
+    status = np.zeros(nb, dtype=np.int32)
+    opt = lambda t: None if t is None else _ptr(t)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        pr = _narrow(pairs) if sum_p else None
+        rc = capi.lib().irotavg_window_uncertainty_batch_dev(
+            nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(Q),
+            *matrix_strides(Q), opt(w), float(sigma), opt(outs["var"]),
+            None if np32 is None else np32.ctypes.data_as(C.POINTER(C.c_int32)), opt(pr), opt(pv), opt(outs["edge_var"]),
+            opt(outs["leverage"]), opt(outs["chi2"]), scale.ctypes.data_as(C.POINTER(C.c_double)),
+            status.ctypes.data_as(C.POINTER(C.c_int32)), _stream(device))
+    if rc != capi.OK and rc not in allow_rc:
+        raise capi.IrotavgError(rc, "irotavg_window_uncertainty_batch_dev")
+    return dict(rc=rc, pair_var=pv, scale=scale, status=status, **outs)

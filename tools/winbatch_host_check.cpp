@@ -1,6 +1,6 @@
 // winbatch_host_check.cpp -- the host arithmetic of irotavg_window_solve_batch_dev (irotavg_amd/csrc/winbatch.hpp: size
-// checks, packing offsets, descriptors, the stride rule, the span of a strided matrix and the 16-byte row rule) as a
-// stand-alone program that needs no device, meant to be built with a sanitizer:
+// checks, packing offsets, descriptors, the stride rule, the span of a strided matrix and the 16-byte row rule) and of
+// irotavg_window_uncertainty_batch_dev (pair offsets, the LDS layout, the "nothing asked for" rule) as a stand-alone program that needs no device, meant to be built with a sanitizer:
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -Iirotavg_amd/csrc
 //       tools/winbatch_host_check.cpp -o winbatch_host_check && ./winbatch_host_check
 // Exit status 0 and "winbatch host check ok" when every expectation holds.
@@ -154,6 +154,67 @@ int main() {
     EXPECT(!rows16(0x1000, 1, 4) && !rows16(0x1000, 8, 1) && !rows16(0x1000, 4, 2) && !rows16(0x1000, -4, 1) &&
            !rows16(0x1000, 4, -1) && !rows16(0x1000, 1, 1000) && !rows16(0x1000, lmin, 1) && !rows16(0x1000, 4, lmax));
     EXPECT(rows16(~(uintptr_t)15, 4, 1) && !rows16(~(uintptr_t)7, 4, 1));
+    // ---- the uncertainty batch (irotavg_window_uncertainty_batch_dev): pair offsets, LDS, the "nothing asked for" rule
+    {
+        WinCovPlan C;
+        const int32_t np1[1] = {5}, neg[1] = {-1};
+        EXPECT(!wincov_plan(0, one, nullptr, C) && !wincov_plan(-1, one, np1, C) && !wincov_plan(WIN_BATCH_MAX + 1, one, nullptr, C));
+        EXPECT(!wincov_plan(1, nullptr, np1, C) && !wincov_plan(1, one, neg, C));
+        EXPECT(wincov_plan(1, one, nullptr, C) && C.sum_p == 0 && C.desc[0].np == 0 && C.desc[0].poff == 0);
+        EXPECT(wincov_plan(1, one, np1, C) && C.sum_p == 5 && C.desc[0].np == 5 && C.sum_m == 40 && C.sum_n == 12);
+        EXPECT(C.lds == wincov_lds(12, 40, 10, true).bytes);
+        for (const auto &b : bad) {
+            const int32_t s[9] = {12, 2, 40, b[0], b[1], b[2], 2, 1, 1}, c[3] = {0, 1, 2};
+            EXPECT(!wincov_plan(3, s, c, C) && !wincov_plan(3, s, nullptr, C));
+        }
+        const int32_t s3[9] = {12, 2, 40, 320, 256, 640, 2, 1, 1}, c3[3] = {7, 0, imax}, cneg[3] = {7, imin, 3};
+        EXPECT(!wincov_plan(3, s3, cneg, C));
+        EXPECT(wincov_plan(3, s3, c3, C) && C.sum_p == 7 + (int64_t)imax && C.sum_m == 681 && C.sum_n == 334);
+        EXPECT(C.desc[0].poff == 0 && C.desc[1].poff == 7 && C.desc[2].poff == 7 && C.desc[2].np == imax);
+        EXPECT(C.lds == wincov_lds(320, 640, 64, true).bytes && C.lds <= WIN_MAX_LDS);
+        // random batches: descriptors in the caller's order, offsets the 64-bit cumulative sums
+        std::vector<int32_t> s, c;
+        unsigned r = 777u;
+        auto rnd = [&](int lo, int hi) {
+            r = r * 1664525u + 1013904223u;
+            return lo + (int)((r >> 8) % (unsigned)(hi - lo + 1));
+        };
+        for (int b = 0; b < 3000; b++) {
+            const int nu = rnd(1, 64), f = rnd(0, 320 - nu);
+            int ne = rnd(1, 640);
+            while (!win_fits(nu + f, f, ne)) ne--;
+            s.insert(s.end(), {nu + f, f, ne});
+            c.push_back(b % 3 == 0 ? 0 : rnd(0, 4000000));
+        }
+        EXPECT(wincov_plan(3000, s.data(), c.data(), C) && C.desc.size() == 3000);
+        int64_t e = 0, v = 0, p = 0;
+        size_t lds = 0;
+        for (int b = 0; b < 3000; b++) {
+            const WinCovDesc &d = C.desc[(size_t)b];
+            EXPECT(d.d.idx == b && d.d.nv == s[3 * b] && d.d.f == s[3 * b + 1] && d.d.ne == s[3 * b + 2] && d.np == c[(size_t)b]);
+            EXPECT(d.d.eoff == e && d.d.voff == v && d.poff == p);
+            const WinCovLds L = wincov_lds(d.d.nv, d.d.ne, d.d.nv - d.d.f, true);
+            // the arrays follow each other without overlap; double4 rows on 32 bytes, doubles and id pairs on 8
+            EXPECT(L.oQ == 0 && L.oQQ == 32 * (size_t)d.d.nv && L.oR == L.oQQ + 32 * (size_t)d.d.ne && L.oM == L.oR + 32 * (size_t)d.d.ne);
+            EXPECT(L.oI == L.oM + 8 * (size_t)(d.d.nv - d.d.f) * WINCOV_LD && L.oSc == L.oI + 8 * (size_t)d.d.ne);
+            EXPECT(L.oM % 32 == 0 && L.oI % 8 == 0 && L.oRed % 8 == 0 && L.bytes == L.oRed + 16 * WINCOV_THREADS && L.bytes <= WIN_MAX_LDS);
+            if (L.bytes > lds) lds = L.bytes;
+            e += d.d.ne;
+            v += d.d.nv;
+            p += d.np;
+        }
+        EXPECT(C.sum_m == e && C.sum_n == v && C.sum_p == p && C.lds == lds && p > (int64_t)imax);
+        // the staged kernel's layout: no copy of the measurements, laid out for the limits
+        const WinCovLds O = wincov_lds(WIN_MAX_NV, WIN_MAX_NE, WIN_MAX_NU, false);
+        EXPECT(O.oQQ == O.oR && O.oR == 10240 && O.oM == 30720 && O.oI == 64000 && O.bytes == 74752);
+        // asked for: any one output is enough; pairs need a positive count AND both arrays
+        EXPECT(!wincov_asked(false, 0, false, false, false, false, false) && !wincov_asked(false, 0, true, false, false, false, false));
+        EXPECT(wincov_asked(true, 0, false, false, false, false, false) && wincov_asked(false, 0, false, true, false, false, false));
+        EXPECT(wincov_asked(false, 0, false, false, true, false, false) && wincov_asked(false, 0, false, false, false, true, false));
+        EXPECT(wincov_asked(false, 0, false, false, false, false, true) && wincov_asked(false, 3, true, false, false, false, false));
+        EXPECT(!wincov_asked(true, 3, false, true, true, true, true) && !wincov_asked(true, -1, true, true, true, true, true));
+        EXPECT(!wincov_asked(true, lmin, true, true, true, true, true) && wincov_asked(false, lmax, true, false, false, false, false));
+    }
     if (failures) {
         std::fprintf(stderr, "%d expectation(s) failed\n", failures);
         return 1;
