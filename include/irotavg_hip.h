@@ -415,6 +415,31 @@ int irotavg_window_uncertainty_batch_dev(int64_t nb, const int32_t *sizes, const
                                          double *leverage_dev, double *chi2_dev, double *scale, int32_t *results,
                                          void *stream);
 
+/* The closure gate for many small problems in one call, on arrays that live on the device (docs/window_gate_batch.md):
+ * irotavg_window_gate on every problem, one workgroup per problem, ONE launch. nb .. sigma are exactly those of
+ * irotavg_window_uncertainty_batch_dev (Q_dev is only read), so the Q_dev and weights_dev a batched solve leaves can be
+ * passed on as they are.
+ *   ncand        HOST, nb counts (each >= 0; no cap per problem); problem b's candidates are the rows
+ *                sum_{a<b} ncand_a .. of cand_I_dev, cand_QQ_dev and the three outputs (offsets formed in 64 bits)
+ *   cand_I_dev   sum(ncand) pairs of int32 view ids LOCAL to the problem, 8-byte aligned
+ *   cand_QQ_dev  strided sum(ncand) x 4 (cq_rs, cq_cs): the stride rule above
+ *   angle_dev / pair_var_dev / chi2_dev  sum(ncand) contiguous doubles each, or NULL
+ *   scale        HOST, nb doubles or NULL; results: HOST, nb statuses or NULL
+ * IROTAVG_ERR_BAD_ARG before any device work: what irotavg_window_uncertainty_batch_dev refuses of the shared arguments, a
+ * negative count, candidates counted without both candidate arrays, a pointer / stride / alignment of the candidate
+ * arrays the rules refuse, or nothing asked for (no candidates and no scale, or no output pointer at all); no HIP
+ * device: IROTAVG_ERR_NO_DEVICE. Edge and candidate ids are read on the device alone: the workgroup of a problem with an
+ * id outside [0, n_total), or a candidate with i == j, reports IROTAVG_ERR_BAD_ARG and indexes nothing with it; a
+ * singular problem (also: a candidate pair_var that is not finite) reports IROTAVG_ERR_SOLVER. A problem that fails leaves
+ * its rows of the three outputs, and its entry of scale, exactly as they were; the other problems are computed. The
+ * launch goes on `stream` itself; the call blocks until every result record has arrived and returns the first non-zero
+ * status in problem order. Results are bitwise those of irotavg_window_gate on each problem alone. */
+int irotavg_window_gate_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                  int64_t qq_rs, int64_t qq_cs, const double *Q_dev, int64_t q_rs, int64_t q_cs,
+                                  const double *weights_dev, double sigma, const int32_t *ncand, const int32_t *cand_I_dev,
+                                  const double *cand_QQ_dev, int64_t cq_rs, int64_t cq_cs, double *angle_dev,
+                                  double *pair_var_dev, double *chi2_dev, double *scale, int32_t *results, void *stream);
+
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash
  * each, followed by the scalars that choose kernels (level shapes, far-entry count, fused-assembly / two-launch
@@ -556,6 +581,26 @@ int irotavg_window_uncertainty(int64_t m, int64_t n_total, int f, const int32_t 
                                const double *Q, int64_t ldq, const double *weights /* m or NULL */, double sigma,
                                double *var /* n_total or NULL */, int64_t npairs, const int32_t *pairs, double *pair_var,
                                double *edge_var, double *leverage, double *chi2 /* m each or NULL */, double *scale);
+
+/* The closure gate of one window-size problem on caller data (layout and weights as irotavg_window_uncertainty; host
+ * pointers), no handle (docs/window_gate_batch.md). A candidate is a row one could append to I / QQ: view ids (i, j) =
+ * (cand_I[2c], cand_I[2c+1]) of the problem and the quaternion [x y z w] in row c of cand_QQ (column-major, leading
+ * dimension ldcq), read exactly as an edge row is read. It is a new, independent measurement, also when the pair has an
+ * edge already; nothing is added to the problem.
+ *   angle[c]     |r_c|, r_c = K1's residual of the candidate at Q
+ *   pair_var[c]  u' Sigma u, u = e_j - e_i; a fixed view (< f) contributes no coefficient, both fixed: 0
+ *   chi2[c]      |r_c|^2 / (s^2 (pair_var[c] + sigma^4)), s^2 the scale of irotavg_window_uncertainty, sigma the argument in
+ *                both weight modes; NaN when s^2 is NaN (angle and pair_var are still given)
+ * ncand entries each, or NULL; scale: one double or NULL. IROTAVG_ERR_BAD_ARG before any device work: what
+ * irotavg_window_uncertainty refuses of the problem, ncand < 0, ncand > 0 without cand_I / cand_QQ (or ldcq < ncand), a
+ * candidate id outside [0, n_total) or i == j, or nothing asked for (no candidates and no scale, or no output pointer at
+ * all). IROTAVG_ERR_SOLVER: A' diag(d^2) A is singular. In both cases no output is written. More than 256 candidates take
+ * further launches of the same kernel; the candidates are staged on the host first (96 bytes each), so a count that memory
+ * cannot hold ends as IROTAVG_ERR_NOMEM. Two identical calls are bitwise equal. */
+int irotavg_window_gate(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, const double *Q,
+                        int64_t ldq, const double *weights /* m or NULL */, double sigma, int64_t ncand,
+                        const int32_t *cand_I, const double *cand_QQ, int64_t ldcq, double *angle, double *pair_var,
+                        double *chi2 /* ncand each or NULL */, double *scale);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-GPU: the IRLS solve sharded by contiguous ranges of free views; one

@@ -49,6 +49,7 @@ SYMBOLS = [
     "irotavg_graph_set_weights_dev", "irotavg_graph_get_weights_dev", "irotavg_graph_get_residuals_dev",
     "irotavg_graph_rotation_variance_dev", "irotavg_graph_edge_diagnostics_dev", "irotavg_window_solve_batch_dev",
     "irotavg_window_uncertainty", "irotavg_window_uncertainty_batch_dev",
+    "irotavg_window_gate", "irotavg_window_gate_batch_dev",
 ]
 
 
@@ -173,6 +174,9 @@ def lib():
     L.irotavg_window_uncertainty_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp,
                                                        C.c_int64, C.c_int64, vp, C.c_double, vp, C.POINTER(C.c_int32), vp,
                                                        vp, vp, vp, vp, _dp, C.POINTER(C.c_int32), vp]
+    L.irotavg_window_gate_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp, C.c_int64,
+                                                C.c_int64, vp, C.c_double, C.POINTER(C.c_int32), vp, vp, C.c_int64,
+                                                C.c_int64, vp, vp, vp, _dp, C.POINTER(C.c_int32), vp]
     L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
     L.irotavg_viewgraph_num_connections.restype = C.c_int64
@@ -201,6 +205,8 @@ def lib():
                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     L.irotavg_window_uncertainty.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
                                              C.c_double, _dp, C.c_int64, _ip, _dp, _dp, _dp, _dp, _dp]
+    L.irotavg_window_gate.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_double,
+                                      C.c_int64, _ip, _dp, C.c_int64, _dp, _dp, _dp, _dp]
     L.irotavg_trim_memory.argtypes = []
     L.irotavg_trim_memory.restype = C.c_int64
     L.irotavg_oneshot_cache.argtypes = [C.c_int]
@@ -580,6 +586,35 @@ def window_uncertainty(I, QQ, Q, f, weights=None, sigma=5 * np.pi / 180, pairs=N
     if rc != OK and rc not in allow_rc:
         raise IrotavgError(rc, "irotavg_window_uncertainty")
     return dict(rc=rc, var=var, pair_var=pv[:len(P)], edge_var=out[0], leverage=out[1], chi2=out[2], scale=scale.value)
+
+
+def window_gate(I, QQ, Q, f, cand_I, cand_QQ, weights=None, sigma=5 * np.pi / 180, angle=True, pair_var=True, chi2=True,
+                allow_rc=()):
+    """irotavg_window_gate: the closure gate of a window-size problem, no handle. cand_I: (ncand, 2) view ids of the
+    problem, cand_QQ: (ncand, 4) quaternions [x y z w], read as edge rows are. weights as window_uncertainty takes them.
+    Returns dict(rc, angle, pair_var, chi2, scale); an output that was not asked for is None. Arrays are preset to NaN
+    and written only on success."""
+    I = edges(I)
+    QQ = fmat(QQ)
+    Q = fmat(Q)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if w is not None and w.shape != (len(I),):
+        raise ValueError("weights must have %d entries" % len(I))
+    cI = np.ascontiguousarray(cand_I, dtype=np.int32).reshape(-1, 2)
+    cQ = fmat(np.asarray(cand_QQ, dtype=np.float64).reshape(-1, 4))
+    if len(cQ) != len(cI):
+        raise ValueError("cand_QQ must have %d rows" % len(cI))
+    nc, n_total = len(cI), Q.shape[0]
+    out = [np.full(nc, np.nan) if want else None for want in (angle, pair_var, chi2)]
+    scale = C.c_double(np.nan)
+    rc = lib().irotavg_window_gate(len(I), n_total, int(f), _i(I), _d(QQ), QQ.shape[0], _d(Q), n_total,
+                                   None if w is None else _d(w), float(sigma), nc, _i(cI) if nc else None,
+                                   _d(cQ) if nc else None, max(nc, 1), *[None if a is None else _d(a) for a in out],
+                                   C.byref(scale))
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_window_gate")
+    return dict(rc=rc, angle=out[0], pair_var=out[1], chi2=out[2], scale=scale.value)
+
 
 def plan_host(world, rank, I, n_total, f):
     """Host-only partition plan of one rank (irotavg_dist_plan_host): dict with the owned range,

@@ -956,6 +956,77 @@ int irotavg_window_uncertainty(int64_t m, int64_t n_total, int f, const int32_t 
     API_CATCH
 }
 
+// The closure gate of one window-size problem on caller arrays, no handle (docs/window_gate_batch.md): launches of
+// k_window_cov with the candidates staged as the view-graph route stages them (operator rows of the two ends, the poses
+// of the two ends, the measurement), 256 to a launch. What irotavg_window_gate_batch_dev is bitwise equal to per problem.
+int irotavg_window_gate(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, const double *Q,
+                        int64_t ldq, const double *weights, double sigma, int64_t ncand, const int32_t *cand_I,
+                        const double *cand_QQ, int64_t ldcq, double *angle, double *pair_var, double *chi2, double *scale) {
+    if (!I || !QQ || !Q || m <= 0 || m > WIN_MAX_NE || n_total <= 0 || n_total > WIN_MAX_NV || ldqq < m || ldq < n_total ||
+        f < 0 || f >= n_total || !window_fits((int)n_total, f, (int)m))
+        return IROTAVG_ERR_BAD_ARG;
+    if (ncand > 0x7fffffffLL || !wingate_asked(ncand, cand_I && cand_QQ, angle, pair_var, chi2, scale) || (ncand > 0 && ldcq < ncand))
+        return IROTAVG_ERR_BAD_ARG;
+    // the kernel indexes LDS with the endpoints and the candidate rows unguarded on this route
+    for (int64_t k = 0; k < 2 * m; k++)
+        if (I[k] < 0 || I[k] >= n_total) return IROTAVG_ERR_BAD_ARG;
+    for (int64_t t = 0; t < ncand; t++) {
+        const int32_t i = cand_I[2 * t], j = cand_I[2 * t + 1];
+        if (i < 0 || i >= n_total || j < 0 || j >= n_total || i == j) return IROTAVG_ERR_BAD_ARG;
+    }
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    API_TRY
+    std::vector<double> qa((size_t)4 * m), Qa((size_t)4 * n_total);
+    for (int64_t k = 0; k < m; k++)
+        for (int c = 0; c < 4; c++) qa[(size_t)4 * k + c] = QQ[(size_t)c * ldqq + k];
+    for (int64_t r = 0; r < n_total; r++)
+        for (int c = 0; c < 4; c++) Qa[(size_t)4 * r + c] = Q[(size_t)c * ldq + r];
+    // operator rows by the pair rule (-1: a fixed view, no coefficient), the poses of both ends, the measurement
+    std::vector<int32_t> crow((size_t)2 * ncand);
+    std::vector<double> cq((size_t)12 * ncand), ang((size_t)ncand), cv((size_t)ncand), cc((size_t)ncand);
+    for (int64_t t = 0; t < ncand; t++) {
+        const int32_t i = cand_I[2 * t], j = cand_I[2 * t + 1];
+        crow[2 * t] = i < f ? -1 : i - f;
+        crow[2 * t + 1] = j < f ? -1 : j - f;
+        for (int c = 0; c < 4; c++) {
+            cq[(size_t)12 * t + c] = Qa[(size_t)4 * i + c];
+            cq[(size_t)12 * t + 4 + c] = Qa[(size_t)4 * j + c];
+            cq[(size_t)12 * t + 8 + c] = cand_QQ[(size_t)c * ldcq + t];
+        }
+    }
+    WinCovQuery q{};
+    q.nv = (int)n_total;
+    q.f = f;
+    q.ne = (int)m;
+    q.I = I;
+    q.qq_aos = qa.data();
+    q.Q_aos = Qa.data();
+    q.sigma = sigma;
+    q.weights = weights;
+    q.nc = (int)ncand;
+    q.crow = crow.data();
+    q.cq = cq.data();
+    q.angle = ang.data();
+    q.cand_var = cv.data();
+    q.cand_chi2 = cc.data();
+    struct Owner {
+        WinCov *w = wincov_new();
+        ~Owner() { wincov_delete(w); }
+    } own;
+    const int rc = wincov_query(*own.w, q);
+    if (rc != IROTAVG_OK) return rc;  // outputs untouched
+    for (int64_t t = 0; t < ncand; t++)  // the batched kernel's rule: a pair_var that is not finite is a failed inverse
+        if (!(std::fabs(cv[(size_t)t]) < INFINITY)) return IROTAVG_ERR_SOLVER;
+    for (int64_t t = 0; t < ncand; t++) {
+        if (angle) angle[t] = ang[(size_t)t];
+        if (pair_var) pair_var[t] = cv[(size_t)t];
+        if (chi2) chi2[t] = cc[(size_t)t];
+    }
+    if (scale) *scale = q.s2;
+    return IROTAVG_OK;
+    API_CATCH
+}
+
 // replaces irotavg::quat_normalised for host-resident rows: Eigen normalized() per row
 // (ral/l1_irls.cpp:982-991), evaluated by the same device kernel as the resident variant.
 int irotavg_quat_normalised(int64_t n, double *Q, int64_t ldq, int f) {

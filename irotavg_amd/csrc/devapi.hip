@@ -157,7 +157,7 @@ bool dev_matrix_ok(const double *p, int64_t rows, int cols, int64_t rs, int64_t 
 }
 bool dev_vector_ok(const double *p, int64_t n, int device) { return dev_matrix_ok(p, n, 1, 1, 1, device); }
 
-// the checks irotavg_window_solve_batch_dev and irotavg_window_uncertainty_batch_dev make of the packed problem arrays
+// the checks irotavg_window_solve_batch_dev, irotavg_window_uncertainty_batch_dev and irotavg_window_gate_batch_dev make of the packed problem arrays
 // before any device work (alignment, the stride rule), and with a device (the lowest and the highest element of each)
 bool win_arrays_host_ok(const void *I, const double *QQ, int64_t qq_rs, int64_t qq_cs, const double *Q, int64_t q_rs,
                         int64_t q_cs, const double *w, int64_t sum_m, int64_t sum_n) {
@@ -397,7 +397,7 @@ int irotavg_window_uncertainty_batch_dev(int64_t nb, const int32_t *sizes, const
     if (!I_dev || !QQ_dev || !Q_dev) return IROTAVG_ERR_BAD_ARG;
     return guarded([&]() -> int {
         WinCovPlan plan;
-        if (!wincov_plan(nb, sizes, npairs, plan)) return IROTAVG_ERR_BAD_ARG;
+        if (!wincov_plan(nb, sizes, npairs, nullptr, plan)) return IROTAVG_ERR_BAD_ARG;
         if (!wincov_asked(var_dev, plan.sum_p, pairs_dev && pair_var_dev, edge_var_dev, leverage_dev, chi2_dev, scale))
             return IROTAVG_ERR_BAD_ARG;
         if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n))
@@ -422,6 +422,57 @@ int irotavg_window_uncertainty_batch_dev(int64_t nb, const int32_t *sizes, const
         const WinCovArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
                              weights_dev, var_dev, plan.sum_p > 0 ? pairs_dev : nullptr, plan.sum_p > 0 ? pair_var_dev : nullptr,
                              edge_var_dev, leverage_dev, chi2_dev};
+        return wincov_batch_dev(plan, device, A, sigma, scale, results, static_cast<hipStream_t>(stream));
+    });
+}
+
+// The closure gate of many small problems on packed device arrays, one workgroup each, one launch
+// (docs/window_gate_batch.md): the candidates of k_window_gate_user, everything else as the call above.
+int irotavg_window_gate_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                                  int64_t qq_cs, const double *Q_dev, int64_t q_rs, int64_t q_cs, const double *weights_dev,
+                                  double sigma, const int32_t *ncand, const int32_t *cand_I_dev, const double *cand_QQ_dev,
+                                  int64_t cq_rs, int64_t cq_cs, double *angle_dev, double *pair_var_dev, double *chi2_dev,
+                                  double *scale, int32_t *results, void *stream) {
+    if (!I_dev || !QQ_dev || !Q_dev) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        WinCovPlan plan;
+        if (!wincov_plan(nb, sizes, nullptr, ncand, plan)) return IROTAVG_ERR_BAD_ARG;
+        const int64_t sum_c = plan.sum_c;
+        if (!wingate_asked(sum_c, cand_I_dev && cand_QQ_dev, angle_dev, pair_var_dev, chi2_dev, scale)) return IROTAVG_ERR_BAD_ARG;
+        if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n))
+            return IROTAVG_ERR_BAD_ARG;
+        double *const per_cand[3] = {angle_dev, pair_var_dev, chi2_dev};
+        if (sum_c > 0) {
+            for (double *p : per_cand)
+                if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return IROTAVG_ERR_BAD_ARG;
+            if ((reinterpret_cast<uintptr_t>(cand_I_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(cand_QQ_dev) & 7) != 0 ||
+                !strides_ok(sum_c, 4, cq_rs, cq_cs))
+                return IROTAVG_ERR_BAD_ARG;
+        }
+        if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!win_arrays_dev_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n, device))
+            return IROTAVG_ERR_BAD_ARG;
+        if (sum_c > 0) {
+            if (!dev_ptr_ok(cand_I_dev, device) || !dev_ptr_ok(cand_I_dev + 2 * sum_c - 1, device) ||
+                !dev_matrix_ok(cand_QQ_dev, sum_c, 4, cq_rs, cq_cs, device))
+                return IROTAVG_ERR_BAD_ARG;
+            for (double *p : per_cand)
+                if (p && !dev_vector_ok(p, sum_c, device)) return IROTAVG_ERR_BAD_ARG;
+        }
+        WinCovArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs, weights_dev,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        A.gate = true;
+        if (sum_c > 0) {  // (without candidates the kernel is handed no candidate array at all)
+            A.cand = cand_I_dev;
+            A.cand_QQ = cand_QQ_dev;
+            A.cq_rs = (long long)cq_rs;
+            A.cq_cs = (long long)cq_cs;
+            A.angle = angle_dev;
+            A.cand_var = pair_var_dev;
+            A.cand_chi2 = chi2_dev;
+        }
         return wincov_batch_dev(plan, device, A, sigma, scale, results, static_cast<hipStream_t>(stream));
     });
 }

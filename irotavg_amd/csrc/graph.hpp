@@ -344,7 +344,7 @@ struct WinCovQuery {
     double s2;                      // OUT
 };
 int wincov_query(WinCov &wc, WinCovQuery &q);  // IROTAVG_ERR_SOLVER: singular, outputs untouched
-// the batched form on the caller's DEVICE arrays (irotavg_window_uncertainty_batch_dev; plan: winbatch.hpp), packed as
+// the batched form on the caller's DEVICE arrays (irotavg_window_uncertainty_batch_dev, irotavg_window_gate_batch_dev; plan: winbatch.hpp), packed as
 // WinBatchArrays; pairs = sum(npairs) pairs of view ids local to their problem; every output may be nullptr
 struct WinCovPlan;
 struct WinCovArrays {
@@ -358,6 +358,13 @@ struct WinCovArrays {
     const int32_t *pairs;
     double *pair_var;       // OUT sum(npairs)
     double *edge_var, *leverage, *chi2;  // OUT sum(m) each
+    // irotavg_window_gate_batch_dev (gate: the instance of the kernel that reads candidates): sum(ncand) pairs of view ids
+    // local to their problem, their measurements as a strided matrix, three outputs of sum(ncand) each
+    bool gate = false;
+    const int32_t *cand = nullptr;
+    const double *cand_QQ = nullptr;
+    long long cq_rs = 0, cq_cs = 0;
+    double *angle = nullptr, *cand_var = nullptr, *cand_chi2 = nullptr;
 };
 int wincov_batch_dev(const WinCovPlan &plan, int device, const WinCovArrays &A, double sigma, double *scale /* host */,
                      int32_t *results /* host */, hipStream_t stream);

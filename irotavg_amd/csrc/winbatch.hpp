@@ -1,6 +1,7 @@
 // winbatch.hpp -- the host arithmetic of the window kernels, of irotavg_window_solve_batch_dev and of
-// irotavg_window_uncertainty_batch_dev: size limits, the staging layout, the stride rule of the `_dev` API, the plan of a
-// batch (offsets and descriptors from `sizes`), the LDS layout and the pair offsets of the uncertainty kernels. Plain C++ with no HIP
+// irotavg_window_uncertainty_batch_dev / irotavg_window_gate_batch_dev: size limits, the staging layout, the stride rule of
+// the `_dev` API, the plan of a batch (offsets and descriptors from `sizes`), the LDS layout and the pair and candidate
+// offsets of the uncertainty kernels. Plain C++ with no HIP
 // type in it, so that a stand-alone program can run all of it under a sanitizer on a machine without a device
 // (tools/winbatch_host_check.cpp).
 #pragma once
@@ -135,19 +136,23 @@ inline bool winbatch_plan(int64_t nb, const int32_t *sizes, int kernel, WinBatch
 // ---- the uncertainty of such problems: k_window_cov / k_window_cov_user (wincov.hip), irotavg_window_uncertainty[_batch_dev]
 constexpr int WINCOV_THREADS = 256;
 constexpr int WINCOV_LD = WIN_MAX_NU + 1;  // row stride of M in LDS (bank spread), whatever the problem's nu
+constexpr int WINCOV_CAND_CHUNK = 256;     // candidate measurements the batched gate keeps in LDS at a time (8 KB)
 // dynamic LDS of one workgroup, in bytes from its base: the quaternions, (stage: the measurements, as WinIoUser keeps
-// them,) per edge the residual and the weight, M, the endpoints, three vectors of nu, the reduction scratch
+// them,) per edge the residual and the weight, M, the endpoints, three vectors of nu, the reduction scratch, (a batched
+// problem with nc candidates: one chunk of their measurements)
 struct WinCovLds {
-    size_t oQ, oQQ, oR, oM, oI, oSc, oCol, oRow, oRed, bytes;
+    size_t oQ, oQQ, oR, oM, oI, oSc, oCol, oRow, oRed, oC, bytes;
 };
-constexpr WinCovLds wincov_lds(int nv, int ne, int nu, bool stage) {
+constexpr WinCovLds wincov_lds(int nv, int ne, int nu, bool stage, int nc = 0) {
     const size_t oQQ = 32 * (size_t)nv, oR = oQQ + (stage ? 32 * (size_t)ne : 0), oM = oR + 32 * (size_t)ne;
     const size_t oI = oM + sizeof(double) * (size_t)nu * WINCOV_LD, oSc = oI + 8 * (size_t)ne;
     const size_t oCol = oSc + sizeof(double) * (size_t)nu, oRow = oCol + sizeof(double) * (size_t)nu;
     const size_t oRed = oRow + sizeof(double) * (size_t)nu;
-    return WinCovLds{0, oQQ, oR, oM, oI, oSc, oCol, oRow, oRed, oRed + sizeof(double) * 2 * WINCOV_THREADS};
+    const size_t end = oRed + sizeof(double) * 2 * WINCOV_THREADS, rows = nc < WINCOV_CAND_CHUNK ? (nc > 0 ? nc : 0) : WINCOV_CAND_CHUNK;
+    const size_t oC = (end + 31) & ~(size_t)31;  // double4 rows (the vectors before it leave `end` on 8 bytes)
+    return WinCovLds{0, oQQ, oR, oM, oI, oSc, oCol, oRow, oRed, oC, rows ? oC + 32 * rows : end};
 }
-static_assert(wincov_lds(WIN_MAX_NV, WIN_MAX_NE, WIN_MAX_NU, true).bytes <= WIN_MAX_LDS,
+static_assert(wincov_lds(WIN_MAX_NV, WIN_MAX_NE, WIN_MAX_NU, true, 0x7fffffff).bytes <= WIN_MAX_LDS,
               "every term grows with its size: a problem inside the limits fits");
 
 // what a workgroup of the uncertainty kernels leaves: the sequence number last, as WinResult::seq
@@ -155,38 +160,41 @@ struct WinCovResult {
     int status, seq;
     double s2;
 };
-// one problem of irotavg_window_uncertainty_batch_dev: the solve's descriptor, then its pairs in the packed pair arrays
+// one problem of irotavg_window_uncertainty_batch_dev / irotavg_window_gate_batch_dev: the solve's descriptor, then its
+// pairs in the packed pair arrays and its candidates in the packed candidate arrays
 struct WinCovDesc {
     WinDesc d;
-    long long poff;
-    int np, pad;
+    long long poff, coff;
+    int np, nc;
 };
 struct WinCovPlan {
     std::vector<WinCovDesc> desc;  // in the caller's order
-    int64_t sum_m = 0, sum_n = 0, sum_p = 0;
-    size_t lds = 0;  // largest wincov_lds(..., true).bytes of the batch
+    int64_t sum_m = 0, sum_n = 0, sum_p = 0, sum_c = 0;
+    size_t lds = 0;  // largest wincov_lds(..., true, nc).bytes of the batch
 };
-// sizes as winbatch_plan takes them (the same limits); npairs: nb counts or nullptr (no pairs anywhere).
-// false: what winbatch_plan refuses, or a negative pair count.
-inline bool wincov_plan(int64_t nb, const int32_t *sizes, const int32_t *npairs, WinCovPlan &out) {
+// sizes as winbatch_plan takes them (the same limits); npairs / ncand: nb counts each or nullptr (none anywhere).
+// false: what winbatch_plan refuses, or a negative count.
+inline bool wincov_plan(int64_t nb, const int32_t *sizes, const int32_t *npairs, const int32_t *ncand, WinCovPlan &out) {
     WinBatchPlan base;
     if (!winbatch_plan(nb, sizes, 1, base)) return false;  // kernel 1: one list, in the caller's order
-    for (int64_t b = 0; npairs && b < nb; b++)
-        if (npairs[b] < 0) return false;
+    for (int64_t b = 0; b < nb; b++)
+        if ((npairs && npairs[b] < 0) || (ncand && ncand[b] < 0)) return false;
     out.desc.assign((size_t)nb, WinCovDesc{});
     out.lds = 0;
-    int64_t poff = 0;
+    int64_t poff = 0, coff = 0;
     for (int64_t b = 0; b < nb; b++) {
         const WinDesc &d = base.desc[(size_t)b];
-        const int np = npairs ? npairs[b] : 0;
-        out.desc[(size_t)b] = WinCovDesc{d, (long long)poff, np, 0};
-        const size_t l = wincov_lds(d.nv, d.ne, d.nv - d.f, true).bytes;
+        const int np = npairs ? npairs[b] : 0, nc = ncand ? ncand[b] : 0;
+        out.desc[(size_t)b] = WinCovDesc{d, (long long)poff, (long long)coff, np, nc};
+        const size_t l = wincov_lds(d.nv, d.ne, d.nv - d.f, true, nc).bytes;
         if (l > out.lds) out.lds = l;
         poff += np;
+        coff += nc;
     }
     out.sum_m = base.sum_m;
     out.sum_n = base.sum_n;
     out.sum_p = poff;
+    out.sum_c = coff;
     return true;
 }
 // A query must ask for something: pose variances, pair variances, an edge output or the scale. (Pairs are asked for by
@@ -194,6 +202,12 @@ inline bool wincov_plan(int64_t nb, const int32_t *sizes, const int32_t *npairs,
 inline bool wincov_asked(bool var, int64_t pairs, bool pair_arrays, bool edge_var, bool leverage, bool chi2, bool scale) {
     if (pairs < 0 || (pairs > 0 && !pair_arrays)) return false;
     return var || pairs > 0 || edge_var || leverage || chi2 || scale;
+}
+// The gate must ask for something too: an output array with candidates to fill it, or the scale. (A positive count needs
+// both candidate arrays.)
+inline bool wingate_asked(int64_t cands, bool cand_arrays, bool angle, bool pair_var, bool chi2, bool scale) {
+    if (cands < 0 || (cands > 0 && !cand_arrays)) return false;
+    return (cands > 0 && (angle || pair_var || chi2)) || scale;
 }
 
 }  // namespace irh

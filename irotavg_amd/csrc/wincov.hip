@@ -10,6 +10,8 @@
 //   k_window_cov_user  blockIdx.x selects a descriptor; the problem lies in the caller's packed device arrays
 //                      (irotavg_window_uncertainty_batch_dev, docs/window_uncertainty_batch.md): ids checked by the
 //                      workgroup, outputs stored only once the problem is known to have succeeded
+//   k_window_gate_user the same on caller arrays with the candidates of the closure gate, which the instance above
+//                      compiles out (irotavg_window_gate_batch_dev, docs/window_gate_batch.md)
 //   1. residuals r_k (K1's formula) and weights: d_k = 1 / (|r_k|^2 + sigma^2), Geman-McClure at a zero step, or the
 //      caller's own (a per-call switch)
 //   2. M: one owner thread per row walks the edges in index order (no atomics: bitwise deterministic)
@@ -34,7 +36,7 @@ namespace {
 
 constexpr int WC_MAX_NU = WIN_MAX_NU, WC_MAX_NV = WIN_MAX_NV, WC_MAX_NE = WIN_MAX_NE;  // window_fits' limits
 constexpr int WC_MAX_P = 1024;                                   // pairs staged per launch
-constexpr int WC_MAX_C = 256;                                    // candidates staged per launch
+constexpr int WC_MAX_C = WINCOV_CAND_CHUNK;                      // candidates staged per launch, and per LDS chunk of the batched gate
 constexpr int WC_LD = WINCOV_LD;                                 // row stride of M in LDS (bank spread)
 constexpr int WC_THREADS = WINCOV_THREADS;
 
@@ -115,6 +117,20 @@ struct WcIoSlot {  // the library's own staging slot: every output has its place
         reinterpret_cast<double *>(slot + oChi)[k] = c;
     }
     __device__ __forceinline__ void put_pair(int q, double v) const { reinterpret_cast<double *>(slot + oPv)[q] = v; }
+    // candidates: the host has formed the rows and fetched the poses (one launch stages at most WC_MAX_C of them)
+    static constexpr bool kCand = true;
+    // (q is counted in 64 bits: the batched form has no cap, and q + 256 must not wrap next to INT32_MAX)
+    __device__ __forceinline__ int2 cand_rows(long long q, int) const { return reinterpret_cast<const int2 *>(slot + oCR)[q]; }
+    __device__ __forceinline__ const double4 *cand_stage(double4 *, long long, int) const { return nullptr; }
+    __device__ __forceinline__ WinCovCand cand(long long q, int, const double4 *, const double4 *) const {
+        return reinterpret_cast<const WinCovCand *>(slot + oCQ)[q];
+    }
+    __device__ __forceinline__ void put_cand(long long q, double a, double v, double c) const {
+        double *ca = reinterpret_cast<double *>(slot + oCa);
+        ca[q] = a;
+        ca[WC_MAX_C + q] = v;
+        ca[2 * WC_MAX_C + q] = c;
+    }
 };
 struct WinCovUser {  // the caller's packed arrays of a batch (kernel argument); any output may be nullptr
     const int2 *I;
@@ -127,11 +143,20 @@ struct WinCovUser {  // the caller's packed arrays of a batch (kernel argument);
     const int2 *pairs;
     double *pair_var, *edge_var, *leverage, *chi2;
     int qq_aos, q_aos;
+    // the candidates of the closure gate (k_window_gate_user alone reads these)
+    const int2 *cand;
+    const double *CQ;
+    long long cq_rs, cq_cs;
+    double *angle, *cand_var, *cand_chi2;
+    int cq_aos;
 };
-struct WcIoUser {  // one problem of them: rows eoff.. of I / QQ / w and the edge outputs, voff.. of Q / var, poff.. of the pairs
-    static constexpr bool kUser = true;
+// one problem of them: rows eoff.. of I / QQ / w and the edge outputs, voff.. of Q / var, poff.. of the pairs, coff.. of
+// the candidates (kGate: the instance that has them)
+template <bool kGate>
+struct WcIoUser {
+    static constexpr bool kUser = true, kCand = kGate;
     WinCovUser U;
-    long long eoff, voff, poff;
+    long long eoff, voff, poff, coff;
     __device__ __forceinline__ int2 edge(int k) const { return U.I[eoff + k]; }
     __device__ __forceinline__ double4 q(int v) const { return ld_row(U.Q, U.q_rs, U.q_cs, voff + v, U.q_aos != 0); }
     // The rows go through LDS and are read back as double4, so that edge_log sees its measurement in the form the staged
@@ -154,7 +179,40 @@ struct WcIoUser {  // one problem of them: rows eoff.. of I / QQ / w and the edg
         if (U.chi2) U.chi2[eoff + k] = c;
     }
     __device__ __forceinline__ void put_pair(int q, double v) const { U.pair_var[poff + q] = v; }
+    __device__ __forceinline__ int2 cand_ids(long long q) const { return U.cand[coff + q]; }
+    // view ids (checked: inside, i != j) -> operator rows by the pair rule: a fixed end has no coefficient
+    __device__ __forceinline__ int2 cand_rows(long long q, int f) const {
+        const int2 p = cand_ids(q);
+        return make_int2(p.x < f ? -1 : p.x - f, p.y < f ? -1 : p.y - f);
+    }
+    // n measurements from row c0 into LDS (the caller brackets this with barriers): read back as double4 there, as the
+    // edges' are, so that edge_log is handed what the staged kernel's load hands it
+    __device__ __forceinline__ const double4 *cand_stage(double4 *lds, long long c0, int n) const {
+        for (int k = threadIdx.x; k < n; k += blockDim.x) lds[k] = ld_row(U.CQ, U.cq_rs, U.cq_cs, coff + c0 + k, U.cq_aos != 0);
+        return lds;
+    }
+    // candidate q, the k-th of its chunk: the poses of its ends from LDS, its measurement from the chunk
+    __device__ __forceinline__ WinCovCand cand(long long q, int k, const double4 *sQ, const double4 *chunk) const {
+        const int2 p = cand_ids(q);
+        return WinCovCand{sQ[p.x], sQ[p.y], chunk[k]};
+    }
+    __device__ __forceinline__ void put_cand(long long q, double a, double v, double c) const {
+        if (U.angle) U.angle[coff + q] = a;
+        if (U.cand_var) U.cand_var[coff + q] = v;
+        if (U.cand_chi2) U.cand_chi2[coff + q] = c;
+    }
 };
+
+// The gate's arithmetic, one copy for the staged and the batched kernel (they must agree bit for bit): the candidate's
+// residual at its ends' poses, its norm, and chi2 = |r|^2 / (s^2 (pair_var + sigma^4)) with sigma^4 = 1 / d0^2, d0 the
+// weight of a zero residual.
+__device__ __forceinline__ void wc_gate(const WinCovCand &cd, double v, double s2, double sg2, double &angle, double &chi2) {
+    double rx, ry, rz;
+    edge_log(cd.qi, cd.qj, cd.qq, rx, ry, rz);
+    const double e2 = wc_norm2(rx, ry, rz);
+    angle = sqrt(e2);
+    chi2 = e2 / (s2 * (v + sg2 * sg2));
+}
 
 __device__ __forceinline__ void wc_finish(WinCovResult *res, int status, double s2, int seq) {
     res->status = status;
@@ -180,7 +238,7 @@ __device__ __forceinline__ void wincov_body(const WinCovParams &P, const IO &io,
 
     const int t = threadIdx.x, nv = P.nv, f = P.f, ne = P.ne, nu = nv - f;
     const bool ok = nv >= 1 && nv <= WC_MAX_NV && f >= 0 && nu >= 1 && nu <= WC_MAX_NU && ne >= 1 && ne <= WC_MAX_NE &&
-                    P.np >= 0 && (IO::kUser || P.np <= WC_MAX_P) && P.nc >= 0 && P.nc <= WC_MAX_C;
+                    P.np >= 0 && (IO::kUser || P.np <= WC_MAX_P) && P.nc >= 0 && (IO::kUser || P.nc <= WC_MAX_C);
     if (!ok) {  // (the host checks the same before the launch)
         if (t == 0) wc_finish(res, IROTAVG_ERR_BAD_ARG, NAN, P.seq);
         return;
@@ -203,6 +261,11 @@ __device__ __forceinline__ void wincov_body(const WinCovParams &P, const IO &io,
             const int2 p = io.pair_ids(q);
             outside = outside || (unsigned)p.x >= (unsigned)nv || (unsigned)p.y >= (unsigned)nv;
         }
+        if constexpr (IO::kCand)
+            for (long long q = t; q < P.nc; q += WC_THREADS) {  // i == j is no measurement between two views
+                const int2 p = io.cand_ids(q);
+                outside = outside || (unsigned)p.x >= (unsigned)nv || (unsigned)p.y >= (unsigned)nv || p.x == p.y;
+            }
         if (outside) sDead = 2;
         __syncthreads();
         if (sDead != 0) {
@@ -306,6 +369,11 @@ __device__ __forceinline__ void wincov_body(const WinCovParams &P, const IO &io,
         if (t < nu && !(fabs(M[t * WC_LD + t]) < INFINITY)) sDead = 1;
         for (int k = t; k < ne; k += WC_THREADS)
             if (!(fabs(wc_edge_var(M, sI[k], f)) < INFINITY)) sDead = 1;
+        if constexpr (IO::kCand)
+            for (long long q = t; q < P.nc; q += WC_THREADS) {
+                const int2 ab = io.cand_rows(q, f);
+                if (!(fabs(wc_usu(M, ab.x, ab.y)) < INFINITY)) sDead = 1;
+            }
         __syncthreads();
         if (sDead == 0 && io.U.var)
             for (int v = t; v < nv; v += WC_THREADS) io.U.var[io.voff + v] = v < f ? 0.0 : M[(v - f) * WC_LD + (v - f)];
@@ -318,7 +386,8 @@ __device__ __forceinline__ void wincov_body(const WinCovParams &P, const IO &io,
         }
     }
     const bool store = !IO::kUser || sDead == 0;  // (kUser: uniform, read behind the barrier above)
-    for (int k = t; k < (store && P.first ? ne : 0); k += WC_THREADS) {
+    constexpr bool kEdgeOut = !(IO::kUser && IO::kCand);  // the batched gate has no edge output: nothing to compute for one
+    for (int k = t; k < (kEdgeOut && store && P.first ? ne : 0); k += WC_THREADS) {
         const double4 rr = sR[k];
         const double v = wc_edge_var(M, sI[k], f), w = rr.w * rr.w, l = w * v;
         if (!IO::kUser && !(fabs(v) < INFINITY)) sDead = 1;
@@ -329,21 +398,24 @@ __device__ __forceinline__ void wincov_body(const WinCovParams &P, const IO &io,
         const bool in = ab.x >= -1 && ab.x < nu && ab.y >= -1 && ab.y < nu;
         io.put_pair(q, in ? wc_usu(M, ab.x, ab.y) : NAN);
     }
-    if constexpr (!IO::kUser) {
-        const int2 *cr = reinterpret_cast<const int2 *>(io.slot + oCR);
-        const WinCovCand *cq = reinterpret_cast<const WinCovCand *>(io.slot + oCQ);
-        double *ca = reinterpret_cast<double *>(io.slot + oCa);
-        for (int q = t; q < P.nc; q += WC_THREADS) {
-            const int2 ab = cr[q];
-            const WinCovCand cd = cq[q];
-            double rx, ry, rz;
-            edge_log(cd.qi, cd.qj, cd.qq, rx, ry, rz);
-            const double e2 = wc_norm2(rx, ry, rz);
-            const bool in = ab.x >= -1 && ab.x < nu && ab.y >= -1 && ab.y < nu;
-            const double v = in ? wc_usu(M, ab.x, ab.y) : NAN;
-            ca[q] = sqrt(e2);
-            ca[WC_MAX_C + q] = v;
-            ca[2 * WC_MAX_C + q] = e2 / (s2 * (v + sg2 * sg2));  // sigma^4 = 1 / d0^2, d0 the weight of a zero residual
+    if constexpr (IO::kCand) {
+        // the candidates of the gate, a chunk of measurements at a time (kUser: through LDS; the staged form has them all
+        // in its slot). The trip counts are uniform: P.nc and `store` are the workgroup's.
+        double4 *sC = reinterpret_cast<double4 *>(lds + L.oC);
+        for (long long c0 = 0; c0 < (store ? P.nc : 0); c0 += WC_MAX_C) {
+            const int n = (int)min((long long)WC_MAX_C, P.nc - c0);
+            const double4 *chunk = io.cand_stage(sC, c0, n);
+            if constexpr (IO::kUser) __syncthreads();
+            for (int k = t; k < n; k += WC_THREADS) {
+                const int2 ab = io.cand_rows(c0 + k, f);
+                const WinCovCand cd = io.cand(c0 + k, k, sQ, chunk);
+                const bool in = ab.x >= -1 && ab.x < nu && ab.y >= -1 && ab.y < nu;
+                const double v = in ? wc_usu(M, ab.x, ab.y) : NAN;
+                double angle, chi2;
+                wc_gate(cd, v, s2, sg2, angle, chi2);
+                io.put_cand(c0 + k, angle, v, chi2);
+            }
+            if constexpr (IO::kUser) __syncthreads();
         }
     }
     __threadfence_system();
@@ -368,7 +440,22 @@ __global__ __launch_bounds__(WC_THREADS) void k_window_cov_user(WinCovParams Pk,
     P.f = d.d.f;
     P.ne = d.d.ne;
     P.np = d.np;
-    wincov_body(P, WcIoUser{U, d.d.eoff, d.d.voff, d.poff}, wincov_lds(d.d.nv, d.d.ne, d.d.nv - d.d.f, true), R + d.d.idx);
+    wincov_body(P, WcIoUser<false>{U, d.d.eoff, d.d.voff, d.poff, 0}, wincov_lds(d.d.nv, d.d.ne, d.d.nv - d.d.f, true), R + d.d.idx);
+}
+
+// The same with the candidates of descriptor b (irotavg_window_gate_batch_dev): a second instance of the body, so that
+// the one above stays the code it was.
+__global__ __launch_bounds__(WC_THREADS) void k_window_gate_user(WinCovParams Pk, const WinCovDesc *__restrict__ D, WinCovUser U,
+                                                                 WinCovResult *__restrict__ R) {
+    const WinCovDesc d = D[blockIdx.x];
+    WinCovParams P = Pk;
+    P.nv = d.d.nv;
+    P.f = d.d.f;
+    P.ne = d.d.ne;
+    P.np = d.np;
+    P.nc = d.nc;
+    wincov_body(P, WcIoUser<true>{U, d.d.eoff, d.d.voff, d.poff, d.coff}, wincov_lds(d.d.nv, d.d.ne, d.d.nv - d.d.f, true, d.nc),
+                R + d.d.idx);
 }
 
 }  // namespace
@@ -448,7 +535,7 @@ struct WinCovBatchDev {
     std::mutex mu;
     MappedBlock blk;  // portable: the callers' current devices may differ
     int seq = 0;
-    int attr_device = -1;  // k_window_cov_user may use the LDS of a problem at the limits on this device
+    int attr_device[2] = {-1, -1};  // k_window_cov_user / k_window_gate_user may use the LDS of a problem at the limits there
 };
 static WinCovBatchDev &wincov_batch_state() {
     static WinCovBatchDev *w = new WinCovBatchDev();  // (never destroyed: no HIP call at process exit)
@@ -472,14 +559,17 @@ int wincov_batch_dev(const WinCovPlan &plan, int device, const WinCovArrays &A, 
     const WinCovUser U{reinterpret_cast<const int2 *>(A.I), A.QQ, A.qq_rs, A.qq_cs, A.Q, A.q_rs, A.q_cs, A.weights, A.var,
                        reinterpret_cast<const int2 *>(A.pairs), A.pair_var, A.edge_var, A.leverage, A.chi2,
                        rows16(reinterpret_cast<uintptr_t>(A.QQ), A.qq_rs, A.qq_cs),
-                       rows16(reinterpret_cast<uintptr_t>(A.Q), A.q_rs, A.q_cs)};
-    if (wb.attr_device != device) {
-        constexpr size_t most = wincov_lds(WC_MAX_NV, WC_MAX_NE, WC_MAX_NU, true).bytes;
-        IRH_CHECK(hipFuncSetAttribute((const void *)k_window_cov_user, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-        wb.attr_device = device;
+                       rows16(reinterpret_cast<uintptr_t>(A.Q), A.q_rs, A.q_cs),
+                       reinterpret_cast<const int2 *>(A.cand), A.cand_QQ, A.cq_rs, A.cq_cs, A.angle, A.cand_var, A.cand_chi2,
+                       A.cand_QQ ? rows16(reinterpret_cast<uintptr_t>(A.cand_QQ), A.cq_rs, A.cq_cs) : 0};
+    const auto kernel = A.gate ? k_window_gate_user : k_window_cov_user;
+    if (wb.attr_device[A.gate] != device) {
+        const size_t most = wincov_lds(WC_MAX_NV, WC_MAX_NE, WC_MAX_NU, true, A.gate ? WINCOV_CAND_CHUNK : 0).bytes;
+        IRH_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+        wb.attr_device[A.gate] = device;
     }
     // the LDS of the largest problem of THIS batch: small problems share a compute unit
-    hipLaunchKernelGGL(k_window_cov_user, dim3((unsigned)nb), dim3(WC_THREADS), plan.lds, stream, P,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(WC_THREADS), plan.lds, stream, P,
                        reinterpret_cast<const WinCovDesc *>(wb.blk.hdev + oD), U, reinterpret_cast<WinCovResult *>(wb.blk.hdev));
     IRH_CHECK(hipGetLastError());
     // 5 ms: long batches, inputs still in flight on the caller's stream, a kernel that died

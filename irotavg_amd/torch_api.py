@@ -221,23 +221,24 @@ def window_solve_batch(sizes, edge_index, QQ, Q, cost=4, sigma=5 * 3.14159265358
 
 
 # ---- their uncertainty in one call (irotavg_window_uncertainty_batch_dev, docs/window_uncertainty_batch.md) --------------
-def pair_offsets(npairs, nb):
+def pair_offsets(npairs, nb, name="npairs"):
     """npairs: host integers, one count per problem (or None: no pairs) -> (counts as contiguous int32, first pair row of
-    every problem, sum): the packing the C call assumes, formed in 64 bits."""
+    every problem, sum): the packing the C call assumes, formed in 64 bits. The candidate counts of window_gate_batch go
+    through here too (`name`: what an error calls them)."""
     import numpy as np
     if npairs is None:
         return None, np.zeros(nb, dtype=np.int64), 0
     if isinstance(npairs, torch.Tensor):
         if npairs.is_cuda:
-            raise TypeError("npairs must be a host array, got a tensor on %s" % npairs.device)
+            raise TypeError("%s must be a host array, got a tensor on %s" % (name, npairs.device))
         npairs = npairs.numpy()
     c = np.asarray(npairs)
     if c.dtype.kind not in "iu":
-        raise TypeError("npairs must be integers, got %s" % c.dtype)
+        raise TypeError("%s must be integers, got %s" % (name, c.dtype))
     if c.shape != (nb,):
-        raise ValueError("npairs must have shape (%d,), got %s" % (nb, c.shape))
+        raise ValueError("%s must have shape (%d,), got %s" % (name, nb, c.shape))
     if c.size and (c.min() < 0 or c.max() > INT32_MAX):
-        raise ValueError("npairs must be counts in int32 range")
+        raise ValueError("%s must be counts in int32 range" % name)
     c64 = c.astype(np.int64)
     return np.ascontiguousarray(c, dtype=np.int32), np.cumsum(c64) - c64, int(c64.sum())
 
@@ -303,3 +304,64 @@ def window_uncertainty_batch(sizes, edge_index, QQ, Q, weights=None, sigma=5 * 3
     if rc != capi.OK and rc not in allow_rc:
         raise capi.IrotavgError(rc, "irotavg_window_uncertainty_batch_dev")
     return dict(rc=rc, pair_var=pv, scale=scale, status=status, **outs)
+
+
+# ---- the closure gate on the same arrays (irotavg_window_gate_batch_dev, docs/window_gate_batch.md) ------------------------
+def window_gate_batch(sizes, edge_index, QQ, Q, cand_index, cand_QQ, ncand, weights=None, sigma=5 * 3.141592653589793 / 180,
+                      angle=True, pair_var=True, chi2=True, allow_rc=()):
+    """The closure gate of nb independent window-size problems, each as capi.window_gate, one workgroup per problem, in one
+    launch on torch's current stream. sizes, edge_index, QQ, Q, weights: as window_uncertainty_batch takes them (Q is only
+    read).
+
+    cand_index: (sum ncand, 2) int32 or int64 view ids local to their problem, cand_QQ: (sum ncand, 4) float64 with any
+    strides, ncand: the host counts per problem. angle / pair_var / chi2: True (a new tensor, preset to NaN), False / None
+    (not computed), or a contiguous float64 tensor of sum ncand entries to fill. Returns dict(rc, angle, pair_var, chi2,
+    scale, status); scale and status are host numpy arrays of nb entries (scale NaN where the problem failed). rc is the
+    first non-zero status in problem order; anything but OK raises unless listed in allow_rc. A problem that fails leaves
+    its rows of every output as they were."""
+    import numpy as np
+    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
+    nb = len(s32)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2), placed=False)
+    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), placed=False)
+    _check(Q, "Q", (torch.float64,), (sum_n, 4), placed=False)
+    if ncand is None:
+        raise ValueError("ncand is needed: one count per problem")
+    nc32, _, sum_c = pair_offsets(ncand, nb, "ncand")
+    _check(cand_index, "cand_index", (torch.int32, torch.int64), (sum_c, 2), placed=False)
+    _check(cand_QQ, "cand_QQ", (torch.float64,), (sum_c, 4), placed=False)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), device)
+    _check(Q, "Q", (torch.float64,), (sum_n, 4), device)
+    _check(cand_index, "cand_index", (torch.int32, torch.int64), (sum_c, 2), device)
+    _check(cand_QQ, "cand_QQ", (torch.float64,), (sum_c, 4), device)
+
+    def vector(t, name, n):
+        _check(t, name, (torch.float64,), (n,), device)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        return t
+    w = None if weights is None else vector(weights, "weights", sum_m)
+    outs = {}
+    for name, want in (("angle", angle), ("pair_var", pair_var), ("chi2", chi2)):
+        if want is True:
+            outs[name] = torch.full((sum_c,), float("nan"), dtype=torch.float64, device=device)
+        elif want is False or want is None:
+            outs[name] = None
+        else:
+            outs[name] = vector(want, name, sum_c)
+    scale = np.full(nb, np.nan)
+    status = np.zeros(nb, dtype=np.int32)
+    opt = lambda t: None if t is None or t.numel() == 0 else _ptr(t)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        ci = _narrow(cand_index)
+        rc = capi.lib().irotavg_window_gate_batch_dev(
+            nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(Q),
+            *matrix_strides(Q), None if w is None else _ptr(w), float(sigma), nc32.ctypes.data_as(C.POINTER(C.c_int32)),
+            opt(ci), opt(cand_QQ), *matrix_strides(cand_QQ), opt(outs["angle"]), opt(outs["pair_var"]), opt(outs["chi2"]),
+            scale.ctypes.data_as(C.POINTER(C.c_double)), status.ctypes.data_as(C.POINTER(C.c_int32)), _stream(device))
+    if rc != capi.OK and rc not in allow_rc:
+        raise capi.IrotavgError(rc, "irotavg_window_gate_batch_dev")
+    return dict(rc=rc, scale=scale, status=status, **outs)

@@ -1,6 +1,8 @@
 // winbatch_host_check.cpp -- the host arithmetic of irotavg_window_solve_batch_dev (irotavg_amd/csrc/winbatch.hpp: size
 // checks, packing offsets, descriptors, the stride rule, the span of a strided matrix and the 16-byte row rule) and of
-// irotavg_window_uncertainty_batch_dev (pair offsets, the LDS layout, the "nothing asked for" rule) as a stand-alone program that needs no device, meant to be built with a sanitizer:
+// irotavg_window_uncertainty_batch_dev / irotavg_window_gate_batch_dev (pair and candidate offsets, the LDS layout with its
+// chunk of candidate measurements, the "nothing asked for" rules) as a stand-alone program that needs no device, meant to
+// be built with a sanitizer:
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -Iirotavg_amd/csrc
 //       tools/winbatch_host_check.cpp -o winbatch_host_check && ./winbatch_host_check
 // Exit status 0 and "winbatch host check ok" when every expectation holds.
@@ -158,18 +160,18 @@ int main() {
     {
         WinCovPlan C;
         const int32_t np1[1] = {5}, neg[1] = {-1};
-        EXPECT(!wincov_plan(0, one, nullptr, C) && !wincov_plan(-1, one, np1, C) && !wincov_plan(WIN_BATCH_MAX + 1, one, nullptr, C));
-        EXPECT(!wincov_plan(1, nullptr, np1, C) && !wincov_plan(1, one, neg, C));
-        EXPECT(wincov_plan(1, one, nullptr, C) && C.sum_p == 0 && C.desc[0].np == 0 && C.desc[0].poff == 0);
-        EXPECT(wincov_plan(1, one, np1, C) && C.sum_p == 5 && C.desc[0].np == 5 && C.sum_m == 40 && C.sum_n == 12);
+        EXPECT(!wincov_plan(0, one, nullptr, nullptr, C) && !wincov_plan(-1, one, np1, nullptr, C) && !wincov_plan(WIN_BATCH_MAX + 1, one, nullptr, nullptr, C));
+        EXPECT(!wincov_plan(1, nullptr, np1, nullptr, C) && !wincov_plan(1, one, neg, nullptr, C));
+        EXPECT(wincov_plan(1, one, nullptr, nullptr, C) && C.sum_p == 0 && C.desc[0].np == 0 && C.desc[0].poff == 0);
+        EXPECT(wincov_plan(1, one, np1, nullptr, C) && C.sum_p == 5 && C.desc[0].np == 5 && C.sum_m == 40 && C.sum_n == 12);
         EXPECT(C.lds == wincov_lds(12, 40, 10, true).bytes);
         for (const auto &b : bad) {
             const int32_t s[9] = {12, 2, 40, b[0], b[1], b[2], 2, 1, 1}, c[3] = {0, 1, 2};
-            EXPECT(!wincov_plan(3, s, c, C) && !wincov_plan(3, s, nullptr, C));
+            EXPECT(!wincov_plan(3, s, c, nullptr, C) && !wincov_plan(3, s, nullptr, nullptr, C));
         }
         const int32_t s3[9] = {12, 2, 40, 320, 256, 640, 2, 1, 1}, c3[3] = {7, 0, imax}, cneg[3] = {7, imin, 3};
-        EXPECT(!wincov_plan(3, s3, cneg, C));
-        EXPECT(wincov_plan(3, s3, c3, C) && C.sum_p == 7 + (int64_t)imax && C.sum_m == 681 && C.sum_n == 334);
+        EXPECT(!wincov_plan(3, s3, cneg, nullptr, C));
+        EXPECT(wincov_plan(3, s3, c3, nullptr, C) && C.sum_p == 7 + (int64_t)imax && C.sum_m == 681 && C.sum_n == 334);
         EXPECT(C.desc[0].poff == 0 && C.desc[1].poff == 7 && C.desc[2].poff == 7 && C.desc[2].np == imax);
         EXPECT(C.lds == wincov_lds(320, 640, 64, true).bytes && C.lds <= WIN_MAX_LDS);
         // random batches: descriptors in the caller's order, offsets the 64-bit cumulative sums
@@ -186,7 +188,7 @@ int main() {
             s.insert(s.end(), {nu + f, f, ne});
             c.push_back(b % 3 == 0 ? 0 : rnd(0, 4000000));
         }
-        EXPECT(wincov_plan(3000, s.data(), c.data(), C) && C.desc.size() == 3000);
+        EXPECT(wincov_plan(3000, s.data(), c.data(), nullptr, C) && C.desc.size() == 3000);
         int64_t e = 0, v = 0, p = 0;
         size_t lds = 0;
         for (int b = 0; b < 3000; b++) {
@@ -214,6 +216,68 @@ int main() {
         EXPECT(wincov_asked(false, 0, false, false, false, false, true) && wincov_asked(false, 3, true, false, false, false, false));
         EXPECT(!wincov_asked(true, 3, false, true, true, true, true) && !wincov_asked(true, -1, true, true, true, true, true));
         EXPECT(!wincov_asked(true, lmin, true, true, true, true, true) && wincov_asked(false, lmax, true, false, false, false, false));
+    }
+    // ---- the gate batch (irotavg_window_gate_batch_dev): candidate offsets and counts, the LDS chunk, its "asked for" rule
+    {
+        WinCovPlan C;
+        const int32_t nc1[1] = {5}, neg[1] = {-1}, np1[1] = {3};
+        EXPECT(!wincov_plan(0, one, nullptr, nc1, C) && !wincov_plan(1, nullptr, nullptr, nc1, C) && !wincov_plan(1, one, nullptr, neg, C));
+        EXPECT(!wincov_plan(1, one, neg, nc1, C) && !wincov_plan(1, one, np1, neg, C));
+        EXPECT(wincov_plan(1, one, nullptr, nullptr, C) && C.sum_c == 0 && C.desc[0].nc == 0 && C.desc[0].coff == 0);
+        EXPECT(wincov_plan(1, one, np1, nc1, C) && C.sum_c == 5 && C.sum_p == 3 && C.desc[0].nc == 5 && C.desc[0].np == 3);
+        EXPECT(C.lds == wincov_lds(12, 40, 10, true, 5).bytes && C.lds == wincov_lds(12, 40, 10, true, 5).oC + 5 * 32);
+        for (const auto &b : bad) {
+            const int32_t s[9] = {12, 2, 40, b[0], b[1], b[2], 2, 1, 1}, c[3] = {0, 1, 2};
+            EXPECT(!wincov_plan(3, s, nullptr, c, C));
+        }
+        const int32_t s3[9] = {12, 2, 40, 320, 256, 640, 2, 1, 1}, c3[3] = {7, imax, imax}, cneg[3] = {7, imin, 3};
+        EXPECT(!wincov_plan(3, s3, nullptr, cneg, C));
+        EXPECT(wincov_plan(3, s3, nullptr, c3, C) && C.sum_c == 7 + 2 * (int64_t)imax && C.sum_p == 0);
+        EXPECT(C.desc[0].coff == 0 && C.desc[1].coff == 7 && C.desc[2].coff == 7 + (int64_t)imax && C.desc[2].nc == imax);
+        // the chunk never grows past WINCOV_CAND_CHUNK rows: the largest problem with any number of candidates fits
+        EXPECT(C.lds == wincov_lds(320, 640, 64, true, imax).bytes && C.lds == wincov_lds(320, 640, 64, true).oC + 32 * WINCOV_CAND_CHUNK);
+        EXPECT(C.lds <= WIN_MAX_LDS && WINCOV_CAND_CHUNK == 256);
+        EXPECT(wincov_lds(12, 40, 10, true, -4).bytes == wincov_lds(12, 40, 10, true).bytes);
+        EXPECT(wincov_lds(12, 40, 10, true, 256).bytes == wincov_lds(12, 40, 10, true, 257).bytes);
+        // random batches: offsets the 64-bit cumulative sums of both counts, the chunk behind the reduction scratch
+        std::vector<int32_t> s, c, pc;
+        unsigned r = 4242u;
+        auto rnd = [&](int lo, int hi) {
+            r = r * 1664525u + 1013904223u;
+            return lo + (int)((r >> 8) % (unsigned)(hi - lo + 1));
+        };
+        for (int b = 0; b < 3000; b++) {
+            const int nu = rnd(1, 64), f = rnd(0, 320 - nu);
+            int ne = rnd(1, 640);
+            while (!win_fits(nu + f, f, ne)) ne--;
+            s.insert(s.end(), {nu + f, f, ne});
+            c.push_back(b % 4 == 0 ? 0 : (b % 4 == 1 ? rnd(1, 300) : rnd(0, 4000000)));
+            pc.push_back(rnd(0, 9));
+        }
+        EXPECT(wincov_plan(3000, s.data(), pc.data(), c.data(), C) && C.desc.size() == 3000);
+        int64_t p = 0, q = 0;
+        size_t lds = 0;
+        for (int b = 0; b < 3000; b++) {
+            const WinCovDesc &d = C.desc[(size_t)b];
+            EXPECT(d.d.idx == b && d.nc == c[(size_t)b] && d.np == pc[(size_t)b] && d.coff == q && d.poff == p);
+            const WinCovLds L = wincov_lds(d.d.nv, d.d.ne, d.d.nv - d.d.f, true, d.nc), L0 = wincov_lds(d.d.nv, d.d.ne, d.d.nv - d.d.f, true);
+            // double4 rows on 32 bytes behind everything the plain layout holds; without candidates nothing is added
+            EXPECT(L.oC >= L0.bytes && L.oC < L0.bytes + 32 && L.oC % 32 == 0 && L.oRed == L0.oRed && L.oM == L0.oM);
+            EXPECT(L0.bytes == L0.oRed + 16 * WINCOV_THREADS && L.bytes <= WIN_MAX_LDS);
+            EXPECT(L.bytes == (d.nc ? L.oC + 32 * (size_t)(d.nc < WINCOV_CAND_CHUNK ? d.nc : WINCOV_CAND_CHUNK) : L0.bytes));
+            if (L.bytes > lds) lds = L.bytes;
+            p += d.np;
+            q += d.nc;
+        }
+        EXPECT(C.sum_c == q && C.sum_p == p && C.lds == lds && q > (int64_t)imax);
+        // asked for: an output needs candidates to fill it; the scale alone is a request; a count needs both arrays
+        EXPECT(!wingate_asked(0, false, false, false, false, false) && !wingate_asked(0, true, true, true, true, false));
+        EXPECT(wingate_asked(0, false, false, false, false, true) && wingate_asked(0, false, true, true, true, true));
+        EXPECT(wingate_asked(4, true, true, false, false, false) && wingate_asked(4, true, false, true, false, false));
+        EXPECT(wingate_asked(4, true, false, false, true, false) && wingate_asked(4, true, false, false, false, true));
+        EXPECT(!wingate_asked(4, true, false, false, false, false) && !wingate_asked(4, false, true, true, true, true));
+        EXPECT(!wingate_asked(-1, true, true, true, true, true) && !wingate_asked(lmin, true, true, true, true, true));
+        EXPECT(wingate_asked(lmax, true, true, false, false, false));
     }
     if (failures) {
         std::fprintf(stderr, "%d expectation(s) failed\n", failures);
