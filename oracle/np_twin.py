@@ -160,7 +160,11 @@ def irls(QQ, I, Q, f, cost=4, sigma=5 * np.pi / 180, max_iters=50, change_th=1e-
     return dict(Q=Q, weights=weights, iters=iters, scores=np.array(scores))
 
 
-def l1decode_pd(A, Hfun, y, pdmaxiter=2):  # :228-468, x0 = 0
+def l1decode_pd(A, Hfun, y, pdmaxiter=2, trace=None, solve=None):  # :228-468, x0 = 0
+    """trace: a list that receives one dict per primal-dual iteration -- bound ("l1", "l2", "f1", "f2": the guarded
+    bound of :347-380 that fixed the step, in that order on a tie; "one": none was below 1), trials (of the
+    back-tracking loop), sdg (after the iteration) and spread (max(sigx) / min(sigx) of its Hessian). solve: a callable
+    (H, rhs) -> dx in place of the SuperLU solve. Neither changes a bit of what is computed otherwise."""
     PDTOL, alpha, beta, mu = 1e-3, 0.01, 0.5, 10
     m, n = A.shape
     x = np.zeros(n)
@@ -186,21 +190,25 @@ def l1decode_pd(A, Hfun, y, pdmaxiter=2):  # :228-468, x0 = 0
         sigx = sig1 - sig2 ** 2 / sig1
         w1 = -1 / tau * (A.T @ (-1 / fu1 + 1 / fu2))
         w1p = w1 - A.T @ ((sig2 / sig1) * w2)
-        dx = sla.splu(Hfun(sigx)).solve(w1p)
+        dx = sla.splu(Hfun(sigx)).solve(w1p) if solve is None else solve(Hfun(sigx), w1p)
         Adx = A @ dx
         du = (w2 - sig2 * Adx) / sig1
         dl1 = -(l1 / fu1) * (Adx - du) - l1 - (1 / tau) / fu1
         dl2 = (l2 / fu2) * (Adx + du) - l2 - (1 / tau) / fu2
         Atdv = A.T @ (dl1 - dl2)
-        s = 1.0
-        for num, den in ((-l1, dl1), (-l2, dl2)):
+        s, bound = 1.0, "one"
+        for name, num, den in (("l1", -l1, dl1), ("l2", -l2, dl2)):
             sel = den < 0
             if sel.any():
-                s = min(s, (num[sel] / den[sel]).min())
-        for num, den in ((-fu1, Adx - du), (-fu2, -Adx - du)):
+                b = (num[sel] / den[sel]).min()
+                if b < s:
+                    s, bound = b, name
+        for name, num, den in (("f1", -fu1, Adx - du), ("f2", -fu2, -Adx - du)):
             sel = den > 0
             if sel.any():
-                s = min(s, (num[sel] / den[sel]).min())
+                b = (num[sel] / den[sel]).min()
+                if b < s:
+                    s, bound = b, name
         s *= 0.99
         suff, back = False, 0
         while not suff:
@@ -214,9 +222,13 @@ def l1decode_pd(A, Hfun, y, pdmaxiter=2):  # :228-468, x0 = 0
             s *= beta
             back += 1
             if back > 32:
+                if trace is not None:
+                    trace.append(dict(bound=bound, trials=back, sdg=sdg, spread=sigx.max() / sigx.min()))
                 return x, True
         x, u, Ax, Atv, l1, l2, fu1, fu2 = xp, up, Axp, Atvp, l1p, l2p, fu1p, fu2p
         sdg = -(fu1 @ l1 + fu2 @ l2)
+        if trace is not None:
+            trace.append(dict(bound=bound, trials=back, sdg=sdg, spread=sigx.max() / sigx.min()))
         tau = mu * 2 * m / sdg
         rcent = np.concatenate([-l1 * fu1, -l2 * fu2]) - 1 / tau
         resnorm = np.sqrt(rdp @ rdp + rcent @ rcent)
