@@ -390,12 +390,13 @@ class Graph:
         check(lib().irotavg_graph_get_residuals(self._h, _d(r), self.m), "get_residuals")
         return r
 
-    def ls_solve(self, allow_rc=()):
+    def ls_solve(self, allow_rc=(), return_rc=False):
+        """X (nu x 3); with return_rc the pair (return code, X): the handle's iterate is copied out whatever the code."""
         X = np.zeros((self.nu, 3), order="F")
         rc = lib().irotavg_graph_ls_solve(self._h, _d(X), self.nu)
         if rc != OK and rc not in allow_rc:
             raise IrotavgError(rc, "irotavg_graph_ls_solve")
-        return X
+        return (rc, X) if return_rc else X
 
     def update_weights(self, cost, sigma):
         check(lib().irotavg_graph_update_weights(self._h, cost, sigma), "update_weights")

@@ -74,11 +74,15 @@ __device__ __forceinline__ void gj_invert32(double (&d)[GJB], int l, double thr)
 // publish their halves of the pivot row, the 32 lanes that own column k publish a(r, k), and after one
 // wave-local LDS round trip every lane has its row's multiplier and its half of the pivot row: 16 fma
 // per pivot instead of 32 and no v_readlane (two per fma above; they, not the fma, set the 13 us).
-// Row k is scaled by the same fma as the others (multiplier (p - 1) / p: a_kj - ((p - 1) / p) a_kj =
-// a_kj / p), so the wave never diverges; column k is patched afterwards by its owners. LDS operations of a
-// wave execute in order, so one buffer serves every pivot. `buf`: 64 doubles.
+// Row k is scaled by the same fma as the others (multiplier (p - 1) / p: a_kj - ((p - 1) / p) a_kj = a_kj / p), so
+// the wave never diverges. For a pivot p > 1 that difference cancels and loses log10 p digits, so for pivots above
+// `exact_above` the addend is selected to 0 and the multiplier is -1 / p: a_kj / p = 0 + (1 / p) a_kj. (The
+// preconditioner's sweep inverts the UNSCALED coarse operator: with weights over six decades, pivots of 1e6, its
+// inverse was good to 1e-10 only: tests/test_gpu_pcg_iterates.py. A Jacobi-scaled sweep -- marginals.hip -- has no
+// pivot above 1 but for rounding; it and the one-level handle pass exact_above = HUGE_VAL and keep their arithmetic.) Column k is patched
+// afterwards by its owners. LDS operations of a wave execute in order, so one buffer serves every pivot. `buf`: 64 doubles.
 __device__ __forceinline__ void gj_invert32_split(double (&d)[GJB / 2], int l, int h, double thr,
-                                                  double *buf) {
+                                                  double *buf, double exact_above) {
     double *rowb = buf, *colb = buf + GJB;
 #pragma unroll
     for (int k = 0; k < GJB; k++) {
@@ -100,9 +104,10 @@ __device__ __forceinline__ void gj_invert32_split(double (&d)[GJB / 2], int l, i
         __builtin_amdgcn_wave_barrier();
         const double ip = (piv > thr && piv > 0.0) ? rcp_newton(piv) : 0.0;
         const bool me = l == k;
-        const double m = me ? (ip != 0.0 ? (piv - 1.0) * ip : 1.0) : ark * ip;
+        const bool big = me && piv > exact_above;
+        const double m = me ? (big ? -ip : (ip != 0.0 ? (piv - 1.0) * ip : 1.0)) : ark * ip;
 #pragma unroll
-        for (int j = 0; j < HALF; j++) d[j] = fma(-m, pr[j], d[j]);
+        for (int j = 0; j < HALF; j++) d[j] = fma(-m, pr[j], big ? 0.0 : d[j]);
         if (h == hk) d[jk] = me ? ip : -(ark * ip);
     }
 }
@@ -290,7 +295,8 @@ constexpr int GJ_LA_THREADS = 320;
 __global__ __launch_bounds__(GJ_LA_THREADS, 4) void k_gj_update_la(
     int npad, int k0, double *__restrict__ A, const double *__restrict__ Wr,
     const double *__restrict__ Wc, double *__restrict__ WrN, double *__restrict__ WcN,
-    const double *__restrict__ Sr, double *__restrict__ Sw, const double *__restrict__ maxdiag) {
+    const double *__restrict__ Sr, double *__restrict__ Sw, const double *__restrict__ maxdiag,
+    double exact_above) {
     __shared__ double Cs[GJT][GJB + 1];
     __shared__ double Rs[GJB][GJT + 4];   // Rt_k chunk; later the updated rows of block k+1
     __shared__ double Dv[GJB][GJB + 1];   // Rt_k[:, cols k+1], then D', then D'^-1
@@ -402,7 +408,7 @@ __global__ __launch_bounds__(GJ_LA_THREADS, 4) void k_gj_update_la(
         double d[GJB / 2];
 #pragma unroll
         for (int j = 0; j < GJB / 2; j++) d[j] = Dv[l][GJB / 2 * h + j];
-        gj_invert32_split(d, l, h, kDeadTol * maxdiag[0], Pv);
+        gj_invert32_split(d, l, h, kDeadTol * maxdiag[0], Pv, exact_above);
         __syncthreads();  // (1) the update waves are done with the Rt_k chunk in Rs
 #pragma unroll
         for (int j = 0; j < GJB / 2; j++) Dv[l][GJB / 2 * h + j] = d[j];
@@ -1263,6 +1269,10 @@ void dense_refresh(Graph &g) {
     }
     // look-ahead sweep: the update of step k also produces the panel of step k+1 (ping-pong panels)
     // and the snapshot of block (k+2, k+2) for the launch after it (ping-pong snapshots)
+    // The last level of a hierarchy scales the row of a pivot above 1 without cancellation (gj_invert32_split). A
+    // handle that is ONE dense level keeps the sweep's earlier arithmetic: its solves are refined to their attainable
+    // residual, and the referee tests of that path sit at cond x 2^-52 of one particular rounding.
+    const double exact_above = g.levels.size() > 1 ? 1.0 : HUGE_VAL;
     const size_t pan = (size_t)32 * npad;
     if (g.dense_wr.n < 2 * pan) g.dense_wr.alloc(2 * pan);
     if (g.dense_wc.n < 2 * pan) g.dense_wc.alloc(2 * pan);
@@ -1280,7 +1290,7 @@ void dense_refresh(Graph &g) {
         double *sr = g.dense_la.p + ((step + 1) & 1) * GJB * GJB, *sw = g.dense_la.p + (step & 1) * GJB * GJB;
         if (k0 + GJB < npad)
             hipLaunchKernelGGL(k_gj_update_la, dim3(nchunk * nchunk), dim3(GJ_LA_THREADS), 0, g.stream, npad, k0,
-                               g.dense_inv.p, wr, wc, wrn, wcn, sr, sw, g.dense_maxdiag.p);
+                               g.dense_inv.p, wr, wc, wrn, wcn, sr, sw, g.dense_maxdiag.p, exact_above);
         else
             hipLaunchKernelGGL(k_gj_update, dim3(nchunk * nchunk), dim3(256), 0, g.stream, npad, k0,
                                g.dense_inv.p, wr, wc);
@@ -1327,7 +1337,7 @@ void dense_invert_spd(Graph &g, double *A, int npad) {
         double *sr = g.dense_la.p + ((step + 1) & 1) * GJB * GJB, *sw = g.dense_la.p + (step & 1) * GJB * GJB;
         if (k0 + GJB < npad)
             hipLaunchKernelGGL(k_gj_update_la, dim3(nchunk * nchunk), dim3(GJ_LA_THREADS), 0, g.stream, npad, k0, A, wr,
-                               wc, wrn, wcn, sr, sw, g.dense_maxdiag.p);
+                               wc, wrn, wcn, sr, sw, g.dense_maxdiag.p, HUGE_VAL);  // (Jacobi-scaled: pivots of ~1 at most)
         else
             hipLaunchKernelGGL(k_gj_update, dim3(nchunk * nchunk), dim3(256), 0, g.stream, npad, k0, A, wr, wc);
         cur ^= 1;

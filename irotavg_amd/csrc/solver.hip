@@ -930,6 +930,29 @@ __global__ __launch_bounds__(kRowBlock) void k_jacobi_z(int n, const double *__r
     block_sum3_store(a0, a1, a2, part_rz + 4 * blockIdx.x);
 }
 
+// the last level of a hierarchy that the level cap ended without a dense inverse, where no other kernel of the cycle
+// can carry them (cycle_from): its correction is the Jacobi sweep already in x. y = x, with the convergence prologue
+// (CHECK) and the b.y partials (part_dot != nullptr) that the first and the last kernel of a deeper cycle carry
+template <bool CHECK>
+__global__ __launch_bounds__(kRowBlock) void k_jacobi_bottom(int n, const double4 *__restrict__ b,
+                                                             const double4 *__restrict__ x, double4 *__restrict__ y,
+                                                             double *__restrict__ part_dot,
+                                                             const double *__restrict__ part_rr, int nparts,
+                                                             int first, double rtol2, double *__restrict__ scal,
+                                                             int *__restrict__ flags) {
+    if (flags[FL_DONE]) return;
+    if (CHECK && pcg_check(part_rr, nparts, first, rtol2, scal, flags)) return;
+    double a0 = 0, a1 = 0, a2 = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const double4 bi = b[i], xi = x[i];
+        y[i] = xi;
+        a0 += bi.x * xi.x;
+        a1 += bi.y * xi.y;
+        a2 += bi.z * xi.z;
+    }
+    if (part_dot != nullptr) block_sum3_store(a0, a1, a2, part_dot + 4 * blockIdx.x);
+}
+
 // The guard of the banded direct solver's closure path (Graph::bcr_guard): the preconditioner IS a direct solve
 // (regularised: bcr.hip), so the convergence prologue and the r.z partials are kernels of their own around it.
 __global__ void k_pcg_check_only(const double *__restrict__ part_rr, int nparts, int first, double rtol2,
@@ -1737,9 +1760,22 @@ static void cycle_from(Graph &g, int from, bool check_first, bool dot_from, doub
     if (g.ndense > 0) {
         dense_apply(g, CL.b.p, CL.y.p, check, dot_from && last_is_from, part_dot, np_rr, first, rtol2);
         if (dot_from && last_is_from && np_dot) *np_dot = dense_apply_grid(g);
+    } else if (last_is_from || check) {
+        // level cap reached without a dense level, and no kernel before this one in the cycle (additive top level over
+        // a capped level 1; or over levels 1 and 2 with the level-1 down-sweep done by the update): the copy carries the
+        // convergence prologue itself, and the b.y partials when no up-sweep follows (nl == 1 never comes here: the
+        // caller's k_jacobi_z path)
+        const int ge = grid_for_elems(CL.n);
+        double *pd = (dot_from && last_is_from) ? part_dot : nullptr;
+        if (check)
+            hipLaunchKernelGGL((k_jacobi_bottom<true>), dim3(ge), dim3(kRowBlock), 0, g.stream, CL.n, CL.b.p, CL.x.p,
+                               CL.y.p, pd, g.part_rr.p, np_rr, first, rtol2, g.scal.p, g.flags.p);
+        else
+            hipLaunchKernelGGL((k_jacobi_bottom<false>), dim3(ge), dim3(kRowBlock), 0, g.stream, CL.n, CL.b.p, CL.x.p,
+                               CL.y.p, pd, g.part_rr.p, np_rr, first, rtol2, g.scal.p, g.flags.p);
+        if (pd && np_dot) *np_dot = ge;
     } else {
         // level cap reached without a dense level: its correction is the Jacobi sweep already in x.
-        // (check/dot are handled by the caller's k_jacobi_z path when nl == 1.)
         IRH_CHECK(hipMemcpyAsync(CL.y.p, CL.x.p, sizeof(double4) * (size_t)CL.n,
                                  hipMemcpyDeviceToDevice, g.stream));
     }
