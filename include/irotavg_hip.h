@@ -344,7 +344,8 @@ int irotavg_edge_diagnostics(int64_t m, int64_t n_total, int f, const int32_t *I
  * IROTAVG_HOST_BUILD=0) and keeps its own copies: the caller's buffers are only read and are free again on return.
  * opt->device (or the current device) is the handle's device. An edge index outside [0, n_total) is found by the
  * build's first kernel: IROTAVG_ERR_BAD_ARG, *g stays NULL. No HIP device: IROTAVG_ERR_NO_DEVICE. init_mst has no
- * device form (its sweep is order-dependent): bring initial rotations with irotavg_graph_set_rotations_dev. */
+ * device form at handle size (window-size problems: irotavg_window_init_mst_batch_dev below): bring initial rotations
+ * with irotavg_graph_set_rotations_dev. */
 int irotavg_graph_create_dev(irotavg_graph **g, int64_t m, int64_t n_total, int f, const int32_t *I_dev,
                              const double *QQ_dev, int64_t qq_rs, int64_t qq_cs, const irotavg_options *opt,
                              void *stream);
@@ -439,6 +440,27 @@ int irotavg_window_gate_batch_dev(int64_t nb, const int32_t *sizes, const int32_
                                   const double *weights_dev, double sigma, const int32_t *ncand, const int32_t *cand_I_dev,
                                   const double *cand_QQ_dev, int64_t cq_rs, int64_t cq_cs, double *angle_dev,
                                   double *pair_var_dev, double *chi2_dev, double *scale, int32_t *results, void *stream);
+
+/* irotavg_init_mst for many small problems in one call, on arrays that live on the device (docs/window_init_batch.md):
+ * the first link of init -> solve -> gate, one workgroup per problem, ONE launch. sizes, packing, limits, the stride
+ * rule, alignment and the lowest / highest-element check are those of irotavg_window_solve_batch_dev, so the Q_dev this
+ * call leaves can be passed on as it is.
+ *   Q_dev       the rows of fixed views (< f of their problem) are read and never written; the rows of free views are
+ *               written and never read, so they may be uninitialised (NaN included)
+ *   results     HOST, nb statuses, or NULL
+ * IROTAVG_ERR_BAD_ARG before any device work: what irotavg_window_solve_batch_dev refuses of nb, sizes, pointers, strides
+ * and alignment, and a problem with f < 1 (irotavg_init_mst refuses f <= 0: view 0 is the anchor and must be fixed); no
+ * HIP device: IROTAVG_ERR_NO_DEVICE. The edge ids are read on the device alone: the workgroup of a problem with an id
+ * outside [0, n_total) reports IROTAVG_ERR_BAD_ARG and indexes nothing with it; a problem with a view no edge reaches
+ * from view 0 reports IROTAVG_ERR_NOT_SPANNING (as on the host, a fixed view other than 0 counts as seen only once an
+ * edge reaches it). A problem that fails keeps every byte of its rows of Q_dev -- irotavg_init_mst itself may have
+ * written some of them before it fails --; the other problems are computed. The launch goes on `stream` itself: inputs
+ * may still be in flight there, Q_dev is ready for whatever is enqueued on it next. The call blocks until every result
+ * record has arrived and returns the first non-zero status in problem order. On success every problem's rows are
+ * bitwise those irotavg_init_mst leaves on that problem alone. */
+int irotavg_window_init_mst_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                      int64_t qq_rs, int64_t qq_cs, double *Q_dev, int64_t q_rs, int64_t q_cs,
+                                      int32_t *results, void *stream);
 
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash

@@ -50,6 +50,7 @@ SYMBOLS = [
     "irotavg_graph_rotation_variance_dev", "irotavg_graph_edge_diagnostics_dev", "irotavg_window_solve_batch_dev",
     "irotavg_window_uncertainty", "irotavg_window_uncertainty_batch_dev",
     "irotavg_window_gate", "irotavg_window_gate_batch_dev",
+    "irotavg_window_init_mst_batch_dev",
 ]
 
 
@@ -177,6 +178,8 @@ def lib():
     L.irotavg_window_gate_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp, C.c_int64,
                                                 C.c_int64, vp, C.c_double, C.POINTER(C.c_int32), vp, vp, C.c_int64,
                                                 C.c_int64, vp, vp, vp, _dp, C.POINTER(C.c_int32), vp]
+    L.irotavg_window_init_mst_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp,
+                                                    C.c_int64, C.c_int64, C.POINTER(C.c_int32), vp]
     L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
     L.irotavg_viewgraph_num_connections.restype = C.c_int64

@@ -387,6 +387,30 @@ int irotavg_window_solve_batch_dev(int64_t nb, const int32_t *sizes, const int32
     });
 }
 
+// irotavg_init_mst on many small problems on packed device arrays, one workgroup each, one launch
+// (docs/window_init_batch.md): the arrays, the plan and the checks of the call above; view 0 must be fixed.
+int irotavg_window_init_mst_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                      int64_t qq_rs, int64_t qq_cs, double *Q_dev, int64_t q_rs, int64_t q_cs,
+                                      int32_t *results, void *stream) {
+    if (!I_dev || !QQ_dev || !Q_dev) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        WinBatchPlan plan;
+        if (!winbatch_plan(nb, sizes, 1, plan)) return IROTAVG_ERR_BAD_ARG;  // kernel 1: one list, in the caller's order
+        for (const WinDesc &d : plan.desc)
+            if (d.f < 1) return IROTAVG_ERR_BAD_ARG;  // irotavg_init_mst refuses f <= 0
+        if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, nullptr, plan.sum_m, plan.sum_n))
+            return IROTAVG_ERR_BAD_ARG;
+        if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!win_arrays_dev_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, nullptr, plan.sum_m, plan.sum_n, device))
+            return IROTAVG_ERR_BAD_ARG;
+        const WinBatchArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
+                               nullptr};
+        return window_init_mst_batch_dev(plan, device, A, results, static_cast<hipStream_t>(stream));
+    });
+}
+
 // The uncertainty of many small problems on packed device arrays, one workgroup each, one launch
 // (docs/window_uncertainty_batch.md). Handle-free and on the caller's stream itself, as irotavg_window_solve_batch_dev.
 int irotavg_window_uncertainty_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,

@@ -322,6 +322,11 @@ struct WinBatchArrays {
 };
 int window_solve_batch_dev(const WinBatchPlan &plan, int device, const WinBatchArrays &A, int cost, double sigma,
                            int l1_max, int irls_max, double change_th, int32_t *results, hipStream_t stream);
+// winmst.hip: irotavg_init_mst on every problem of such a batch in one launch (irotavg_window_init_mst_batch_dev;
+// docs/window_init_batch.md). plan: winbatch_plan(..., kernel = 1, ...), every f >= 1; A.weights unused. Free rows of
+// A.Q are written and never read, fixed rows read and never written.
+int window_init_mst_batch_dev(const WinBatchPlan &plan, int device, const WinBatchArrays &A, int32_t *results /* host */,
+                              hipStream_t stream);
 // wincov.hip: the uncertainty queries of a window-size problem in one kernel launch (docs/viewgraph_uncertainty.md)
 struct WinCov;
 WinCov *wincov_new();

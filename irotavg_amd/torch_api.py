@@ -365,3 +365,36 @@ def window_gate_batch(sizes, edge_index, QQ, Q, cand_index, cand_QQ, ncand, weig
     if rc != capi.OK and rc not in allow_rc:
         raise capi.IrotavgError(rc, "irotavg_window_gate_batch_dev")
     return dict(rc=rc, scale=scale, status=status, **outs)
+
+
+# ---- their initialisation in one call (irotavg_window_init_mst_batch_dev, docs/window_init_batch.md) ----------------------
+def window_init_mst_batch(sizes, edge_index, QQ, Q, allow_rc=()):
+    """capi.init_mst on nb independent window-size problems, one workgroup per problem, in one launch on torch's current
+    stream: the call in front of window_solve_batch. sizes, edge_index, QQ, Q: as window_solve_batch takes them, every
+    problem with f >= 1 (view 0 is the anchor).
+
+    Q is updated in place: the rows of free views are written (they are never read, so they may be uninitialised), the
+    rows of fixed views are read and never written. Returns dict(rc, Q, status); status is a host numpy array of nb
+    entries. rc is the first non-zero status in problem order (ERR_BAD_ARG: an edge id outside the problem,
+    ERR_NOT_SPANNING: a view no edge reaches from view 0); anything but OK raises unless listed in allow_rc. A problem
+    that fails keeps its rows of Q as they were. On success the rows are bitwise those of capi.init_mst on each problem
+    alone."""
+    import numpy as np
+    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2), placed=False)
+    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), placed=False)
+    _check(Q, "Q", (torch.float64,), (sum_n, 4), placed=False)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), device)
+    _check(Q, "Q", (torch.float64,), (sum_n, 4), device)
+    nb = len(s32)
+    status = np.zeros(nb, dtype=np.int32)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        rc = capi.lib().irotavg_window_init_mst_batch_dev(
+            nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(Q),
+            *matrix_strides(Q), status.ctypes.data_as(C.POINTER(C.c_int32)), _stream(device))
+    if rc != capi.OK and rc not in allow_rc:
+        raise capi.IrotavgError(rc, "irotavg_window_init_mst_batch_dev")
+    return dict(rc=rc, Q=Q, status=status)
