@@ -462,6 +462,38 @@ int irotavg_window_init_mst_batch_dev(int64_t nb, const int32_t *sizes, const in
                                       int64_t qq_rs, int64_t qq_cs, double *Q_dev, int64_t q_rs, int64_t q_cs,
                                       int32_t *results, void *stream);
 
+/* Cycle-consistency screening of relative rotations before any solve (docs/cycle_check.md): for every edge k = (a, b) the
+ * triangles it closes with two other edges, (k1, k2) with k1 joining b and c, k2 joining c and a, c outside {a, b}, no
+ * self loop among the three; parallel edges are distinct, every pair counts. The error of a triangle is the angle of
+ * q(k2, c->a) (x) q(k1, b->c) (x) q(k, a->b), wrapped into [-pi, pi) as the edge residual is, in absolute value;
+ * q(k, a_k->b_k) = QQ_k and q(k, b_k->a_k) is QQ_k with w negated. No poses, no weights, no fixed views, any topology.
+ *   I           m pairs of ids in [0, n_total)
+ *   QQ, ldqq    m x 4 column-major [x y z w], ldqq >= m; taken as given, not normalised
+ *   threshold   radians, >= 0 (+inf accepted)
+ *   tri_count   m int32 or NULL: triangles of edge k (a count above 2^31 - 1 is stored as 2^31 - 1)
+ *   tri_ok      m int32 or NULL: those with error <= threshold
+ *   tri_min     m doubles or NULL: the smallest error, +inf without a triangle
+ *   summary     4 int64 on the HOST or NULL: sum of tri_count; edges with tri_ok >= 1; edges with tri_count >= 1 and
+ *               tri_ok == 0; edges with tri_count == 0
+ * A triangle whose error is not finite counts, is never ok and leaves tri_min alone. A self loop gets 0, 0, +inf.
+ * IROTAVG_ERR_BAD_ARG before any device work: NULL I or QQ, m <= 0 or above 0x3fffffff, n_total <= 0 or above 0x7fffffff,
+ * a threshold that is NaN or negative, ldqq < m. No HIP device: IROTAVG_ERR_NO_DEVICE. An id outside [0, n_total) is found
+ * on the device before anything is indexed with it: IROTAVG_ERR_BAD_ARG. Outputs are written on success alone; with all
+ * four NULL the call is the id check. Memory is O(m) whatever n_total is. Deterministic: two calls give the same bytes. */
+int irotavg_cycle_check(int64_t m, int64_t n_total, const int32_t *I, const double *QQ, int64_t ldqq, double threshold,
+                        int32_t *tri_count, int32_t *tri_ok, double *tri_min, int64_t summary[4]);
+/* The same on arrays that live on the device: I_dev m pairs (8-byte aligned), QQ_dev a strided m x 4 matrix under the
+ * stride rule above, tri_min_dev 8-byte and the count arrays 4-byte aligned, the lowest and highest element of every array
+ * device memory of the current device (else IROTAVG_ERR_BAD_ARG, before any kernel). The kernels go on `stream` itself:
+ * inputs may still be in flight there, the outputs are ready for whatever is enqueued on it next. The call blocks until
+ * the error word and the summary are back. Bitwise the host call. */
+int irotavg_cycle_check_dev(int64_t m, int64_t n_total, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                            int64_t qq_cs, double threshold, int32_t *tri_count_dev, int32_t *tri_ok_dev,
+                            double *tri_min_dev, int64_t summary[4] /* HOST */, void *stream);
+/* Testing and measuring aid, NOT a stable interface (it may change or go without notice): the lanes that share one edge
+ * in the triangle kernel, 8, 16, 32 or 64; 0 gives the default back. Process-wide. The results do not depend on it. Returns the width in force before the call, IROTAVG_ERR_BAD_ARG for any other value. */
+int irotavg_cycle_check_group(int lanes);
+
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash
  * each, followed by the scalars that choose kernels (level shapes, far-entry count, fused-assembly / two-launch

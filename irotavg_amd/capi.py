@@ -51,6 +51,7 @@ SYMBOLS = [
     "irotavg_window_uncertainty", "irotavg_window_uncertainty_batch_dev",
     "irotavg_window_gate", "irotavg_window_gate_batch_dev",
     "irotavg_window_init_mst_batch_dev",
+    "irotavg_cycle_check", "irotavg_cycle_check_dev", "irotavg_cycle_check_group",
 ]
 
 
@@ -180,6 +181,10 @@ def lib():
                                                 C.c_int64, vp, vp, vp, _dp, C.POINTER(C.c_int32), vp]
     L.irotavg_window_init_mst_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp,
                                                     C.c_int64, C.c_int64, C.POINTER(C.c_int32), vp]
+    L.irotavg_cycle_check.argtypes = [C.c_int64, C.c_int64, _ip, _dp, C.c_int64, C.c_double, _ip, _ip, _dp, _i64p]
+    L.irotavg_cycle_check_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, vp, vp, vp, _i64p,
+                                          vp]
+    L.irotavg_cycle_check_group.argtypes = [C.c_int]
     L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
     L.irotavg_viewgraph_num_connections.restype = C.c_int64
@@ -496,8 +501,11 @@ def rotation_variance(I, QQ, Q, weights, f, pairs=None, marginals=True, allow_rc
     """irotavg_rotation_variance: the query without a handle (through the kept one-shot handle), from the rotations and
     weights irls returned."""
     I = edges(I)
-    QQ = fmat(QQ)
+    # Copies in the order ral.l1ra / ral.irls make theirs. The kept one-shot handle is found by the arrays' addresses
+    # first, so a hit needs the allocator to hand these copies the blocks the last call's copies left; the same requests in
+    # the same order make that likelier (QQ no longer lands in Q's freed block), they do not guarantee it.
     Q = fmat(Q)
+    QQ = fmat(QQ)
     w = np.ascontiguousarray(weights, dtype=np.float64)
     n_total = Q.shape[0]
     return _variance_call(lambda *a: lib().irotavg_rotation_variance(len(I), n_total, int(f), _i(I), _d(QQ),
@@ -518,8 +526,8 @@ def edge_diagnostics(I, QQ, Q, weights, f, edge_var=True, leverage=True, chi2=Tr
     """irotavg_edge_diagnostics: the query without a handle (through the kept one-shot handle), from the rotations and
     weights irls returned."""
     I = edges(I)
+    Q = fmat(Q)    # (the order of ral.irls's copies, as in rotation_variance)
     QQ = fmat(QQ)
-    Q = fmat(Q)
     w = np.ascontiguousarray(weights, dtype=np.float64)
     n_total = Q.shape[0]
     return _edge_call(lambda *a: lib().irotavg_edge_diagnostics(len(I), n_total, int(f), _i(I), _d(QQ), QQ.shape[0],
@@ -618,6 +626,40 @@ def window_gate(I, QQ, Q, f, cand_I, cand_QQ, weights=None, sigma=5 * np.pi / 18
     if rc != OK and rc not in allow_rc:
         raise IrotavgError(rc, "irotavg_window_gate")
     return dict(rc=rc, angle=out[0], pair_var=out[1], chi2=out[2], scale=scale.value)
+
+
+SUMMARY_FIELDS = ("triangles", "supported", "contradicted", "untested")
+
+
+def cycle_check(I, QQ, n_total, threshold=5 * np.pi / 180, count=True, ok=True, min_err=True, summary=True, allow_rc=()):
+    """irotavg_cycle_check (docs/cycle_check.md): the triangle test of every edge, before any solve. Returns dict(rc,
+    tri_count, tri_ok (int32, m each), tri_min (float64, m), summary (dict of SUMMARY_FIELDS)); an output that was not
+    asked for is None. Counts are preset to -1 and tri_min to NaN, and written only on success."""
+    I = edges(I)
+    QQ = fmat(QQ)
+    m = len(I)
+    if QQ.shape != (m, 4):
+        raise ValueError("QQ must be (%d, 4)" % m)
+    cnt = np.full(m, -1, dtype=np.int32) if count else None
+    okc = np.full(m, -1, dtype=np.int32) if ok else None
+    mn = np.full(m, np.nan) if min_err else None
+    s = (C.c_int64 * 4)(-1, -1, -1, -1)
+    rc = lib().irotavg_cycle_check(m, int(n_total), _i(I), _d(QQ), QQ.shape[0], float(threshold),
+                                   None if cnt is None else _i(cnt), None if okc is None else _i(okc),
+                                   None if mn is None else _d(mn), s if summary else None)
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_cycle_check")
+    return dict(rc=rc, tri_count=cnt, tri_ok=okc, tri_min=mn,
+                summary=dict(zip(SUMMARY_FIELDS, (int(v) for v in s))) if summary and rc == OK else None)
+
+
+def cycle_check_group(lanes):
+    """irotavg_cycle_check_group: the lanes per edge of the triangle kernel (8, 16, 32, 64; 0: the default); returns the
+    width in force before. A measuring aid: no result depends on it."""
+    old = lib().irotavg_cycle_check_group(int(lanes))
+    if old < 0:
+        raise IrotavgError(old, "irotavg_cycle_check_group")
+    return old
 
 
 def plan_host(world, rank, I, n_total, f):

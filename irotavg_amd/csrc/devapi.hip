@@ -501,4 +501,46 @@ int irotavg_window_gate_batch_dev(int64_t nb, const int32_t *sizes, const int32_
     });
 }
 
+// The triangle test of every edge (docs/cycle_check.md; the kernels: cycles.hip). Handle-free; the device form runs on the
+// caller's stream itself, as the batched window calls do.
+static bool cycle_sizes_ok(int64_t m, int64_t n_total, double threshold) {
+    return m > 0 && m <= 0x3fffffffLL && n_total > 0 && n_total <= 0x7fffffffLL && threshold >= 0.0;  // (NaN: false)
+}
+
+int irotavg_cycle_check(int64_t m, int64_t n_total, const int32_t *I, const double *QQ, int64_t ldqq, double threshold,
+                        int32_t *tri_count, int32_t *tri_ok, double *tri_min, int64_t summary[4]) {
+    if (!I || !QQ || !cycle_sizes_ok(m, n_total, threshold) || ldqq < m) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        const CycleArrays A{I, QQ, 1, (long long)ldqq, tri_count, tri_ok, tri_min};
+        return cycle_check_host(m, n_total, A, threshold, summary);
+    });
+}
+
+int irotavg_cycle_check_dev(int64_t m, int64_t n_total, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                            int64_t qq_cs, double threshold, int32_t *tri_count_dev, int32_t *tri_ok_dev,
+                            double *tri_min_dev, int64_t summary[4], void *stream) {
+    if (!I_dev || !QQ_dev || !cycle_sizes_ok(m, n_total, threshold) || !strides_ok(m, 4, qq_rs, qq_cs)) return IROTAVG_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(I_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(QQ_dev) & 7) != 0 ||
+        (reinterpret_cast<uintptr_t>(tri_min_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(tri_count_dev) & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(tri_ok_dev) & 3) != 0)
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!dev_ptr_ok(I_dev, device) || !dev_ptr_ok(I_dev + 2 * m - 1, device) ||
+            !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device))
+            return IROTAVG_ERR_BAD_ARG;
+        int32_t *const counts[2] = {tri_count_dev, tri_ok_dev};
+        for (int32_t *p : counts)
+            if (p && (!dev_ptr_ok(p, device) || !dev_ptr_ok(p + m - 1, device))) return IROTAVG_ERR_BAD_ARG;
+        if (tri_min_dev && !dev_vector_ok(tri_min_dev, m, device)) return IROTAVG_ERR_BAD_ARG;
+        const CycleArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, tri_count_dev, tri_ok_dev, tri_min_dev};
+        return cycle_check_dev(m, n_total, A, threshold, summary, static_cast<hipStream_t>(stream));
+    });
+}
+
+int irotavg_cycle_check_group(int lanes) { return cycle_check_group(lanes); }
+
 }  // extern "C"

@@ -327,6 +327,20 @@ int window_solve_batch_dev(const WinBatchPlan &plan, int device, const WinBatchA
 // A.Q are written and never read, fixed rows read and never written.
 int window_init_mst_batch_dev(const WinBatchPlan &plan, int device, const WinBatchArrays &A, int32_t *results /* host */,
                               hipStream_t stream);
+// cycles.hip: the triangle test of every edge (irotavg_cycle_check[_dev]; docs/cycle_check.md). The arguments have been
+// checked. The device form runs on `stream` and writes the caller's device arrays; the host form uploads, runs the same
+// kernels and copies back. Both block until the error word and the summary are back; outputs may each be nullptr.
+struct CycleArrays {
+    const int32_t *I;  // m pairs
+    const double *QQ;  // strided m x 4 (device form) / column-major with qq_cs = ldqq, qq_rs = 1 (host form)
+    long long qq_rs, qq_cs;
+    int32_t *tri_count, *tri_ok;
+    double *tri_min;
+};
+int cycle_check_dev(int64_t m, int64_t n_total, const CycleArrays &A, double threshold, int64_t *summary /* host */,
+                    hipStream_t stream);
+int cycle_check_host(int64_t m, int64_t n_total, const CycleArrays &A, double threshold, int64_t *summary);
+int cycle_check_group(int lanes);  // irotavg_cycle_check_group
 // wincov.hip: the uncertainty queries of a window-size problem in one kernel launch (docs/viewgraph_uncertainty.md)
 struct WinCov;
 WinCov *wincov_new();

@@ -151,6 +151,12 @@ class TorchGraph(capi.Graph):
             raise capi.IrotavgError(rc, "irotavg_graph_edge_diagnostics_dev")
         return dict(rc=rc, edge_var=outs[0], leverage=outs[1], chi2=outs[2], scale=scale.value)
 
+    def cycle_check(self, edge_index, QQ, threshold=5 * 3.141592653589793 / 180, **kw):
+        """cycle_check (below) of the tensors passed, with the handle's n_total: the handle keeps no copy of the caller's
+        arrays in their layout, and the screen needs neither its poses nor its weights."""
+        _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
+        return cycle_check(edge_index, QQ, self.n_total, threshold, **kw)
+
     # the host-array forms of the parent stay reachable under their own names
     host_set_rotations = capi.Graph.set_rotations
     host_set_weights = capi.Graph.set_weights
@@ -398,3 +404,56 @@ def window_init_mst_batch(sizes, edge_index, QQ, Q, allow_rc=()):
     if rc != capi.OK and rc not in allow_rc:
         raise capi.IrotavgError(rc, "irotavg_window_init_mst_batch_dev")
     return dict(rc=rc, Q=Q, status=status)
+
+
+# ---- the triangle test before any solve (irotavg_cycle_check_dev, docs/cycle_check.md) ------------------------------------
+def cycle_check(edge_index, QQ, n_total, threshold=5 * 3.141592653589793 / 180, count=True, ok=True, min_err=True,
+                summary=True, allow_rc=()):
+    """Cycle-consistency screening of relative rotations on torch's current stream: for every edge the triangles it closes
+    with two other edges, how many of them are consistent within `threshold` radians, and the smallest inconsistency. No
+    poses, no weights, no fixed views, any topology.
+
+    edge_index: (m, 2) int32 or int64 (narrowed on the device: a value outside int32 range becomes an id the device check
+    refuses), QQ: (m, 4) float64 with any strides. count / ok / min_err: True (a new tensor), False / None (not computed),
+    or a contiguous tensor of m entries to fill (int32 for the counts, float64 for min_err). Returns dict(rc, tri_count,
+    tri_ok, tri_min, summary); summary is a host dict of capi.SUMMARY_FIELDS, or None. An id outside [0, n_total) gives
+    ERR_BAD_ARG with every output byte as it was; anything but OK raises unless listed in allow_rc. The call blocks until
+    the summary is back."""
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), placed=False)
+    m = int(edge_index.shape[0])
+    _check(QQ, "QQ", (torch.float64,), (m, 4), placed=False)
+    wants = (("count", count, torch.int32), ("ok", ok, torch.int32), ("min_err", min_err, torch.float64))
+    for name, want, dt in wants:
+        if not (want is True or want is False or want is None):
+            _check(want, name, (dt,), (m,), placed=False)
+    n_total, threshold = int(n_total), float(threshold)
+    if m < 1:
+        raise ValueError("edge_index must have at least one row")
+    if not 0 < n_total <= INT32_MAX:
+        raise ValueError("n_total must lie in [1, 2^31 - 1], got %d" % n_total)
+    if not threshold >= 0.0:
+        raise ValueError("threshold must be a non-negative angle, got %r" % threshold)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (m, 4), device)
+    outs = []
+    for name, want, dt in wants:
+        if want is True:
+            outs.append(torch.empty(m, dtype=dt, device=device))
+        elif want is False or want is None:
+            outs.append(None)
+        else:
+            _check(want, name, (dt,), (m,), device)
+            if not want.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+            outs.append(want)
+    s = (C.c_int64 * 4)(-1, -1, -1, -1)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        rc = capi.lib().irotavg_cycle_check_dev(m, n_total, _ptr(ei), _ptr(QQ), *matrix_strides(QQ), threshold,
+                                                *[None if t is None else _ptr(t) for t in outs], s if summary else None,
+                                                _stream(device))
+    if rc != capi.OK and rc not in allow_rc:
+        raise capi.IrotavgError(rc, "irotavg_cycle_check_dev")
+    return dict(rc=rc, tri_count=outs[0], tri_ok=outs[1], tri_min=outs[2],
+                summary=dict(zip(capi.SUMMARY_FIELDS, (int(v) for v in s))) if summary and rc == capi.OK else None)
