@@ -261,9 +261,17 @@ int irotavg_graph_time_kernel(irotavg_graph *g, int which, int reps, double *ms_
  * levels the long-range edges (loop closures) the solver handles by its Woodbury correction, then 1 if the level-0
  * reduction of the handle's most recent assembly + solve (an IRLS iteration, irotavg_graph_ls_solve) assembled level 0
  * itself -- one launch instead of K3 and the reduction: a handle without closures whose chunks of eight blocks are whole
- * 64-row slices (blocks of 8 / 16 / 24 / 32), IROTAVG_BCR_NO_FUSED_ASM=1 not set -- and 0 if it did not. which of
- * irotavg_graph_time_kernel: 19 = a whole solve (2 L launches), 20 + l = the reduction of level l, 40 + l = its way
- * back. Returns the number of values written (<= cap) or a negative error. */
+ * 64-row slices (blocks of 8 / 16 / 24 / 32), IROTAVG_BCR_NO_FUSED_ASM=1 not set -- and 0 if it did not. Three more
+ * values follow, about the factor of the UNIT-WEIGHT operator: irls starts from weights of one, so the first system of
+ * every irls call on a handle has the same operator, and a handle of three or more levels with blocks of 8 / 16 / 24 and
+ * no closures keeps that factor from its first irls on (the first solve of every later call is a pass over the
+ * right-hand sides alone, bit-identical to the full solve; IROTAVG_BCR_NO_UNIT_FACTOR=1: never kept;
+ * irotavg_trim_memory releases it, the next irls rebuilds it): 1 if the handle holds a valid factor else 0, the solves
+ * served from it so far, its bytes of device memory. which of
+ * irotavg_graph_time_kernel: 19 = a whole solve (2 L launches, always the FULL reduction), 20 + l = the reduction of
+ * level l, 40 + l = its way back; 17 = the right-hand-side-only solve over the kept unit-weight factor (all four
+ * launches, level 0 assembling its slices as in irls), 18 = its upper launch alone -- both IROTAVG_ERR_BAD_ARG on a
+ * handle without a valid factor. Returns the number of values written (<= cap) or a negative error. */
 int irotavg_graph_direct_info(irotavg_graph *g, int64_t *info, int cap);
 
 /* The direct solver has no tolerance and no residual test of its own (SuiteSparseQR / UMFPACK in ral/l1_irls.cpp:131-184,

@@ -426,17 +426,23 @@ class Graph:
     def direct_info(self):
         """irotavg_graph_direct_info: dict(block, levels=[dict(blocks, chunks, reduced)], closures, fused_assembly) of the
         banded direct solver; fused_assembly: the level-0 reduction of the handle's most recent assembly + solve also
-        assembled level 0 (no launch of K3 in front of it)."""
+        assembled level 0 (no launch of K3 in front of it). unit_factor: 1 when the handle keeps the factor of the
+        unit-weight operator (the first system of every irls call), unit_factor_solves: solves served from it so far,
+        unit_factor_bytes: its device memory."""
         out = (C.c_int64 * 64)()
         k = lib().irotavg_graph_direct_info(self._h, out, 64)
         if k < 0:
             raise IrotavgError(k, "direct_info")
         if out[0] == 0:
-            return dict(block=0, levels=[], closures=0, fused_assembly=0)
+            return dict(block=0, levels=[], closures=0, fused_assembly=0, unit_factor=0, unit_factor_solves=0,
+                        unit_factor_bytes=0)
         nl = int(out[1])
         return dict(block=int(out[0]), levels=[dict(blocks=int(out[2 + 3 * l]), chunks=int(out[3 + 3 * l]),
                                                     reduced=int(out[4 + 3 * l])) for l in range(nl)],
-                    closures=int(out[2 + 3 * nl]), fused_assembly=int(out[3 + 3 * nl]) if k > 3 + 3 * nl else 0)
+                    closures=int(out[2 + 3 * nl]), fused_assembly=int(out[3 + 3 * nl]) if k > 3 + 3 * nl else 0,
+                    unit_factor=int(out[4 + 3 * nl]) if k > 4 + 3 * nl else 0,
+                    unit_factor_solves=int(out[5 + 3 * nl]) if k > 5 + 3 * nl else 0,
+                    unit_factor_bytes=int(out[6 + 3 * nl]) if k > 6 + 3 * nl else 0)
 
     def direct_residual(self):
         """irotavg_graph_direct_residual: ||b - A x|| / ||b|| per coordinate of the most recent direct solve."""

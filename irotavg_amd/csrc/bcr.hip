@@ -66,6 +66,7 @@ struct BcrUpLevel {
     int nb, nred, nch;
     gp_cd inD, inR, inXD, inXR, inXG;  // from the level below
     gp_d W, sepD, sepR, extD, extR, extG;
+    gp_d stD, stP, stQ;  // the unit-weight factor's operands of this level (BcrUnit; null: the handle keeps none)
 };
 struct BcrUpArgs {
     int nl;  // levels of the launch; lev[0] = level 1 of the solve
@@ -86,6 +87,7 @@ struct BcrUpArgs {
     // counts itself -- nobody else waits a second for it --, and the top workgroup poisons the solution when the word is
     // set; the host then repeats the solve level by level (bcr_up_failed)
     gp_i fail;
+    gp_d tst;  // the unit-weight factor's part of the single-workgroup top (BcrUnit::top)
 };
 
 struct BcrLevel {
@@ -96,7 +98,35 @@ struct BcrLevel {
     DevBuf<double> sepD, sepR, extD, extR, extG;  // per chunk: what the next level is assembled from
     DevBuf<double> x;                             // nch * 8 blocks of B x 3 (levels >= 1)
 };
+// The factor of the UNIT-WEIGHT operator (the first system of every irls call: weights.setOnes(), ral/l1_irls.cpp:577), kept
+// from the first such solve of the handle on: per level and eliminated block the three A-operands of its products exactly as
+// they read them (D_i^-1, P before phase 2 overwrites it, Q) and a private W whose W_P / W_Q the ways back read and whose W_R
+// the right-hand-side-only pass rewrites; for the single-workgroup top per scheduled elimination r * 4 + e five blocks
+// (D_i^-1, P, Q, W_P, W_Q) and, in slot kTopUnitLast, the inverse of the block that is left. Only run_irls's unit-weight
+// solve writes or reads any of this.
+constexpr int kTopUnitLast = 5 * 4 * kTopRounds;
+struct BcrUnitLevel {
+    DevBuf<double> Wu, Di, P, Q;
+};
+struct BcrUnit {
+    std::vector<BcrUnitLevel> lev;
+    DevBuf<double> top;
+    DevBuf<BcrUpArgs> up_args;  // k_bcr_reduce_up's arguments with W = Wu and the operand arrays (written once)
+    bool valid = false;         // a filling solve has ended with a finite score
+    int last = 0;               // what the most recent solve did: 0 nothing, 1 filled, 2 was served from the store
+    unsigned epoch = 0;         // bcr_unit_trim()'s count when the arrays were allocated
+    int64_t solves = 0, bytes = 0;
+    void release() {
+        lev.clear();
+        top.release();
+        up_args.release();
+        valid = false;
+        last = 0;
+        bytes = 0;
+    }
+};
 struct BcrState {
+    BcrUnit unit;
     int B = 0;
     int NR = 3;    // right-hand-side columns riding along: 3, or 19 with closures
     int nfar = 0;  // long-range edges (loop closures) handled by the Woodbury correction
@@ -651,7 +681,13 @@ __device__ __forceinline__ void bcr_st(double *p, double v) {
 // The reduction of one chunk (the body of k_bcr_reduce; k_bcr_reduce_up runs it for the chunks of several levels in
 // turn). sDG: 16 blocks, sR: 9 right-hand-side slots, sZ: 2 doubles of LDS. COH: the level below was written, and this
 // level's separator data is read, inside the same launch (bcr_ld / bcr_st).
-template <int B, int NR, bool L0, bool TOP, int NW, bool COH>
+// UF (the unit-weight factor, BcrUnit): 1 = the full reduction also keeps the operands of its products (Dinvg, stP, stQ; W is
+// the store's Wu); 2 = the RIGHT-HAND-SIDE-ONLY pass over a kept factor: the gather takes the right-hand sides alone, no
+// sweep -- D_i^-1, P and Q are the stored bits, read from memory as the products' A-operands --, and the three phases run
+// for the one column tile that holds W_R (nt = NT - 1 = 2 B / 16: for B = 8 / 16 / 24 it holds nothing else), on the wave
+// that owns the elimination's sweep in the full form. A column tile of a matrix-core product does not depend on the other
+// tiles, the K order and the subtractions of the puts are the same code: R_a, R_c, W_R, sepR, extR come out bit for bit.
+template <int B, int NR, bool L0, bool TOP, int NW, bool COH, int UF = 0>
 __device__ __forceinline__ void bcr_reduce_body(
     const int chunk, double (*sDG)[B * B], double (*sR)[B * NR], double *sZ,
 
@@ -663,7 +699,7 @@ __device__ __forceinline__ void bcr_reduce_body(
     int nfar, const int *__restrict__ far_i, const int *__restrict__ far_j, int ext0, const int *__restrict__ bptr,
     const int *__restrict__ bghost, const double *__restrict__ bval, const int *__restrict__ ghost_extcol, int place,
     long long *__restrict__ stamps, double *__restrict__ Dinvg, double *__restrict__ topDinv, int *__restrict__ deadctr,
-    int reg) {
+    int reg, double *__restrict__ stP = nullptr, double *__restrict__ stQ = nullptr) {
     typedef BcrDim<B, NR> Dm;
     constexpr int BB = B * B;
     double(*sD)[BB] = sDG;       // sD[0] becomes the chunk's contribution to the separator before it
@@ -676,6 +712,99 @@ __device__ __forceinline__ void bcr_reduce_body(
     constexpr int NT_ = NW * 64;  // threads
     const int kreal = nb - chunk * 8 < 8 ? nb - chunk * 8 : 8;  // real blocks of this chunk
     const bool placed = place && kreal < 8;                      // ... placed so that the last one is the separator
+
+    if constexpr (UF == 2) {
+        static_assert(NR == 3 && !TOP && 16 * (Dm::NT - 1) == 2 * B, "the last column tile holds the right-hand sides alone");
+        constexpr int XB = B * NR;
+        for (int e = tid; e < 9 * XB; e += NT_) (&sR[0][0])[e] = 0.0;
+        if (tid < 2) sZ[tid] = 0.0;
+        __syncthreads();
+        if (L0) {
+            const int row0 = chunk * 8 * B;
+            for (int t = tid; t < kreal * B; t += NT_) {
+                const int row = row0 + t;
+                if (row < n) {
+                    const double4 bb = rhs[row];
+                    double *Rb = &sR[1][0] + t * NR;
+                    Rb[0] = bb.x;
+                    Rb[1] = bb.y;
+                    Rb[2] = bb.z;
+                }
+            }
+        } else {
+            // R_j = sepR[j] + extR[j + 1] of the level below; the raw blocks of a mixed level 1 take theirs from rhs
+            constexpr int NIR = (8 * XB + NT_ - 1) / NT_;
+            double vr[NIR], vy[NIR];
+#pragma unroll
+            for (int u = 0; u < NIR; u++) {
+                const int e = tid + NT_ * u, i = e / XB, el = e - i * XB, gb = chunk * 8 + i;
+                const bool ok = e < 8 * XB && i < kreal && gb < nred;
+                vr[u] = ok ? bcr_ld<COH>(inR + (size_t)gb * XB + el) : 0.0;
+                vy[u] = ok && gb + 1 < nred ? bcr_ld<COH>(inXR + (size_t)(gb + 1) * XB + el) : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < NIR; u++) {
+                const int e = tid + NT_ * u, i = e / XB, gb = chunk * 8 + i;
+                if (e < 8 * XB && i < kreal && gb < nred) (&sR[1][0])[e] = vr[u] + vy[u];
+            }
+            if (chunk * 8 + 8 > nred && nred < nb)
+                for (int t = tid; t < 8 * B; t += NT_) {
+                    const int i = t / B, gb = chunk * 8 + i;
+                    if (gb >= nred && gb < nb) {
+                        const int row = (8 * nred + (gb - nred)) * B + (t - i * B);
+                        if (row < n) {
+                            const double4 bb = rhs[row];
+                            double *Rb = &sR[1][0] + t * NR;
+                            Rb[0] = bb.x;
+                            Rb[1] = bb.y;
+                            Rb[2] = bb.z;
+                        }
+                    }
+                }
+        }
+        __syncthreads();
+        BcrElim<B, NR, 1> E;
+        v4d out[Dm::MT][1];
+#define IRH_BCR_ROUND_RHS(RND)                                                                                      \
+    {                                                                                                               \
+        constexpr int NE = 4 >> RND;                                                                                \
+        int i = -1, a = -1, c = 7;                                                                                  \
+        if (wave < NE) {                                                                                            \
+            if (RND == 0) {                                                                                         \
+                i = 2 * wave;                                                                                       \
+                a = i - 1;                                                                                          \
+                c = i + 1;                                                                                          \
+            } else if (RND == 1) {                                                                                  \
+                i = 1 + 4 * wave;                                                                                   \
+                a = wave == 0 ? -1 : 3;                                                                             \
+                c = wave == 0 ? 3 : 7;                                                                              \
+            } else {                                                                                                \
+                i = 3;                                                                                              \
+            }                                                                                                       \
+        }                                                                                                           \
+        const bool active = i >= 0 && bcr_ridx(placed, kreal, i) >= 0;                                              \
+        const bool hasP = a >= 0 || hasExt;                                                                         \
+        const size_t el = (size_t)chunk * 7 + (i >= 0 ? i : 0);                                                     \
+        if (active)                                                                                                 \
+            E.template phase1<Dm::NT>(Dm::NT - 1, Dinvg + el * BB, stP + el * BB, hasP, stQ + el * BB, sR[i + 1], sZ, \
+                                      sR[c + 1], W + el * B * Dm::NC, sZ, lane);                                    \
+        __syncthreads();                                                                                            \
+        if (active && hasP) {                                                                                       \
+            E.template phase2_mul<Dm::NT>(Dm::NT - 1, stP + el * BB, out, lane);                                    \
+            E.template phase2_put<Dm::NT>(Dm::NT - 1, out, sZ, sZ, false, sR[a + 1], lane);                         \
+        }                                                                                                           \
+        __syncthreads();                                                                                            \
+    }
+        IRH_BCR_ROUND_RHS(0)
+        IRH_BCR_ROUND_RHS(1)
+        IRH_BCR_ROUND_RHS(2)
+#undef IRH_BCR_ROUND_RHS
+        for (int e = tid; e < XB; e += NT_) {
+            bcr_st<COH>(sepR + (size_t)chunk * XB + e, sR[8][e]);
+            if (hasExt) bcr_st<COH>(extR + (size_t)chunk * XB + e, sR[0][e]);
+        }
+        return;
+    }
 
     // ---- load ----
     // A chunk of an upper level whose blocks all come from the level below and sit at their own positions (every chunk
@@ -878,6 +1007,12 @@ __device__ __forceinline__ void bcr_reduce_body(
         /* closures: the inverse of every eliminated block is kept (bcr_closures) */                                \
         if (Dinvg && active && part == 0)                                                                           \
             for (int o = lane; o < BB; o += 64) Dinvg[((size_t)chunk * 7 + i) * BB + o] = sD[i][o];                 \
+        if constexpr (UF == 1)                                                                                      \
+            if (active && part == 0)                                                                                \
+                for (int o = lane; o < BB; o += 64) {                                                               \
+                    stP[((size_t)chunk * 7 + i) * BB + o] = sG[a + 1][o];                                           \
+                    stQ[((size_t)chunk * 7 + i) * BB + o] = sG[i + 1][o];                                           \
+                }                                                                                                   \
         bcr_stamp(stamps, 3 + 4 * RND);                                                                             \
         if (active && !(dbg & 2))                                                                                   \
             E.template phase1<WPE>(part, sD[i], sG[a + 1], hasP, sG[i + 1], sR[i + 1], sD[c], sR[c + 1],            \
@@ -949,6 +1084,7 @@ struct BcrAsmArgs {
     const uint8_t *bflag;
     const double *wsrc, *er;
     double *excess, *idg, *bval;
+    double *stP, *stQ;  // the unit-weight factor's P and Q of level 0 (UF != 0)
 };
 // (ASM: the kernel itself writes val / diag / rhs -- they are no read-only arguments of its)
 template <bool ASM>
@@ -962,7 +1098,7 @@ struct BcrL0Ptr<true> {
     typedef double4 *d4;
 };
 
-template <int B, int NR, bool L0, bool TOP, int NW, bool ASM = false>
+template <int B, int NR, bool L0, bool TOP, int NW, bool ASM = false, int UF = 0>
 __global__ __launch_bounds__(NW * 64, (NW == 4 && B <= 24 && NR == 3 ? 2 : 1)) void k_bcr_reduce(
 
     int nb, int nred, int n, const int *__restrict__ sl_off, const int *__restrict__ col, typename BcrL0Ptr<ASM>::d val,
@@ -1007,9 +1143,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && B <= 24 && NR == 3 ? 2 : 1)) v
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
-    bcr_reduce_body<B, NR, L0, TOP, NW, false>(blockIdx.x, sDG, sR, sZ, nb, nred, n, sl_off, col, val, diag, rhs, inD, inR, inXD, inXR,
-                                               inXG, W, sepD, sepR, extD, extR, extG, xtop, dbg, nfar, far_i, far_j, ext0, bptr,
-                                               bghost, bval, ghost_extcol, place, stamps, Dinvg, topDinv, deadctr, reg);
+    static_assert(UF == 0 || ASM, "the unit-weight factor rides on the assembling launch");
+    bcr_reduce_body<B, NR, L0, TOP, NW, false, UF>(blockIdx.x, sDG, sR, sZ, nb, nred, n, sl_off, col, val, diag, rhs, inD, inR, inXD, inXR,
+                                                   inXG, W, sepD, sepR, extD, extR, extG, xtop, dbg, nfar, far_i, far_j, ext0, bptr,
+                                                   bghost, bval, ghost_extcol, place, stamps, Dinvg, topDinv, deadctr, reg, A.stP,
+                                                   A.stQ);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1056,11 +1194,14 @@ static size_t bcr_top_lds(int B, int n) {
     return ((size_t)(2 * n - 1) * B * B + (size_t)2 * n * B * 3 + 2) * sizeof(double) + sizeof(BcrTopSched);
 }
 
-template <int B, int NW, bool COH>
+// UF (BcrUnit::top): 1 = the operands of every scheduled elimination, what it leaves for the way back and the inverse of the
+// block that is left are also written to tst; 2 = the right-hand-side-only pass: they are read from there (see bcr_reduce_body)
+template <int B, int NW, bool COH, int UF = 0>
 __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__restrict__ Tg, const double *__restrict__ inD,
                                              const double *__restrict__ inR, const double *__restrict__ inXD,
                                              const double *__restrict__ inXR, const double *__restrict__ inXG,
-                                             double *__restrict__ xout, int dbg, long long *__restrict__ stamps) {
+                                             double *__restrict__ xout, int dbg, long long *__restrict__ stamps,
+                                             double *__restrict__ tst = nullptr) {
     constexpr int NR = 3;
     typedef BcrDim<B, NR> Dm;
     constexpr int BB = B * B, XB = B * NR, NT_ = NW * 64;
@@ -1082,7 +1223,7 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
     {
         constexpr int U = 6;
         const int nD = n * BB, nG = (n - 1) * BB, nR = n * XB;
-        for (int e0 = 0; e0 < nD; e0 += U * NT_) {
+        for (int e0 = 0; e0 < nD && UF != 2; e0 += U * NT_) {
             double vd[U], vx[U], vg[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
@@ -1110,6 +1251,24 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
     // ---- the rounds ----
     for (int r = 0; r < T.nr; r++) {
         const int ne = T.ne[r];
+        if constexpr (UF == 2) {
+            const bool active = wave < ne;
+            const int i = active ? T.i[r][wave] : 0, a = active ? T.a[r][wave] : -1, c = active ? T.c[r][wave] : -1;
+            const bool hasP = a >= 0, hasQ = c >= 0;
+            const double *op = tst + (size_t)5 * (4 * r + (active ? wave : 0)) * BB;  // D_i^-1, P, Q
+            BcrElim<B, NR, 1> E;
+            v4d out[Dm::MT][1];
+            if (active)
+                E.template phase1<Dm::NT>(Dm::NT - 1, op, op + BB, hasP, op + 2 * BB, sR[i], sZ, hasQ ? sR[c] : sR[i],
+                                          (double *)nullptr, sZ, lane, hasQ);
+            __syncthreads();
+            if (active && hasP) E.template phase2_mul<Dm::NT>(Dm::NT - 1, op + BB, out, lane);
+            if (active) E.template keep_w<Dm::NT>(Dm::NT - 1, sZ, sZ, hasQ, sR[i], lane);
+            __syncthreads();
+            if (active && hasP) E.template phase2_put<Dm::NT>(Dm::NT - 1, out, sZ, sZ, false, sR[a], lane);
+            __syncthreads();
+            continue;
+        }
         if (wave < ne && !(dbg & 1)) bcr_invert<B>(sD[T.i[r][wave]], lane);
         __syncthreads();
         bcr_stamp(stamps, 2 + 2 * r);
@@ -1122,6 +1281,14 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
             const bool hasP = a >= 0, hasQ = c >= 0;
             BcrElim<B, NR, 2> E;
             v4d out[Dm::MT][2];
+            double *op = UF == 1 ? tst + (size_t)5 * (4 * r + (active ? e : 0)) * BB : nullptr;
+            if constexpr (UF == 1)
+                if (active && part == 0)
+                    for (int o = lane; o < BB; o += 64) {
+                        op[o] = sD[i][o];
+                        op[BB + o] = hasP ? sG[a][o] : 0.0;
+                        op[2 * BB + o] = hasQ ? sG[i][o] : 0.0;
+                    }
             if (active && !(dbg & 2))
                 E.template phase1<WPE>(part, sD[i], hasP ? sG[a] : sZ, hasP, hasQ ? sG[i] : sZ, sR[i], hasQ ? sD[c] : sD[i],
                                        hasQ ? sR[c] : sR[i], (double *)nullptr, sZ, lane, hasQ);
@@ -1131,6 +1298,13 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
             __syncthreads();
             if (active && hasP && !(dbg & 4)) E.template phase2_put<WPE>(part, out, sG[a], sD[a], false, sR[a], lane);
             __syncthreads();
+            // (what keep_w left: nobody writes the places of an eliminated block any more)
+            if constexpr (UF == 1)
+                if (active && part == 0)
+                    for (int o = lane; o < BB; o += 64) {
+                        op[3 * BB + o] = sD[i][o];
+                        op[4 * BB + o] = hasQ ? sG[i][o] : 0.0;
+                    }
         };
         if (ne > 2) products(std::integral_constant<int, 2>());
         else products(std::integral_constant<int, 4>());
@@ -1139,15 +1313,19 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
     // ---- the block that is left ----
     const int last = T.last;
     if (wave == 0) {
-        bcr_invert<B>(sD[last], lane);
+        if constexpr (UF != 2) bcr_invert<B>(sD[last], lane);
+        const double *Dl = UF == 2 ? tst + (size_t)kTopUnitLast * BB : sD[last];
         for (int o = lane; o < XB; o += 64) {
             const int k = o / NR, q = o - NR * k;
             double acc = 0.0;
-            for (int cidx = 0; cidx < B; cidx++) acc += sD[last][k * B + cidx] * sR[last][cidx * NR + q];
+            for (int cidx = 0; cidx < B; cidx++) acc += Dl[k * B + cidx] * sR[last][cidx * NR + q];
             sX[last][o] = acc;
         }
     }
     __syncthreads();
+    // (behind the barrier, like every other record: nothing writes the block that is left any more)
+    if constexpr (UF == 1)
+        for (int o = tid; o < BB; o += NT_) tst[(size_t)kTopUnitLast * BB + o] = sD[last][o];
     bcr_stamp(stamps, 14);
     // ---- the way back: x_i = W_R - W_P x_a - W_Q x_c, rounds in reverse; a unit of work = four rows of a block ----
     {
@@ -1159,6 +1337,8 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
                 const int e = u / UPB, it = u - e * UPB;
                 const int i = T.i[r][e], a = T.a[r][e], c = T.c[r][e];
                 const double *xa = sX[a >= 0 ? a : 0], *xc = sX[c >= 0 ? c : 0];
+                const double *wP = UF == 2 ? tst + ((size_t)5 * (4 * r + e) + 3) * BB : sD[i];
+                const double *wQ = UF == 2 ? tst + ((size_t)5 * (4 * r + e) + 4) * BB : sG[i];
                 const int k = 4 * it + lk;
                 double s0 = 0.0, s1 = 0.0, s2 = 0.0;
 #pragma unroll
@@ -1166,14 +1346,14 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
                     const int cidx = lp + 16 * t;
                     if (cidx < B) {
                         if (a >= 0) {
-                            const double wv = sD[i][k * B + cidx];
+                            const double wv = wP[k * B + cidx];
                             s0 += wv * xa[cidx * 3 + 0];
                             s1 += wv * xa[cidx * 3 + 1];
                             s2 += wv * xa[cidx * 3 + 2];
                         }
                     } else if (cidx < 2 * B) {
                         if (c >= 0) {
-                            const double wv = sG[i][k * B + cidx - B];
+                            const double wv = wQ[k * B + cidx - B];
                             s0 += wv * xc[(cidx - B) * 3 + 0];
                             s1 += wv * xc[(cidx - B) * 3 + 1];
                             s2 += wv * xc[(cidx - B) * 3 + 2];
@@ -1227,29 +1407,31 @@ __global__ __launch_bounds__(512, 1) void k_bcr_top(const BcrTopSched *__restric
 // every such read a split one and a sweep 3.5 x slower)
 extern __shared__ __attribute__((aligned(16))) double up_smem[];
 typedef IRH_GPTR(const BcrUpArgs) gp_args;
-template <int B, bool TOP>
+template <int B, bool TOP, int UF = 0>
 __device__ __noinline__ void bcr_up_chunk(gp_args A, int i, int dbg, long long *stl) {
     constexpr int NR = 3;
     IRH_GPTR(const BcrUpLevel) L = &A->lev[i];
     double(*sDG)[B * B] = reinterpret_cast<double(*)[B * B]>(up_smem);
     double(*sR)[B * NR] = reinterpret_cast<double(*)[B * NR]>(up_smem + 16 * B * B);
     double *sZ = up_smem + 16 * B * B + 9 * B * NR;
-    bcr_reduce_body<B, NR, false, TOP, 8, true>(
+    bcr_reduce_body<B, NR, false, TOP, 8, true, UF>(
         blockIdx.x, sDG, sR, sZ, L->nb, L->nred, A->n, (const int *)A->sl_off, (const int *)A->col, (const double *)A->val,
         (const double *)A->diag, (const double4 *)A->rhs, (const double *)L->inD, (const double *)L->inR, (const double *)L->inXD,
         (const double *)L->inXR, (const double *)L->inXG, (double *)L->W, (double *)L->sepD, (double *)L->sepR, (double *)L->extD,
         (double *)L->extR, (double *)L->extG, (double *)A->xtop, dbg, 0, (const int *)nullptr, (const int *)nullptr, 0, (const int *)nullptr, (const int *)nullptr,
-        (const double *)nullptr, (const int *)nullptr, 0, stl ? stl - (size_t)blockIdx.x * 16 : nullptr, (double *)nullptr,
-        (double *)nullptr, (int *)nullptr, 0);   // (bcr_stamp adds 16 x the workgroup's number)
+        (const double *)nullptr, (const int *)nullptr, 0, stl ? stl - (size_t)blockIdx.x * 16 : nullptr,
+        UF ? (double *)L->stD : (double *)nullptr, (double *)nullptr, (int *)nullptr, 0, UF ? (double *)L->stP : (double *)nullptr,
+        UF ? (double *)L->stQ : (double *)nullptr);   // (bcr_stamp adds 16 x the workgroup's number)
 }
-template <int B>
+template <int B, int UF = 0>
 __device__ __noinline__ void bcr_up_top(gp_args A, int i, int dbg, long long *stl) {
     IRH_GPTR(const BcrUpLevel) L = &A->lev[i];
-    bcr_top_body<B, 8, true>(up_smem, (const BcrTopSched *)&A->top, (const double *)L->inD, (const double *)L->inR,
-                             (const double *)L->inXD, (const double *)L->inXR, (const double *)L->inXG, (double *)A->xtop_all, dbg,
-                             stl ? stl - (size_t)blockIdx.x * 16 : nullptr);
+    bcr_top_body<B, 8, true, UF>(up_smem, (const BcrTopSched *)&A->top, (const double *)L->inD, (const double *)L->inR,
+                                 (const double *)L->inXD, (const double *)L->inXR, (const double *)L->inXG, (double *)A->xtop_all, dbg,
+                                 stl ? stl - (size_t)blockIdx.x * 16 : nullptr, UF ? (double *)A->tst : (double *)nullptr);
 }
-template <int B>
+// UF != 0 (the unit-weight factor: the launch that fills it, the right-hand-side-only launch): a sixteen-block top only
+template <int B, int UF = 0>
 __global__ __launch_bounds__(512, 1) void k_bcr_reduce_up(const BcrUpArgs *__restrict__ Ap, unsigned gen, int dbg,
                                                           long long *__restrict__ stamps) {
     constexpr int NR = 3;
@@ -1291,16 +1473,18 @@ __global__ __launch_bounds__(512, 1) void k_bcr_reduce_up(const BcrUpArgs *__res
             // bad: NaN into every entry -- it then reaches every solution row on the ways back, no view takes a step
             // (step_apply leaves a rotation alone when its step is not finite) and the score is NaN
             if (A.top16) {
-                if (!bad) bcr_up_top<B>(Ag, i, dbg, stl);
+                if (!bad) bcr_up_top<B, UF>(Ag, i, dbg, stl);
                 else
                     for (int e = threadIdx.x; e < A.top.n * B * NR; e += 512) A.xtop_all[e] = __builtin_nan("");
             } else {
-                if (!bad) bcr_up_chunk<B, true>(Ag, i, dbg, stl);
-                else
+                if constexpr (UF == 0) {
+                    if (!bad) bcr_up_chunk<B, true>(Ag, i, dbg, stl);
+                }
+                if (bad)
                     for (int e = threadIdx.x; e < B * NR; e += 512) A.xtop[e] = __builtin_nan("");
             }
         } else {
-            if (fine) bcr_up_chunk<B, false>(Ag, i, dbg, stl);
+            if (fine) bcr_up_chunk<B, false, UF>(Ag, i, dbg, stl);
             if (stl && threadIdx.x == 0) stl[18] = (long long)__builtin_readcyclecounter();
             // every thread's separator stores have been acknowledged before the workgroup is counted
             __builtin_amdgcn_s_waitcnt(0);
@@ -1325,6 +1509,7 @@ static size_t bcr_up_lds(int ntop) {
     return ntop > 0 ? std::max(chunk, bcr_top_lds(B, ntop)) : chunk;
 }
 namespace {
+std::atomic<unsigned> g_unit_epoch{0};  // irotavg_trim_memory's count: a store allocated under an older one is released
 std::atomic<int> g_up_used[16];
 template <int B>
 int bcr_up_capacity(int dev) {
@@ -2672,8 +2857,46 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
         if (fused_up) fused_up = bcr_up_reserve<B>(g, S.lev[1].nch);
     }
     if (only < 0 && phase != 2) S.up_used = false;
+    // The unit-weight factor (BcrUnit). run_irls announces the first solve of a call (Graph::bcr_unit_req = 1); on the plain
+    // route -- level 0 assembling its own slices, the upper levels in one launch, a sixteen-block top, blocks of 8 / 16 / 24, no
+    // debug word, not guarded -- the handle's first such solve is the full reduction with its outputs pointed at the store
+    // (uf = 1), every later one the right-hand-side-only pass (uf = 2). Requests 2 and 3 are time_kernel's: the
+    // right-hand-side-only solve of a handle whose store is valid, and its upper launch alone.
+    int uf = 0;
+    BcrUnit &U = S.unit;
+    if (only < 0 && phase != 2) U.last = 0;
+    if constexpr (NR == 3 && (B == 8 || B == 16 || B == 24)) {
+        const int req = g.bcr_unit_req;
+        if (req && fused_up && S.top16 && dbg == 0 && !g.bcr_guard && !g.bcr_out && !g.sw.bcr_no_unit_factor &&
+            (g.bcr_asm_fused || req == 3)) {
+            if (!U.lev.empty() && U.epoch != g_unit_epoch.load(std::memory_order_acquire)) U.release();
+            uf = U.valid ? 2 : (req == 1 ? 1 : 0);
+            if (uf == 1 && U.lev.empty()) {
+                // (lazily: a handle that never makes such a solve -- a solver clone, l1ra alone -- keeps nothing)
+                constexpr int NC = 2 * B + 3;
+                U.epoch = g_unit_epoch.load(std::memory_order_acquire);
+                U.lev.resize((size_t)nl - 1);
+                size_t words = 0;
+                for (int l = 0; l + 1 < nl; l++) {
+                    const size_t ne = (size_t)S.lev[l].nch * 7;
+                    U.lev[(size_t)l].Wu.alloc(ne * B * NC);
+                    U.lev[(size_t)l].Di.alloc(ne * B * B);
+                    U.lev[(size_t)l].P.alloc(ne * B * B);
+                    U.lev[(size_t)l].Q.alloc(ne * B * B);
+                    words += ne * B * (NC + 3 * B);
+                }
+                U.top.alloc((size_t)(kTopUnitLast + 1) * B * B);
+                words += (size_t)(kTopUnitLast + 1) * B * B;
+                U.bytes = (int64_t)(words * sizeof(double));
+                // (a partial chunk skips its padding positions: their slots are never written, and never read)
+            }
+        }
+        U.last = uf;
+    }
+    const bool uf_up_only = uf == 2 && g.bcr_unit_req == 3;
     for (int l = 0; l < nl && phase != 2; l++) {
         if (only >= 0 && only != l) continue;
+        if (l == 0 && uf_up_only) continue;
         if constexpr (NR == 3 && B <= 24) {
             if (S.top16 && l == nl - 1 && !fused_up) {
                 // the single-workgroup top in a launch of its own
@@ -2727,14 +2950,41 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
                 if (g.sw.bcr_fake_up_fail && g.stats.direct_up_fallbacks == 0)
                     IRH_CHECK(hipMemsetAsync(S.up_cnt.p + kUpLevels, 1, sizeof(int), st));
                 const size_t lds = bcr_up_lds<B>(S.top16 ? S.lev[nl - 1].nb : 0);
-                static std::atomic<size_t> lds_set[16];
-                if (lds_set[g.device & 15].load() < lds) {
-                    IRH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bcr_reduce_up<B>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    lds_set[g.device & 15].store(lds);
+                static std::atomic<size_t> lds_set[3][16];
+                auto launch_up = [&](auto uf_tag, const BcrUpArgs *args) {
+                    constexpr int UF = decltype(uf_tag)::value;
+                    if (lds_set[UF][g.device & 15].load() < lds) {
+                        IRH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bcr_reduce_up<B, UF>),
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                        lds_set[UF][g.device & 15].store(lds);
+                    }
+                    hipLaunchKernelGGL((k_bcr_reduce_up<B, UF>), dim3(S.lev[1].nch), dim3(512), lds, st, args, ++S.up_gen, dbg,
+                                       (dbg & 128) ? S.stamps.p : (long long *)nullptr);
+                };
+                if constexpr (B == 8 || B == 16 || B == 24) {
+                    if (uf && !U.up_args.p) {
+                        // the same arguments with W = the store's and the operand arrays
+                        BcrUpArgs A;
+                        IRH_CHECK(hipMemcpyAsync(&A, S.up_args.p, sizeof(A), hipMemcpyDeviceToHost, st));
+                        IRH_CHECK(hipStreamSynchronize(st));
+                        for (int i = 0; i + 1 < A.nl; i++) {
+                            BcrUnitLevel &Ui = U.lev[(size_t)i + 1];
+                            A.lev[i].W = (gp_d)Ui.Wu.p;
+                            A.lev[i].stD = (gp_d)Ui.Di.p;
+                            A.lev[i].stP = (gp_d)Ui.P.p;
+                            A.lev[i].stQ = (gp_d)Ui.Q.p;
+                        }
+                        A.tst = (gp_d)U.top.p;
+                        U.up_args.alloc(1);
+                        IRH_CHECK(hipMemcpyAsync(U.up_args.p, &A, sizeof(A), hipMemcpyHostToDevice, st));
+                        IRH_CHECK(hipStreamSynchronize(st));  // (A is on this stack)
+                    }
+                    if (uf == 2) launch_up(std::integral_constant<int, 2>(), U.up_args.p);
+                    else if (uf == 1) launch_up(std::integral_constant<int, 1>(), U.up_args.p);
+                    else launch_up(std::integral_constant<int, 0>(), S.up_args.p);
+                } else {
+                    launch_up(std::integral_constant<int, 0>(), S.up_args.p);
                 }
-                hipLaunchKernelGGL((k_bcr_reduce_up<B>), dim3(S.lev[1].nch), dim3(512), lds, st, S.up_args.p, ++S.up_gen, dbg,
-                                   (dbg & 128) ? S.stamps.p : (long long *)nullptr);
                 S.up_used = true;
                 continue;
             }
@@ -2744,10 +2994,16 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
         const bool top = l == nl - 1 && !open_top;
 #define IRH_BCR_ARGS                                                                                             \
     L.nb, L.nred, L0.n, L0.sl_off.p, L0.col.p, L0.val.p, L0.diag.p, L0.b.p, F ? F->sepD.p : nullptr,             \
-        F ? F->sepR.p : nullptr, F ? F->extD.p : nullptr, F ? F->extR.p : nullptr, F ? F->extG.p : nullptr, L.W.p, \
+        F ? F->sepR.p : nullptr, F ? F->extD.p : nullptr, F ? F->extR.p : nullptr, F ? F->extG.p : nullptr, Wl, \
         L.sepD.p, L.sepR.p, L.extD.p, L.extR.p, L.extG.p, S.xtop.p, dbg, nfar, fi, fj, S.ext0, g.bptr.p, g.bghost.p,  \
-        g.bval.p, S.ghost_extcol.p, (int)g.bcr_shard, stamps, S.nfar > 0 ? S.Dinv[(size_t)l].p : (double *)nullptr,         \
+        g.bval.p, S.ghost_extcol.p, (int)g.bcr_shard, stamps, Dl,                                                          \
         S.nfar > 0 ? S.topDinv.p : (double *)nullptr, S.nfar > 0 ? S.dead.p : (int *)nullptr, (int)g.bcr_guard, asmA
+        // (the unit-weight factor: level 0's W and inverses are the store's)
+        double *Wl = L.W.p, *Dl = S.nfar > 0 ? S.Dinv[(size_t)l].p : (double *)nullptr;
+        if (uf && l == 0) {
+            Wl = U.lev[0].Wu.p;
+            Dl = U.lev[0].Di.p;
+        }
         // eight waves per chunk when every chunk has a CU to itself (see k_bcr_reduce)
         const bool wide = L.nch <= 256;
         // level 0 assembles its own slices first (ls_solve asked): the chunks' workgroups, then one per slice under no chunk
@@ -2759,13 +3015,35 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
                 asmA = BcrAsmArgs{L.nch,   L0.nsl,    (long long)g.m, (long long)g.mpad, g.slot_eid.p, g.tile_e0.p, g.beid.p,
                                   g.bflag.p, g.bcr_wsrc, g.er.p,         L0.excess.p,       L0.idg.p,     g.bval.p};
                 const int extra = std::max(0, L0.nsl - L.nch * (8 * B / 64));
+                bool launched = false;
+                if constexpr (B == 8 || B == 16 || B == 24) {
+                    if (uf) {
+                        asmA.stP = U.lev[0].P.p;
+                        asmA.stQ = U.lev[0].Q.p;
+#define IRH_BCR_LAUNCH_UNIT(UF_)                                                                                          \
+    if (wide)                                                                                                             \
+        hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, false, 8, true, UF_>), dim3(L.nch + extra), dim3(512), 0, st,       \
+                           IRH_BCR_ARGS);                                                                                 \
+    else                                                                                                                  \
+        hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, false, 4, true, UF_>), dim3(L.nch + extra), dim3(256), 0, st,       \
+                           IRH_BCR_ARGS);
+                        if (uf == 2) {
+                            IRH_BCR_LAUNCH_UNIT(2)
+                        } else {
+                            IRH_BCR_LAUNCH_UNIT(1)
+                        }
+#undef IRH_BCR_LAUNCH_UNIT
+                        launched = true;
+                    }
+                }
 #define IRH_BCR_LAUNCH_ASM(TOP_)                                                                                          \
     if (B <= 24 && wide)                                                                                                  \
         hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, TOP_, (B <= 24 ? 8 : 4), true>), dim3(L.nch + extra),               \
                            dim3(B <= 24 ? 512 : 256), 0, st, IRH_BCR_ARGS);                                               \
     else                                                                                                                  \
         hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, TOP_, 4, true>), dim3(L.nch + extra), dim3(256), 0, st, IRH_BCR_ARGS);
-                if (top) {
+                if (launched) {
+                } else if (top) {
                     IRH_BCR_LAUNCH_ASM(true)
                 } else {
                     IRH_BCR_LAUNCH_ASM(false)
@@ -2807,7 +3085,7 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
     const bool apply = NR == 3 && g.bcr_apply && only < 0 && phase == 0 && (fused_back || (S.top16 && nl == 2)) && !g.bcr_out &&
                        g.ng == 0;
     g.bcr_applied = apply;
-    for (int l = ltop; l >= 0 && phase != 1; l--) {
+    for (int l = ltop; l >= 0 && phase != 1 && !uf_up_only; l--) {
         if (only >= 0 && only != 100 + l) continue;
         BcrLevel &L = S.lev[l];
         if constexpr (NR == 3) {
@@ -2815,7 +3093,7 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
                 if (l > 1) continue;
                 BcrBackPlan P;
                 for (int k = 0; k < nl; k++) {
-                    P.W[k] = S.lev[k].W.p;
+                    P.W[k] = uf && k + 1 < nl ? U.lev[(size_t)k].Wu.p : S.lev[k].W.p;
                     P.nb[k] = S.lev[k].nb;
                 }
                 P.top = ltop;
@@ -2828,7 +3106,8 @@ static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int pha
         }
         const double *xc = l == nl - 1 ? (open_top ? xc_top : S.xtop.p) : S.lev[l + 1].x.p;
         if (l == 0)
-            hipLaunchKernelGGL((k_bcr_back<B, NR, true>), dim3(L.nch), dim3(256), 0, st, L.nb, L.nred, L0.n, L.W.p, xc,
+            hipLaunchKernelGGL((k_bcr_back<B, NR, true>), dim3(L.nch), dim3(256), 0, st, L.nb, L.nred, L0.n,
+                               uf ? U.lev[0].Wu.p : L.W.p, xc,
                                (double *)nullptr, Xout, (double *)nullptr, 0, 0, nfar, xext, (int)g.bcr_shard,
                                apply ? g.Q.p : (double4 *)nullptr, g.f, g.part_score.p, 0);
         else
@@ -3397,6 +3676,11 @@ int bcr_info(Graph &g, int64_t *out, int cap) {
     }
     put(g.bcr->nfar);
     put(g.bcr_asm_fused_last ? 1 : 0);  // the most recent assembly + solve (ls_solve) was ONE launch at level 0
+    // the unit-weight factor: 0 none / 1 stored, solves served from it, its bytes
+    const bool stored = bcr_unit_valid(g);
+    put(stored ? 1 : 0);
+    put(g.bcr->unit.solves);
+    put(stored ? g.bcr->unit.bytes : 0);
     return k;
 }
 
@@ -3584,6 +3868,27 @@ bool bcr_up_failed(Graph &g) {
     bcr_up_release(g);
     return true;
 }
+
+// the unit-weight factor (BcrUnit). bcr_unit_commit: run_irls has the score of the solve it announced -- a finite one makes a
+// filling solve's store valid and counts a solve served from it; a filling solve that failed gives its arrays back.
+void bcr_unit_commit(Graph &g, bool finite) {
+    if (!g.bcr) return;
+    BcrUnit &U = g.bcr->unit;
+    if (U.last == 1) {
+        if (finite) U.valid = true;
+        else U.release();
+    } else if (U.last == 2 && finite) {
+        U.solves += 1;
+    }
+    U.last = 0;
+}
+int bcr_unit_last(Graph &g) { return g.bcr ? g.bcr->unit.last : 0; }
+bool bcr_unit_valid(Graph &g) {
+    return g.bcr && g.bcr->unit.valid && g.bcr->unit.epoch == g_unit_epoch.load(std::memory_order_acquire);
+}
+// irotavg_trim_memory: every handle's store is invalid from now on; a handle gives its arrays back to the pool when it next
+// looks (on its own thread, between its own solves -- not under a solve another thread may be running on it)
+void bcr_unit_trim() noexcept { g_unit_epoch.fetch_add(1, std::memory_order_acq_rel); }
 
 int bcr_levels(Graph &g) {
     if (!g.bcr_B) return 0;

@@ -258,6 +258,7 @@ int irotavg_graph_create(irotavg_graph **out, int64_t m, int64_t n_total, int f,
 int64_t irotavg_trim_memory(void) {
     try {
         StreamPool::get().trim();
+        bcr_unit_trim();  // (the direct solver's unit-weight factors: invalid now, given back when their handles next look)
         return (int64_t)DevPool::get().trim();
     } catch (...) {
         return 0;

@@ -146,6 +146,9 @@ struct Graph {
     // bcr_run) instead of a launch of k_assemble0w in front of it. bcr_asm_fused: asked of the solve that follows;
     // bcr_asm_fused_last: what the most recent ls_solve did (irotavg_graph_direct_info)
     bool bcr_asm_fused = false, bcr_asm_fused_last = false;
+    // the solve that follows may use the handle's unit-weight factor (bcr.hip, BcrUnit): 1 = run_irls's first solve of a
+    // call (weights all one); time_kernel: 2 = the right-hand-side-only solve, 3 = its upper launch alone
+    int bcr_unit_req = 0;
     std::unique_ptr<BcrState, BcrDeleter> bcr;
     std::vector<int> bcr_far_i, bcr_far_j, bcr_far_e;  // long-range edges (rows, edge id): Woodbury correction
     const double *bcr_wsrc = nullptr;                  // per-edge weights of the last assembly and whether the
@@ -412,6 +415,10 @@ int bcr_stamps_up(Graph &g, double *out);                      // development ai
 // the last direct solve went through the single-launch upper reduction and a workgroup of it gave up waiting (its solution
 // is all NaN): clears the word, switches the handle to level-by-level launches and says so (one small synchronous read)
 bool bcr_up_failed(Graph &g);
+void bcr_unit_commit(Graph &g, bool finite);  // the score of the solve that bcr_unit_req = 1 announced is in
+int bcr_unit_last(Graph &g);                  // what the most recent solve did: 0 nothing, 1 filled the store, 2 was served from it
+bool bcr_unit_valid(Graph &g);
+void bcr_unit_trim() noexcept;                // irotavg_trim_memory: every handle's store is released and invalid
 // the device word behind it while such a solve is the last one (kernels behind the solve skip their work when it is set),
 // or nullptr
 const int *bcr_fail_word(Graph &g);

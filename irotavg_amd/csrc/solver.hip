@@ -2243,7 +2243,14 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
             g.bcr_apply = ap_slots > 0;
             g.bcr_applied = false;
             with_res = !(it + 1 >= max_iters || (it > 0 && score <= 50.0 * change_th));
+            // (the first system of a call is the unit-weight one, whatever the rotations: the direct solver may keep its factor)
+            g.bcr_unit_req = it == 0 && fuse_wr ? 1 : 0;
+            struct UnitReq {
+                Graph &g;
+                ~UnitReq() { g.bcr_unit_req = 0; }
+            } unit_req{g};
             rc = ls_solve(g);
+            g.bcr_unit_req = 0;
             g.bcr_apply = false;
             if (rc != IROTAVG_OK) break;
             if (bcr_closures(g) > 0) {
@@ -2338,6 +2345,7 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
                 launch_update_weights(g, cost, sigma);
                 score = apply_step(g);
             }
+            bcr_unit_commit(g, std::isfinite(score));
             if (!std::isfinite(score)) {
                 // the single-launch upper reduction gave up on a wait (another process held its workgroups back: the
                 // reservation only knows this process): its solution is NaN, no view took a step, the kernel behind it left
@@ -2492,6 +2500,7 @@ int time_kernel(Graph &g, int which, int reps, double *ms) {
     hipEvent_t e0, e1;
     IRH_CHECK(hipEventCreate(&e0));
     IRH_CHECK(hipEventCreate(&e1));
+    bool unit_served = true;  // (17 / 18: every repetition took the right-hand-side-only route)
     auto once = [&]() {
         switch (which) {
         case 1: launch_edge_residual(g); break;
@@ -2521,12 +2530,26 @@ int time_kernel(Graph &g, int which, int reps, double *ms) {
         default:
             // 20 + l: reduction of level l of the banded direct solver, 40 + l: its way back, 19: a whole solve
             if (which == 19) (void)bcr_solve(g);
+            else if (which == 17 || which == 18) {
+                // the right-hand-side-only solve over the kept unit-weight factor: all four launches / its upper launch alone
+                g.bcr_unit_req = which == 17 ? 2 : 3;
+                g.bcr_asm_fused = which == 17;
+                g.bcr_wsrc = g.dw.p;
+                g.bcr_wsquare = 1;
+                (void)bcr_solve(g);
+                g.bcr_unit_req = 0;
+                g.bcr_asm_fused = false;
+                unit_served = unit_served && bcr_unit_last(g) == 2;
+                bcr_unit_commit(g, false);
+            }
             else if (which >= 20 && which < 40) (void)bcr_solve(g, which - 20);
             else if (which >= 40 && which < 60) (void)bcr_solve(g, 100 + which - 40);
             break;
         }
     };
-    if (which >= 19 && which < 60) {
+    if (which == 17 || which == 18) {
+        if (!g.bcr_B || !bcr_unit_valid(g)) return IROTAVG_ERR_BAD_ARG;
+    } else if (which >= 19 && which < 60) {
         if (!g.bcr_B) return IROTAVG_ERR_BAD_ARG;
         const int nl = bcr_levels(g);
         if ((which >= 20 && which < 40 && which - 20 >= nl) || (which >= 40 && which - 40 >= nl)) return IROTAVG_ERR_BAD_ARG;
@@ -2562,6 +2585,7 @@ int time_kernel(Graph &g, int which, int reps, double *ms) {
     *ms = (double)t / std::max(reps, 1);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    if ((which == 17 || which == 18) && !unit_served) return IROTAVG_ERR_BAD_ARG;
     return IROTAVG_OK;
 }
 

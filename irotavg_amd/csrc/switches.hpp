@@ -25,7 +25,7 @@ struct Switches {
     int inexact = -1;              // -1: by size; 1 / 0: inexact solves on / off
     // direct solver
     bool bcr_no_mixed = false, bcr_no_top16 = false, bcr_fake_up_fail = false, bcr_fake_give_up = false;
-    bool bcr_no_closures = false, bcr_s_tiles = false, bcr_no_fused_asm = false;
+    bool bcr_no_closures = false, bcr_s_tiles = false, bcr_no_fused_asm = false, bcr_no_unit_factor = false;
     int bcr_up_cap = 1024;         // 1/1024ths of the device the single-launch upper reductions may reserve
     int bcr_dbg = 0, bcr_stamp_chunk = 0;
     // sharded handles
@@ -64,6 +64,7 @@ inline Switches read_switches() {
     s.bcr_no_closures = set("IROTAVG_BCR_NO_CLOSURES");
     s.bcr_s_tiles = set("IROTAVG_BCR_S_TILES");
     s.bcr_no_fused_asm = set("IROTAVG_BCR_NO_FUSED_ASM");
+    s.bcr_no_unit_factor = set("IROTAVG_BCR_NO_UNIT_FACTOR");
     s.bcr_up_cap = num("IROTAVG_BCR_UP_CAP", 1024);
     s.bcr_dbg = num("IROTAVG_BCR_DBG", 0);
     s.bcr_stamp_chunk = num("IROTAVG_BCR_STAMP_CHUNK", 0);
@@ -84,7 +85,7 @@ inline bool operator==(const Switches &a, const Switches &b) {
             s.has_band_direct, s.band_direct, s.host_build, s.upload_threads, s.asm_classic, s.no_small_tuning,
             s.no_dense_refine, s.no_band_inverse, s.pcg_trace, s.cg2_giveup, s.no_settle, s.no_fused_cl, s.inexact,
             s.bcr_no_mixed, s.bcr_no_top16, s.bcr_fake_up_fail, s.bcr_fake_give_up, s.bcr_no_closures, s.bcr_s_tiles,
-            s.bcr_no_fused_asm,             s.bcr_up_cap, s.bcr_dbg, s.bcr_stamp_chunk, s.dist_no_closures, s.dist_halo_p2p, s.no_resident, s.window_stamps,
+            s.bcr_no_fused_asm, s.bcr_no_unit_factor, s.bcr_up_cap, s.bcr_dbg, s.bcr_stamp_chunk, s.dist_no_closures, s.dist_halo_p2p, s.no_resident, s.window_stamps,
             s.resident_min_edges, s.build_timing, s.rotavg_timing);
     };
     return t(a) == t(b);
