@@ -282,6 +282,14 @@ int irotavg_graph_direct_info(irotavg_graph *g, int64_t *info, int cap);
  * has been solved yet. */
 int irotavg_graph_direct_residual(irotavg_graph *g, double *relres);
 
+/* Diagnostic: the right-hand-side part of ONE block elimination of the direct solver, run by one wave through the device
+ * functions every reduction kernel uses for it (the small matrix-core products of irotavg_amd/csrc/bcr.hip, BcrRs), on
+ * host arrays: Dinv (symmetric), P, Q are B x B row-major, R, WR, Ra, Rc are B x 3 row-major, B = 8 / 16 / 24 / 32
+ * (any other: IROTAVG_ERR_BAD_ARG). On return WR = Dinv R; Rc = Rc - Q' WR unless hasQ = 0; Ra = Ra - P WR unless
+ * hasP = 0 -- a skipped update leaves its array as it was. */
+int irotavg_bcr_rhs_products(int B, const double *Dinv, const double *P, const double *Q, const double *R, int hasP,
+                             int hasQ, double *WR, double *Ra, double *Rc);
+
 /* Uncertainty of the IRLS solution (docs/rotation_variance.md). M = A' diag(d^2) A with A = irotavg_make_A's
  * incidence (m x nu, nu = n_total - f) and d = the handle's current weights (irotavg_graph_get_weights), Sigma = M^-1:
  *   var[v]      = Sigma_{v-f, v-f} for a free view v, 0 for a fixed one (n_total entries; NULL: not asked for);

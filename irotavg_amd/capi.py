@@ -37,7 +37,7 @@ SYMBOLS = [
     "irotavg_dist_irls", "irotavg_dist_get_stats", "irotavg_dist_info", "irotavg_dist_plan", "irotavg_dist_plan_host",
     "irotavg_dist_l1ra", "irotavg_dist_create_hosted",
     "irotavg_graph_direct_info",
-    "irotavg_graph_direct_residual",
+    "irotavg_graph_direct_residual", "irotavg_bcr_rhs_products",
     "irotavg_window_solve", "irotavg_window_solve_kernel", "irotavg_trim_memory", "irotavg_rmat2quat", "irotavg_quat2rmat", "irotavg_viewgraph_save_poses",
     "irotavg_oneshot_cache", "irotavg_oneshot_cache_clear", "irotavg_oneshot_cache_stats",
     "irotavg_dist_timing",
@@ -153,6 +153,7 @@ def lib():
     L.irotavg_graph_fingerprint.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.irotavg_graph_direct_info.argtypes = [vp, _i64p, C.c_int]
     L.irotavg_graph_direct_residual.argtypes = [vp, _dp]
+    L.irotavg_bcr_rhs_products.argtypes = [C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]
     L.irotavg_graph_rotation_variance.argtypes = [vp, _dp, C.c_int64, _ip, _dp, _dp]
     L.irotavg_rotation_variance.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
                                             _dp, C.c_int64, _ip, _dp, _dp]
@@ -539,6 +540,22 @@ def edge_diagnostics(I, QQ, Q, weights, f, edge_var=True, leverage=True, chi2=Tr
     return _edge_call(lambda *a: lib().irotavg_edge_diagnostics(len(I), n_total, int(f), _i(I), _d(QQ), QQ.shape[0],
                                                                 _d(Q), Q.shape[0], _d(w), *a),
                       len(I), edge_var, leverage, chi2, allow_rc, "irotavg_edge_diagnostics")
+
+
+def bcr_rhs_products(Dinv, P, Q, R, hasP=True, hasQ=True, Ra=None, Rc=None):
+    """irotavg_bcr_rhs_products (a diagnostic): the right-hand-side part of one block elimination of the direct solver by
+    one wave -- dict(WR = Dinv R, Ra = Ra - P WR, Rc = Rc - Q' WR); Ra / Rc start from zeros unless given, and come back
+    as they went in when hasP / hasQ is false. Dinv (symmetric), P, Q: B x B, R: B x 3, B = 8 / 16 / 24 / 32."""
+    Dinv, P, Q, R = (np.ascontiguousarray(a, dtype=np.float64) for a in (Dinv, P, Q, R))
+    B = Dinv.shape[0]
+    if Dinv.shape != (B, B) or P.shape != (B, B) or Q.shape != (B, B) or R.shape != (B, 3):
+        raise ValueError("shapes")
+    WR = np.full((B, 3), np.nan)
+    Ra = np.zeros((B, 3)) if Ra is None else np.array(Ra, dtype=np.float64, order="C").reshape(B, 3)
+    Rc = np.zeros((B, 3)) if Rc is None else np.array(Rc, dtype=np.float64, order="C").reshape(B, 3)
+    check(lib().irotavg_bcr_rhs_products(B, _d(Dinv), _d(P), _d(Q), _d(R), 1 if hasP else 0, 1 if hasQ else 0, _d(WR),
+                                         _d(Ra), _d(Rc)), "irotavg_bcr_rhs_products")
+    return dict(WR=WR, Ra=Ra, Rc=Rc)
 
 
 def oneshot_cache(enable):

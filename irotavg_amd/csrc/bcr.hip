@@ -19,7 +19,8 @@
 // (v_mfma_f64_16x16x4_f64: operands are distributed over the lanes, so no operand is broadcast through
 // LDS -- with vector FMAs every value of P, Q and D^-1 would have to reach all 64 lanes, and eight waves
 // per CU saturate the LDS port with that); the accumulator layout of one product IS the B-operand layout
-// of the next (row = 4 reg + lane / 16), so W never leaves the registers between the two. D_i^-1 is
+// of the next (row = 4 reg + lane / 16), so W never leaves the registers between the two (the right-hand sides, three
+// columns of a sixteen-column tile, run on v_mfma_f64_4x4x4_4b_f64 instead: BcrRs). D_i^-1 is
 // formed by a symmetric sweep (Gauss-Jordan without pivoting: SPD), a column per lane, the pivot row
 // broadcast through LDS (bcr_invert). A pivot not above kDeadTol x its original diagonal entry is dead
 // (an isolated view, a floating component): its unknown solves to 0, as everywhere else in this library.
@@ -364,15 +365,133 @@ __device__ __forceinline__ void bcr_mul_w(const double (&aop)[BcrDim<B>::MT][Bcr
         }
 }
 
+// The right-hand sides as SMALL products. With three right-hand sides and 2 B a multiple of 16 (B = 8 / 16 / 24 / 32) the
+// last 16-column tile of W holds W_R and thirteen columns of zeros: 3 MT KS products of 64 pipe clocks each for 3 useful
+// columns of 16. v_mfma_f64_4x4x4_4b_f64 runs four independent 4 x 4 x 4 products per instruction at an issue every ~18
+// clocks (tools/micro/mfma_f64.hip) and holds one double per lane for each of A, B and the accumulator; the layout is the
+// 16x16x4 one with the sixteen columns cut into four blocks: block = (lane / 4) % 4 for all three, A[i][k] sits in lane
+// 16 k + 4 block + i, B[k][j] in lane 16 k + 4 block + j, D[i][j] in lane 16 i + 4 block + j -- measured, it is documented
+// nowhere (tools/micro/mfma_f64_4x4x4_layout.hip prints it). A block of the instruction is a ROW GROUP of four rows: instruction t
+// of a product covers the row groups 4 t ... 4 t + 3 (B = 24: 4 + 2, B = 8: 2 -- the other blocks run on zeros), its A-operand
+// of k-step s is the 4 x 4 block (group, s) of D_i^-1, Q' or P, its B-operand the rows 4 s ... 4 s + 3 of the B x 3 matrix on
+// the right (column 3 reads as zero) in every block. MT = ceil(B / 16) instructions per k-step, KS k-steps: 12 instructions
+// per product at B = 24. The matrix on the right of the second and third product is W_R itself: its owner writes it over
+// R_i in LDS (nobody else reads R_i, and the single-workgroup top keeps W_R there anyway) and reads it back as an operand.
+template <int B>
+struct BcrRs {
+    static constexpr int MT = (B + 15) / 16, KS = B / 4, NG = B / 4;
+    int blk, ai, ak, bk, bj, di, dj;
+    __device__ __forceinline__ explicit BcrRs(int lane)
+        : blk((lane >> 2) & 3), ai(lane & 3), ak(lane >> 4), bk(lane >> 4), bj(lane & 3), di(lane >> 4), dj(lane & 3) {}
+    // A-operands from the row-major B x B matrix M (or its transpose)
+    template <bool TRANS>
+    __device__ __forceinline__ void load_a(const double *M, double (&aop)[MT][KS]) const {
+#pragma unroll
+        for (int t = 0; t < MT; t++) {
+            const int g = 4 * t + blk;
+            const int row = 4 * (g < NG ? g : NG - 1) + ai;
+#pragma unroll
+            for (int s = 0; s < KS; s++) {
+                const int k = 4 * s + ak;
+                const double v = TRANS ? M[k * B + row] : M[row * B + k];
+                aop[t][s] = g < NG ? v : 0.0;
+            }
+        }
+    }
+    // B-operands from the row-major B x 3 matrix X
+    __device__ __forceinline__ void load_b(const double *X, double (&bop)[KS]) const {
+        const int j = bj < 3 ? bj : 2;
+#pragma unroll
+        for (int s = 0; s < KS; s++) {
+            const double v = X[(4 * s + bk) * 3 + j];
+            bop[s] = bj < 3 ? v : 0.0;
+        }
+    }
+    // acc[t] = sum over the k-steps, in their order (k-steps outermost: the MT accumulators are independent chains)
+    __device__ __forceinline__ void mul(const double (&aop)[MT][KS], const double (&bop)[KS], double (&acc)[MT]) const {
+#pragma unroll
+        for (int t = 0; t < MT; t++) acc[t] = 0.0;
+#pragma unroll
+        for (int s = 0; s < KS; s++)
+#pragma unroll
+            for (int t = 0; t < MT; t++) acc[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(aop[t][s], bop[s], acc[t], 0, 0, 0);
+    }
+    // the lane's entry of instruction t: row (of B) and column (of 3), or row = -1
+    __device__ __forceinline__ int row(int t) const {
+        const int g = 4 * t + blk;
+        return g < NG && dj < 3 ? 4 * g + di : -1;
+    }
+};
+
+// W_R = D_i^-1 R_i over R_i (and to Wg: row stride 2 B + 3, columns 2 B ...), R_c -= Q' W_R
+template <int B>
+__device__ __forceinline__ void bcr_rs_phase1(const double *Di, const double *Q, double *Ri, double *Rc, double *Wg, int lane,
+                                              bool hasQ) {
+    typedef BcrRs<B> S_;
+    const S_ S(lane);
+    double aop[S_::MT][S_::KS], bop[S_::KS], acc[S_::MT];
+    S.template load_a<true>(Di, aop);
+    S.load_b(Ri, bop);
+    S.mul(aop, bop, acc);
+#pragma unroll
+    for (int t = 0; t < S_::MT; t++) {
+        const int row = S.row(t);
+        if (row >= 0) {
+            Ri[row * 3 + S.dj] = acc[t];
+            if (Wg) Wg[row * (2 * B + 3) + 2 * B + S.dj] = acc[t];
+        }
+    }
+    if (!hasQ) return;
+    S.template load_a<true>(Q, aop);
+    S.load_b(Ri, bop);
+    S.mul(aop, bop, acc);
+#pragma unroll
+    for (int t = 0; t < S_::MT; t++) {
+        const int row = S.row(t);
+        if (row >= 0) Rc[row * 3 + S.dj] -= acc[t];
+    }
+}
+// P W_R: the lane's entries of the (at most two) instructions
+template <int B>
+__device__ __forceinline__ v2d bcr_rs_pw(const double *P, const double *Wr, int lane) {
+    typedef BcrRs<B> S_;
+    static_assert(S_::MT <= 2, "two instructions per k-step");
+    const S_ S(lane);
+    double aop[S_::MT][S_::KS], bop[S_::KS], acc[S_::MT];
+    S.template load_a<false>(P, aop);
+    S.load_b(Wr, bop);
+    S.mul(aop, bop, acc);
+    return v2d{acc[0], S_::MT > 1 ? acc[S_::MT - 1] : 0.0};
+}
+// the same as FUNCTIONS, for the single-workgroup top: its body has no registers to spare (248 of 256 before the small
+// products), and what a call costs -- the registers of the small products are the callee's -- is a few dozen clocks
+template <int B>
+__device__ __noinline__ void bcr_rs_phase1_call(const double *Di, const double *Q, double *Ri, double *Rc, int lane, bool hasQ) {
+    bcr_rs_phase1<B>(Di, Q, Ri, Rc, nullptr, lane, hasQ);
+}
+template <int B>
+__device__ __noinline__ v2d bcr_rs_pw_call(const double *P, const double *Wr, int lane) {
+    return bcr_rs_pw<B>(P, Wr, lane);
+}
+
 // The matrix-core part of one block elimination. The 16-column tiles of W are independent of each other in all
 // three products, so they are dealt to the waves of the elimination's group (one wave in the first round of a
 // four-wave workgroup, two in the second, four in the third; four from the start in a sixteen-wave workgroup):
 // this wave owns the tiles nt = part, part + WPE, ... and keeps them in w[][slot] between the phases (workgroup
 // barriers lie in between). NTPW: slots of a wave.
-template <int B, int NR, int NTPW>
+// RSCALL: the small products of the right-hand sides are calls (bcr_top_body)
+template <int B, int NR, int NTPW, bool RSCALL = false>
 struct BcrElim {
     typedef BcrDim<B, NR> Dm;
     v4d w[Dm::MT][NTPW];
+    // the last column tile holds W_R alone: its owner runs it as small products (BcrRs), in every phase. With WPE waves
+    // per elimination that is the wave of part (NT - 1) % WPE, in its slot (NT - 1) / WPE -- the same in all four functions
+    static constexpr bool RS = NR == 3 && 16 * (Dm::NT - 1) == 2 * B;
+    template <int WPE>
+    __device__ __forceinline__ static bool rs_mine(int part) {
+        return RS && part == (Dm::NT - 1) % WPE;
+    }
+#define IRH_RS_SKIP(sl) (SM && (sl) == (Dm::NT - 1) / WPE)
 
     // W = Di^-1 [P' | Q | R] (Di^-1 in LDS), W -> global (the way back reads it), and the right neighbour:
     // D_c -= Q' W_Q, R_c -= Q' W_R
@@ -380,10 +499,30 @@ struct BcrElim {
     // nullptr: W is not wanted in memory)
     template <int WPE>
     __device__ __forceinline__ void phase1(int part, const double *Di, const double *P, bool hasP, const double *Q,
-                                           const double *Ri, double *Dc, double *Rc, double *Wg, const double *zero,
+                                           double *Ri, double *Dc, double *Rc, double *Wg, const double *zero,
                                            int lane, bool hasQ = true) {
+        if (rs_mine<WPE>(part)) phase1_t<WPE, true>(part, Di, P, hasP, Q, Ri, Dc, Rc, Wg, zero, lane, hasQ);
+        else phase1_t<WPE, false>(part, Di, P, hasP, Q, Ri, Dc, Rc, Wg, zero, lane, hasQ);
+    }
+    __device__ __forceinline__ void rs_phase1(const double *Di, const double *Q, double *Ri, double *Rc, double *Wg, int lane,
+                                              bool hasQ) const {
+        if constexpr (!RS) return;
+        else if constexpr (RSCALL) bcr_rs_phase1_call<B>(Di, Q, Ri, Rc, lane, hasQ);
+        else bcr_rs_phase1<B>(Di, Q, Ri, Rc, Wg, lane, hasQ);
+    }
+    template <int WPE, bool SM>
+    __device__ __forceinline__ void phase1_t(int part, const double *Di, const double *P, bool hasP, const double *Q,
+                                             double *Ri, double *Dc, double *Rc, double *Wg, const double *zero,
+                                             int lane, bool hasQ) {
         constexpr int NS = (Dm::NT + WPE - 1) / WPE;
         static_assert(NS <= NTPW, "slots");
+        if (SM) {
+            rs_phase1(Di, Q, Ri, Rc, Wg, lane, hasQ);
+            if (NS == 1) return;
+            // (the wide tiles' operands are not requested while the small products' are live: the sixteen-block top
+            // has no registers to spare)
+            __builtin_amdgcn_sched_barrier(0);
+        }
         double aop[Dm::MT][Dm::KS];
         // (the inverse is symmetric: read by columns -- consecutive lanes, consecutive words -- instead of by rows, whose
         // stride of 2 B words puts sixteen lanes on four banks)
@@ -424,14 +563,17 @@ struct BcrElim {
 #pragma unroll
             for (int sl = 0; sl < NS; sl++) bop[sl] = base[sl][(4 * s + lk) * stride[sl]];
 #pragma unroll
-            for (int sl = 0; sl < NS; sl++)
+            for (int sl = 0; sl < NS; sl++) {
+                if (IRH_RS_SKIP(sl)) continue;
 #pragma unroll
                 for (int mt = 0; mt < Dm::MT; mt++)
                     w[mt][sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[mt][s], bop[sl], w[mt][sl], 0, 0, 0);
+            }
         }
         if (Wg) {
 #pragma unroll
             for (int sl = 0; sl < NS; sl++) {
+                if (IRH_RS_SKIP(sl)) continue;
                 const int j = 16 * (part + sl * WPE) + lj;
 #pragma unroll
                 for (int mt = 0; mt < Dm::MT; mt++)
@@ -454,7 +596,7 @@ struct BcrElim {
 #pragma unroll
             for (int sl = 0; sl < NS; sl++) {
                 const int nt = part + sl * WPE;
-                if (nt >= Dm::NT || nt < Dm::NT0) continue;
+                if (nt >= Dm::NT || nt < Dm::NT0 || IRH_RS_SKIP(sl)) continue;
 #pragma unroll
                 for (int mt = 0; mt < Dm::MT; mt++)
                     out[mt][sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[mt][s], w[s >> 2][sl][s & 3], out[mt][sl], 0, 0, 0);
@@ -462,7 +604,7 @@ struct BcrElim {
 #pragma unroll
         for (int sl = 0; sl < NS; sl++) {
             const int nt = part + sl * WPE;
-            if (nt >= Dm::NT || nt < Dm::NT0) continue;
+            if (nt >= Dm::NT || nt < Dm::NT0 || IRH_RS_SKIP(sl)) continue;
             const int c = 16 * nt + lj;
 #pragma unroll
             for (int mt = 0; mt < Dm::MT; mt++)
@@ -483,12 +625,18 @@ struct BcrElim {
     // D_i^-1, W_Q over Q, W_R over R_i (after the barrier behind phase1: nobody reads those any more)
     template <int WPE>
     __device__ __forceinline__ void keep_w(int part, double *Di, double *Q, bool hasQ, double *Ri, int lane) const {
+        // (the small products have left W_R over R_i already)
+        if (rs_mine<WPE>(part)) keep_w_t<WPE, true>(part, Di, Q, hasQ, Ri, lane);
+        else keep_w_t<WPE, false>(part, Di, Q, hasQ, Ri, lane);
+    }
+    template <int WPE, bool SM>
+    __device__ __forceinline__ void keep_w_t(int part, double *Di, double *Q, bool hasQ, double *Ri, int lane) const {
         constexpr int NS = (Dm::NT + WPE - 1) / WPE;
         const int lj = lane & 15, lk = lane >> 4;
 #pragma unroll
         for (int sl = 0; sl < NS; sl++) {
             const int nt = part + sl * WPE;
-            if (nt >= Dm::NT) continue;
+            if (nt >= Dm::NT || IRH_RS_SKIP(sl)) continue;
             const int j = 16 * nt + lj;
 #pragma unroll
             for (int mt = 0; mt < Dm::MT; mt++)
@@ -510,20 +658,38 @@ struct BcrElim {
 
     // left neighbour, first half: the products P W (P is read by every wave of the group, and overwritten in
     // the second half -- a barrier lies in between when the group has more than one wave)
+    // (Wr: where phase1 left W_R -- the place of R_i)
     template <int WPE>
-    __device__ __forceinline__ void phase2_mul(int part, const double *P, v4d (&out)[Dm::MT][NTPW], int lane) {
+    __device__ __forceinline__ void phase2_mul(int part, const double *P, const double *Wr, v4d (&out)[Dm::MT][NTPW], int lane) {
+        if (rs_mine<WPE>(part)) phase2_mul_t<WPE, true>(part, P, Wr, out, lane);
+        else phase2_mul_t<WPE, false>(part, P, Wr, out, lane);
+    }
+    template <int WPE, bool SM>
+    __device__ __forceinline__ void phase2_mul_t(int part, const double *P, const double *Wr, v4d (&out)[Dm::MT][NTPW], int lane) {
         constexpr int NS = (Dm::NT + WPE - 1) / WPE;
+        if (SM) {
+            // P W_R: the lane's entry of instruction t travels in out[t][slot][0]
+            if constexpr (RS) {
+                const v2d acc = RSCALL ? bcr_rs_pw_call<B>(P, Wr, lane) : bcr_rs_pw<B>(P, Wr, lane);
+#pragma unroll
+                for (int t = 0; t < Dm::MT; t++) out[t][(Dm::NT - 1) / WPE][0] = acc[t];  // (the other three: not read)
+            }
+            if (NS == 1) return;
+            __builtin_amdgcn_sched_barrier(0);
+        }
         double aop[Dm::MT][Dm::KS];
         bcr_load_a<B, false>(P, lane, aop);
 #pragma unroll
-        for (int sl = 0; sl < NS; sl++)
+        for (int sl = 0; sl < NS; sl++) {
+            if (IRH_RS_SKIP(sl)) continue;
 #pragma unroll
             for (int mt = 0; mt < Dm::MT; mt++) out[mt][sl] = v4d{0.0, 0.0, 0.0, 0.0};
+        }
 #pragma unroll
         for (int s = 0; s < Dm::KS; s++)
 #pragma unroll
             for (int sl = 0; sl < NS; sl++) {
-                if (part + sl * WPE >= Dm::NT) continue;
+                if (part + sl * WPE >= Dm::NT || IRH_RS_SKIP(sl)) continue;
 #pragma unroll
                 for (int mt = 0; mt < Dm::MT; mt++)
                     out[mt][sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[mt][s], w[s >> 2][sl][s & 3], out[mt][sl], 0, 0, 0);
@@ -534,12 +700,29 @@ struct BcrElim {
     template <int WPE>
     __device__ __forceinline__ void phase2_put(int part, const v4d (&out)[Dm::MT][NTPW], double *P, double *Da,
                                                bool assign, double *Ra, int lane) {
+        if (rs_mine<WPE>(part)) phase2_put_t<WPE, true>(part, out, P, Da, assign, Ra, lane);
+        else phase2_put_t<WPE, false>(part, out, P, Da, assign, Ra, lane);
+    }
+    template <int WPE, bool SM>
+    __device__ __forceinline__ void phase2_put_t(int part, const v4d (&out)[Dm::MT][NTPW], double *P, double *Da,
+                                                 bool assign, double *Ra, int lane) {
         constexpr int NS = (Dm::NT + WPE - 1) / WPE;
+        if (SM) {
+            if constexpr (RS) {
+                const BcrRs<B> S(lane);
+#pragma unroll
+                for (int t = 0; t < Dm::MT; t++) {
+                    const int row = S.row(t);
+                    if (row >= 0) Ra[row * NR + S.dj] -= out[t][(Dm::NT - 1) / WPE][0];
+                }
+            }
+            if (NS == 1) return;
+        }
         const int lj = lane & 15, lk = lane >> 4;
 #pragma unroll
         for (int sl = 0; sl < NS; sl++) {
             const int nt = part + sl * WPE;
-            if (nt >= Dm::NT) continue;
+            if (nt >= Dm::NT || IRH_RS_SKIP(sl)) continue;
             const int c = 16 * nt + lj;
 #pragma unroll
             for (int mt = 0; mt < Dm::MT; mt++)
@@ -558,6 +741,7 @@ struct BcrElim {
                 }
         }
     }
+#undef IRH_RS_SKIP
 };
 
 // One row of the level-0 operator into the block arrays of a chunk: `row` lies in block lb (rows lb B ...), r = its
@@ -684,9 +868,10 @@ __device__ __forceinline__ void bcr_st(double *p, double v) {
 // UF (the unit-weight factor, BcrUnit): 1 = the full reduction also keeps the operands of its products (Dinvg, stP, stQ; W is
 // the store's Wu); 2 = the RIGHT-HAND-SIDE-ONLY pass over a kept factor: the gather takes the right-hand sides alone, no
 // sweep -- D_i^-1, P and Q are the stored bits, read from memory as the products' A-operands --, and the three phases run
-// for the one column tile that holds W_R (nt = NT - 1 = 2 B / 16: for B = 8 / 16 / 24 it holds nothing else), on the wave
-// that owns the elimination's sweep in the full form. A column tile of a matrix-core product does not depend on the other
-// tiles, the K order and the subtractions of the puts are the same code: R_a, R_c, W_R, sepR, extR come out bit for bit.
+// for the one column tile that holds W_R (nt = NT - 1 = 2 B / 16: for B = 8 / 16 / 24 it holds nothing else, and runs as
+// small products: BcrRs), on the wave that owns the elimination's sweep in the full form. The right-hand-side products do
+// not depend on the other tiles, the functions, their K order and the subtractions of the puts are the same code: R_a, R_c,
+// W_R, sepR, extR come out bit for bit.
 template <int B, int NR, bool L0, bool TOP, int NW, bool COH, int UF = 0>
 __device__ __forceinline__ void bcr_reduce_body(
     const int chunk, double (*sDG)[B * B], double (*sR)[B * NR], double *sZ,
@@ -790,7 +975,7 @@ __device__ __forceinline__ void bcr_reduce_body(
                                       sR[c + 1], W + el * B * Dm::NC, sZ, lane);                                    \
         __syncthreads();                                                                                            \
         if (active && hasP) {                                                                                       \
-            E.template phase2_mul<Dm::NT>(Dm::NT - 1, stP + el * BB, out, lane);                                    \
+            E.template phase2_mul<Dm::NT>(Dm::NT - 1, stP + el * BB, sR[i + 1], out, lane);                         \
             E.template phase2_put<Dm::NT>(Dm::NT - 1, out, sZ, sZ, false, sR[a + 1], lane);                         \
         }                                                                                                           \
         __syncthreads();                                                                                            \
@@ -1019,7 +1204,7 @@ __device__ __forceinline__ void bcr_reduce_body(
                                    W + ((size_t)chunk * 7 + i) * B * Dm::NC, sZ, lane);                             \
         __syncthreads();                                                                                            \
         bcr_stamp(stamps, 4 + 4 * RND);                                                                             \
-        if (active && hasP && !(dbg & 4)) E.template phase2_mul<WPE>(part, sG[a + 1], out, lane);                   \
+        if (active && hasP && !(dbg & 4)) E.template phase2_mul<WPE>(part, sG[a + 1], sR[i + 1], out, lane);        \
         if (WPE > 1) __syncthreads();                                                                               \
         bcr_stamp(stamps, 5 + 4 * RND);                                                                             \
         if (active && hasP && !(dbg & 4))                                                                           \
@@ -1194,6 +1379,12 @@ static size_t bcr_top_lds(int B, int n) {
     return ((size_t)(2 * n - 1) * B * B + (size_t)2 * n * B * 3 + 2) * sizeof(double) + sizeof(BcrTopSched);
 }
 
+// (the filling solve's copies of a block into the store, as a function: see bcr_rs_phase1_call)
+template <int BB>
+__device__ __noinline__ void bcr_top_keep(double *dst, const double *src, bool have, int lane) {
+    for (int o = lane; o < BB; o += 64) dst[o] = have ? src[o] : 0.0;
+}
+
 // UF (BcrUnit::top): 1 = the operands of every scheduled elimination, what it leaves for the way back and the inverse of the
 // block that is left are also written to tst; 2 = the right-hand-side-only pass: they are read from there (see bcr_reduce_body)
 template <int B, int NW, bool COH, int UF = 0>
@@ -1251,25 +1442,29 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
     // ---- the rounds ----
     for (int r = 0; r < T.nr; r++) {
         const int ne = T.ne[r];
+        // (the lane number as the round sees it is opaque: what the products derive from it -- dozens of offsets per
+        // instantiation -- is formed again in every round instead of living in registers across the whole loop)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
         if constexpr (UF == 2) {
             const bool active = wave < ne;
             const int i = active ? T.i[r][wave] : 0, a = active ? T.a[r][wave] : -1, c = active ? T.c[r][wave] : -1;
             const bool hasP = a >= 0, hasQ = c >= 0;
             const double *op = tst + (size_t)5 * (4 * r + (active ? wave : 0)) * BB;  // D_i^-1, P, Q
-            BcrElim<B, NR, 1> E;
+            BcrElim<B, NR, 1, true> E;
             v4d out[Dm::MT][1];
             if (active)
                 E.template phase1<Dm::NT>(Dm::NT - 1, op, op + BB, hasP, op + 2 * BB, sR[i], sZ, hasQ ? sR[c] : sR[i],
-                                          (double *)nullptr, sZ, lane, hasQ);
+                                          (double *)nullptr, sZ, ln, hasQ);
             __syncthreads();
-            if (active && hasP) E.template phase2_mul<Dm::NT>(Dm::NT - 1, op + BB, out, lane);
-            if (active) E.template keep_w<Dm::NT>(Dm::NT - 1, sZ, sZ, hasQ, sR[i], lane);
+            if (active && hasP) E.template phase2_mul<Dm::NT>(Dm::NT - 1, op + BB, sR[i], out, ln);
+            if (active) E.template keep_w<Dm::NT>(Dm::NT - 1, sZ, sZ, hasQ, sR[i], ln);
             __syncthreads();
-            if (active && hasP) E.template phase2_put<Dm::NT>(Dm::NT - 1, out, sZ, sZ, false, sR[a], lane);
+            if (active && hasP) E.template phase2_put<Dm::NT>(Dm::NT - 1, out, sZ, sZ, false, sR[a], ln);
             __syncthreads();
             continue;
         }
-        if (wave < ne && !(dbg & 1)) bcr_invert<B>(sD[T.i[r][wave]], lane);
+        if (wave < ne && !(dbg & 1)) bcr_invert<B>(sD[T.i[r][wave]], ln);
         __syncthreads();
         bcr_stamp(stamps, 2 + 2 * r);
         auto products = [&](auto wpe_tag) {
@@ -1279,32 +1474,30 @@ __device__ __forceinline__ void bcr_top_body(double *smem, const BcrTopSched *__
             const bool active = e < ne;
             const int i = active ? T.i[r][e] : 0, a = active ? T.a[r][e] : -1, c = active ? T.c[r][e] : -1;
             const bool hasP = a >= 0, hasQ = c >= 0;
-            BcrElim<B, NR, 2> E;
+            BcrElim<B, NR, 2, true> E;
             v4d out[Dm::MT][2];
             double *op = UF == 1 ? tst + (size_t)5 * (4 * r + (active ? e : 0)) * BB : nullptr;
             if constexpr (UF == 1)
-                if (active && part == 0)
-                    for (int o = lane; o < BB; o += 64) {
-                        op[o] = sD[i][o];
-                        op[BB + o] = hasP ? sG[a][o] : 0.0;
-                        op[2 * BB + o] = hasQ ? sG[i][o] : 0.0;
-                    }
+                if (active && part == 0) {
+                    bcr_top_keep<BB>(op, sD[i], true, ln);
+                    bcr_top_keep<BB>(op + BB, hasP ? sG[a] : sZ, hasP, ln);
+                    bcr_top_keep<BB>(op + 2 * BB, hasQ ? sG[i] : sZ, hasQ, ln);
+                }
             if (active && !(dbg & 2))
                 E.template phase1<WPE>(part, sD[i], hasP ? sG[a] : sZ, hasP, hasQ ? sG[i] : sZ, sR[i], hasQ ? sD[c] : sD[i],
-                                       hasQ ? sR[c] : sR[i], (double *)nullptr, sZ, lane, hasQ);
+                                       hasQ ? sR[c] : sR[i], (double *)nullptr, sZ, ln, hasQ);
             __syncthreads();
-            if (active && hasP && !(dbg & 4)) E.template phase2_mul<WPE>(part, sG[a], out, lane);
-            if (active && !(dbg & 2)) E.template keep_w<WPE>(part, sD[i], hasQ ? sG[i] : sZ, hasQ, sR[i], lane);
+            if (active && hasP && !(dbg & 4)) E.template phase2_mul<WPE>(part, sG[a], sR[i], out, ln);
+            if (active && !(dbg & 2)) E.template keep_w<WPE>(part, sD[i], hasQ ? sG[i] : sZ, hasQ, sR[i], ln);
             __syncthreads();
-            if (active && hasP && !(dbg & 4)) E.template phase2_put<WPE>(part, out, sG[a], sD[a], false, sR[a], lane);
+            if (active && hasP && !(dbg & 4)) E.template phase2_put<WPE>(part, out, sG[a], sD[a], false, sR[a], ln);
             __syncthreads();
             // (what keep_w left: nobody writes the places of an eliminated block any more)
             if constexpr (UF == 1)
-                if (active && part == 0)
-                    for (int o = lane; o < BB; o += 64) {
-                        op[3 * BB + o] = sD[i][o];
-                        op[4 * BB + o] = hasQ ? sG[i][o] : 0.0;
-                    }
+                if (active && part == 0) {
+                    bcr_top_keep<BB>(op + 3 * BB, sD[i], true, ln);
+                    bcr_top_keep<BB>(op + 4 * BB, hasQ ? sG[i] : sZ, hasQ, ln);
+                }
         };
         if (ne > 2) products(std::integral_constant<int, 2>());
         else products(std::integral_constant<int, 4>());
@@ -3731,6 +3924,73 @@ int bcr_stamps(Graph &g, int level, int chunk, double *out) {
     IRH_CHECK(hipMemcpyAsync(h, S.stamps.p + (size_t)chunk * 16, sizeof(h), hipMemcpyDeviceToHost, g.stream));
     IRH_CHECK(hipStreamSynchronize(g.stream));
     for (int k = 0; k < 16; k++) out[k] = h[k] ? (double)(h[k] - h[0]) : -1.0;
+    return IROTAVG_OK;
+}
+
+// diagnostic (irotavg_bcr_rhs_products): ONE wave through the right-hand-side products of an elimination, as the
+// right-hand-side-only pass calls them (operands in memory, right-hand sides in LDS)
+template <int B>
+__global__ __launch_bounds__(64) void k_bcr_rhs_products(const double *__restrict__ Dinv, const double *__restrict__ P,
+                                                         const double *__restrict__ Q, const double *__restrict__ R, int hasP,
+                                                         int hasQ, double *__restrict__ WR, double *__restrict__ Ra,
+                                                         double *__restrict__ Rc) {
+    constexpr int NR = 3, XB = B * NR;
+    typedef BcrDim<B, NR> Dm;
+    __shared__ double sR[3][XB], sZ[2];
+    const int lane = threadIdx.x;
+    for (int e = lane; e < XB; e += 64) {
+        sR[0][e] = R[e];
+        sR[1][e] = Ra[e];
+        sR[2][e] = Rc[e];
+    }
+    if (lane < 2) sZ[lane] = 0.0;
+    __syncthreads();
+    BcrElim<B, NR, 1> E;
+    v4d out[Dm::MT][1];
+    E.template phase1<Dm::NT>(Dm::NT - 1, Dinv, P, hasP != 0, Q, sR[0], sZ, sR[2], (double *)nullptr, sZ, lane, hasQ != 0);
+    __syncthreads();
+    if (hasP) {
+        E.template phase2_mul<Dm::NT>(Dm::NT - 1, P, sR[0], out, lane);
+        E.template phase2_put<Dm::NT>(Dm::NT - 1, out, sZ, sZ, false, sR[1], lane);
+    }
+    __syncthreads();
+    for (int e = lane; e < XB; e += 64) {
+        WR[e] = sR[0][e];
+        Ra[e] = sR[1][e];
+        Rc[e] = sR[2][e];
+    }
+}
+template <int B>
+static void bcr_rhs_products_run(const double *d, int hasP, int hasQ, hipStream_t s) {
+    constexpr int BB = B * B, XB = B * 3;
+    static_assert(BcrElim<B, 3, 1>::RS, "block size");
+    double *o = const_cast<double *>(d) + 3 * BB + XB;
+    k_bcr_rhs_products<B><<<1, 64, 0, s>>>(d, d + BB, d + 2 * BB, d + 3 * BB, hasP, hasQ, o, o + XB, o + 2 * XB);
+    IRH_CHECK(hipGetLastError());
+}
+int bcr_rhs_products(int B, const double *Dinv, const double *P, const double *Q, const double *R, int hasP, int hasQ,
+                     double *WR, double *Ra, double *Rc) {
+    if (B != 8 && B != 16 && B != 24 && B != 32) return IROTAVG_ERR_BAD_ARG;
+    hipStream_t s = nullptr;
+    const size_t BB = (size_t)B * B, XB = (size_t)B * 3;
+    DevBuf<double> d;  // D^-1 | P | Q | R | W_R | R_a | R_c
+    d.alloc(3 * BB + 4 * XB);
+    IRH_CHECK(hipMemcpyAsync(d.p, Dinv, BB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + BB, P, BB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + 2 * BB, Q, BB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + 3 * BB, R, XB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + 3 * BB + 2 * XB, Ra, XB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + 3 * BB + 3 * XB, Rc, XB * sizeof(double), hipMemcpyHostToDevice, s));
+    switch (B) {
+    case 8: bcr_rhs_products_run<8>(d.p, hasP, hasQ, s); break;
+    case 16: bcr_rhs_products_run<16>(d.p, hasP, hasQ, s); break;
+    case 24: bcr_rhs_products_run<24>(d.p, hasP, hasQ, s); break;
+    default: bcr_rhs_products_run<32>(d.p, hasP, hasQ, s); break;
+    }
+    IRH_CHECK(hipMemcpyAsync(WR, d.p + 3 * BB + XB, XB * sizeof(double), hipMemcpyDeviceToHost, s));
+    IRH_CHECK(hipMemcpyAsync(Ra, d.p + 3 * BB + 2 * XB, XB * sizeof(double), hipMemcpyDeviceToHost, s));
+    IRH_CHECK(hipMemcpyAsync(Rc, d.p + 3 * BB + 3 * XB, XB * sizeof(double), hipMemcpyDeviceToHost, s));
+    IRH_CHECK(hipStreamSynchronize(s));
     return IROTAVG_OK;
 }
 

@@ -427,6 +427,14 @@ int irotavg_graph_edge_diagnostics(irotavg_graph *h, double *edge_var, double *l
     API_CATCH
 }
 
+int irotavg_bcr_rhs_products(int B, const double *Dinv, const double *P, const double *Q, const double *R, int hasP,
+                             int hasQ, double *WR, double *Ra, double *Rc) {
+    if (!Dinv || !P || !Q || !R || !WR || !Ra || !Rc) return IROTAVG_ERR_BAD_ARG;
+    API_TRY
+    return bcr_rhs_products(B, Dinv, P, Q, R, hasP, hasQ, WR, Ra, Rc);
+    API_CATCH
+}
+
 int irotavg_graph_direct_residual(irotavg_graph *h, double *relres) {
     if (!h || !relres) return IROTAVG_ERR_BAD_ARG;
     API_TRY

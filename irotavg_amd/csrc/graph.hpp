@@ -412,6 +412,9 @@ const int *bcr_gate_skip_word(Graph &g);  // flags[FL_DONE] = 1 unless the last 
 void dense_invert_spd(Graph &g, double *A, int npad);  // in place, npad a multiple of 64 (dense.hip)
 int bcr_stamps(Graph &g, int level, int chunk, double *out);  // development aid
 int bcr_stamps_up(Graph &g, double *out);                      // development aid: 32 x 8 stamps of k_bcr_reduce_up
+// diagnostic (irotavg_bcr_rhs_products): one wave through the right-hand-side products of an elimination, host arrays
+int bcr_rhs_products(int B, const double *Dinv, const double *P, const double *Q, const double *R, int hasP, int hasQ,
+                     double *WR, double *Ra, double *Rc);
 // the last direct solve went through the single-launch upper reduction and a workgroup of it gave up waiting (its solution
 // is all NaN): clears the word, switches the handle to level-by-level launches and says so (one small synchronous read)
 bool bcr_up_failed(Graph &g);
