@@ -10,7 +10,8 @@
 //      planes  rs == 1, cs even, 16-byte aligned: 16-byte accesses on both sides, two rows per thread;
 //      generic anything else that does not alias: 8-byte accesses (coalesced on the handle's side);
 //  * argument checks that keep a wrong pointer away from every kernel: strides that alias, and the lowest and highest
-//    element of every array asked of hipPointerGetAttributes (device memory of the handle's device, or BAD_ARG).
+//    element of every array asked of the runtime (device memory of the handle's device and both in one allocation, so
+//    that everything between them is mapped too, or BAD_ARG).
 // The kernels stream: no reuse, one or two rows per thread, 256-thread workgroups, a grid that covers the array once.
 #include <hip/hip_runtime.h>
 
@@ -148,27 +149,57 @@ bool dev_ptr_ok(const void *p, int device) {
     }
     return at.type == hipMemoryTypeDevice && at.device == device;
 }
+inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+// The elements *first .. *last are device memory of `device` with no unmapped address between them. Asking the runtime
+// about the two ends alone is not enough: an array claimed gigabytes longer than it is can end inside somebody else's
+// allocation -- late in a long process much of the address space is somebody's -- and the kernel then faults on the way
+// there. So the allocation around the first element must reach past the last, directly or through allocations that
+// follow it without a gap (span_covered, winbatch.hpp). In the usual case this is one hipPointerGetAttributes and one
+// hipMemGetAddressRange: as many runtime calls as the two ends took. Memory whose allocation the runtime cannot name is
+// judged by its two ends, as it always was.
+template <typename T>
+bool dev_span_ok(const T *first, const T *last, int device) {
+    if (!dev_ptr_ok(first, device)) return false;
+    bool hop = false;
+    const int covered = span_covered(reinterpret_cast<uintptr_t>(first), reinterpret_cast<uintptr_t>(last + 1),
+                                     [&](uintptr_t at, uintptr_t &base, size_t &size) {
+                                         void *p = reinterpret_cast<void *>(at);
+                                         hipDeviceptr_t b = nullptr;
+                                         if ((hop && !dev_ptr_ok(p, device)) || hipMemGetAddressRange(&b, &size, p) != hipSuccess) {
+                                             (void)hipGetLastError();
+                                             return false;
+                                         }
+                                         hop = true;
+                                         base = reinterpret_cast<uintptr_t>(b);
+                                         return true;
+                                     });
+    return covered < 0 ? dev_ptr_ok(last, device) : covered == 1;
+}
 // the lowest and the highest element of the matrix (negative strides reach below ptr)
 bool dev_matrix_ok(const double *p, int64_t rows, int cols, int64_t rs, int64_t cs, int device) {
-    if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return false;
+    if (!aligned8(p)) return false;
     int64_t lo, hi;
     matrix_span(rows, cols, rs, cs, lo, hi);
-    return dev_ptr_ok(p + lo, device) && dev_ptr_ok(p + hi, device);
+    return dev_span_ok(p + lo, p + hi, device);
 }
 bool dev_vector_ok(const double *p, int64_t n, int device) { return dev_matrix_ok(p, n, 1, 1, 1, device); }
+// `rows` pairs of ids: the first and the last int32
+bool dev_index_ok(const int32_t *p, int64_t rows, int device) { return dev_span_ok(p, p + 2 * rows - 1, device); }
 
-// the checks irotavg_window_solve_batch_dev, irotavg_window_uncertainty_batch_dev and irotavg_window_gate_batch_dev make of the packed problem arrays
-// before any device work (alignment, the stride rule), and with a device (the lowest and the highest element of each)
-bool win_arrays_host_ok(const void *I, const double *QQ, int64_t qq_rs, int64_t qq_cs, const double *Q, int64_t q_rs,
-                        int64_t q_cs, const double *w, int64_t sum_m, int64_t sum_n) {
-    return (reinterpret_cast<uintptr_t>(I) & 7) == 0 && (reinterpret_cast<uintptr_t>(QQ) & 7) == 0 &&
-           (reinterpret_cast<uintptr_t>(Q) & 7) == 0 && (reinterpret_cast<uintptr_t>(w) & 7) == 0 &&
-           strides_ok(sum_m, 4, qq_rs, qq_cs) && strides_ok(sum_n, 4, q_rs, q_cs);
-}
-bool win_arrays_dev_ok(const int32_t *I, const double *QQ, int64_t qq_rs, int64_t qq_cs, const double *Q, int64_t q_rs,
-                       int64_t q_cs, const double *w, int64_t sum_m, int64_t sum_n, int device) {
-    return dev_ptr_ok(I, device) && dev_ptr_ok(I + 2 * sum_m - 1, device) && dev_matrix_ok(QQ, sum_m, 4, qq_rs, qq_cs, device) &&
-           dev_matrix_ok(Q, sum_n, 4, q_rs, q_cs, device) && (!w || dev_vector_ok(w, sum_m, device));
+// The checks every batched window call makes of its packed problem arrays (A: WinBatchArrays or WinCovArrays), in the
+// order the calls have always had: before any device work alignment and the stride rule (BAD_ARG), then a device at all
+// (NO_DEVICE), then the calling thread's current one -> `device`, then the lowest and the highest element of each array
+// (BAD_ARG). A call's own host checks go in front of this, its own pointer checks behind it.
+template <class Arrays>
+int win_arrays_check(const Arrays &A, int64_t sum_m, int64_t sum_n, int &device) {
+    if (!aligned8(A.I) || !aligned8(A.QQ) || !aligned8(A.Q) || !aligned8(A.weights) || !strides_ok(sum_m, 4, A.qq_rs, A.qq_cs) ||
+        !strides_ok(sum_n, 4, A.q_rs, A.q_cs))
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    IRH_CHECK(hipGetDevice(&device));
+    const bool ok = dev_index_ok(A.I, sum_m, device) && dev_matrix_ok(A.QQ, sum_m, 4, A.qq_rs, A.qq_cs, device) &&
+                    dev_matrix_ok(A.Q, sum_n, 4, A.q_rs, A.q_cs, device) && (!A.weights || dev_vector_ok(A.weights, sum_m, device));
+    return ok ? IROTAVG_OK : IROTAVG_ERR_BAD_ARG;
 }
 
 // the ordering contract of a call on an existing handle
@@ -243,15 +274,13 @@ int irotavg_graph_create_dev(irotavg_graph **out, int64_t m, int64_t n_total, in
     if (!out) return IROTAVG_ERR_BAD_ARG;
     *out = nullptr;
     if (!I_dev || !QQ_dev || m <= 0 || m > 0x3fffffffLL || n_total <= 0 || f < 0 || n_total - f < 1 ||
-        n_total > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(I_dev) & 7) != 0 || !strides_ok(m, 4, qq_rs, qq_cs))
+        n_total > 0x7fffffffLL || !aligned8(I_dev) || !strides_ok(m, 4, qq_rs, qq_cs))
         return IROTAVG_ERR_BAD_ARG;
     if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
     return guarded([&]() -> int {
         int device = opt ? opt->device : -1;
         if (device < 0) IRH_CHECK(hipGetDevice(&device));
-        if (!dev_ptr_ok(I_dev, device) || !dev_ptr_ok(I_dev + 2 * m - 1, device) ||
-            !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device))
-            return IROTAVG_ERR_BAD_ARG;
+        if (!dev_index_ok(I_dev, m, device) || !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device)) return IROTAVG_ERR_BAD_ARG;
         DevEdgeSrc src;
         src.I = reinterpret_cast<const int2 *>(I_dev);
         src.qq = QQ_dev;
@@ -373,15 +402,10 @@ int irotavg_window_solve_batch_dev(int64_t nb, const int32_t *sizes, const int32
     return guarded([&]() -> int {
         WinBatchPlan plan;
         if (!winbatch_plan(nb, sizes, kernel, plan)) return IROTAVG_ERR_BAD_ARG;
-        if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n))
-            return IROTAVG_ERR_BAD_ARG;
-        if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
-        int device = 0;
-        IRH_CHECK(hipGetDevice(&device));
-        if (!win_arrays_dev_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n, device))
-            return IROTAVG_ERR_BAD_ARG;
         const WinBatchArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
                                weights_dev};
+        int device = 0;
+        if (const int rc = win_arrays_check(A, plan.sum_m, plan.sum_n, device); rc != IROTAVG_OK) return rc;
         return window_solve_batch_dev(plan, device, A, cost, sigma, l1_iters, irls_iters, change_th, results,
                                       static_cast<hipStream_t>(stream));
     });
@@ -398,15 +422,10 @@ int irotavg_window_init_mst_batch_dev(int64_t nb, const int32_t *sizes, const in
         if (!winbatch_plan(nb, sizes, 1, plan)) return IROTAVG_ERR_BAD_ARG;  // kernel 1: one list, in the caller's order
         for (const WinDesc &d : plan.desc)
             if (d.f < 1) return IROTAVG_ERR_BAD_ARG;  // irotavg_init_mst refuses f <= 0
-        if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, nullptr, plan.sum_m, plan.sum_n))
-            return IROTAVG_ERR_BAD_ARG;
-        if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
-        int device = 0;
-        IRH_CHECK(hipGetDevice(&device));
-        if (!win_arrays_dev_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, nullptr, plan.sum_m, plan.sum_n, device))
-            return IROTAVG_ERR_BAD_ARG;
         const WinBatchArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
                                nullptr};
+        int device = 0;
+        if (const int rc = win_arrays_check(A, plan.sum_m, plan.sum_n, device); rc != IROTAVG_OK) return rc;
         return window_init_mst_batch_dev(plan, device, A, results, static_cast<hipStream_t>(stream));
     });
 }
@@ -424,28 +443,20 @@ int irotavg_window_uncertainty_batch_dev(int64_t nb, const int32_t *sizes, const
         if (!wincov_plan(nb, sizes, npairs, nullptr, plan)) return IROTAVG_ERR_BAD_ARG;
         if (!wincov_asked(var_dev, plan.sum_p, pairs_dev && pair_var_dev, edge_var_dev, leverage_dev, chi2_dev, scale))
             return IROTAVG_ERR_BAD_ARG;
-        if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n))
-            return IROTAVG_ERR_BAD_ARG;
         double *const per_edge[3] = {edge_var_dev, leverage_dev, chi2_dev};
         for (double *p : per_edge)
-            if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return IROTAVG_ERR_BAD_ARG;
-        if ((reinterpret_cast<uintptr_t>(var_dev) & 7) != 0 ||
-            (plan.sum_p > 0 && ((reinterpret_cast<uintptr_t>(pairs_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(pair_var_dev) & 7) != 0)))
-            return IROTAVG_ERR_BAD_ARG;
-        if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
-        int device = 0;
-        IRH_CHECK(hipGetDevice(&device));
-        if (!win_arrays_dev_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n, device))
-            return IROTAVG_ERR_BAD_ARG;
-        for (double *p : per_edge)
-            if (p && !dev_vector_ok(p, plan.sum_m, device)) return IROTAVG_ERR_BAD_ARG;
-        if (var_dev && !dev_vector_ok(var_dev, plan.sum_n, device)) return IROTAVG_ERR_BAD_ARG;
-        if (plan.sum_p > 0 && (!dev_ptr_ok(pairs_dev, device) || !dev_ptr_ok(pairs_dev + 2 * plan.sum_p - 1, device) ||
-                               !dev_vector_ok(pair_var_dev, plan.sum_p, device)))
-            return IROTAVG_ERR_BAD_ARG;
+            if (!aligned8(p)) return IROTAVG_ERR_BAD_ARG;
+        if (!aligned8(var_dev) || (plan.sum_p > 0 && (!aligned8(pairs_dev) || !aligned8(pair_var_dev)))) return IROTAVG_ERR_BAD_ARG;
         const WinCovArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
                              weights_dev, var_dev, plan.sum_p > 0 ? pairs_dev : nullptr, plan.sum_p > 0 ? pair_var_dev : nullptr,
                              edge_var_dev, leverage_dev, chi2_dev};
+        int device = 0;
+        if (const int rc = win_arrays_check(A, plan.sum_m, plan.sum_n, device); rc != IROTAVG_OK) return rc;
+        for (double *p : per_edge)
+            if (p && !dev_vector_ok(p, plan.sum_m, device)) return IROTAVG_ERR_BAD_ARG;
+        if (var_dev && !dev_vector_ok(var_dev, plan.sum_n, device)) return IROTAVG_ERR_BAD_ARG;
+        if (plan.sum_p > 0 && (!dev_index_ok(pairs_dev, plan.sum_p, device) || !dev_vector_ok(pair_var_dev, plan.sum_p, device)))
+            return IROTAVG_ERR_BAD_ARG;
         return wincov_batch_dev(plan, device, A, sigma, scale, results, static_cast<hipStream_t>(stream));
     });
 }
@@ -463,32 +474,22 @@ int irotavg_window_gate_batch_dev(int64_t nb, const int32_t *sizes, const int32_
         if (!wincov_plan(nb, sizes, nullptr, ncand, plan)) return IROTAVG_ERR_BAD_ARG;
         const int64_t sum_c = plan.sum_c;
         if (!wingate_asked(sum_c, cand_I_dev && cand_QQ_dev, angle_dev, pair_var_dev, chi2_dev, scale)) return IROTAVG_ERR_BAD_ARG;
-        if (!win_arrays_host_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n))
-            return IROTAVG_ERR_BAD_ARG;
         double *const per_cand[3] = {angle_dev, pair_var_dev, chi2_dev};
         if (sum_c > 0) {
             for (double *p : per_cand)
-                if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return IROTAVG_ERR_BAD_ARG;
-            if ((reinterpret_cast<uintptr_t>(cand_I_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(cand_QQ_dev) & 7) != 0 ||
-                !strides_ok(sum_c, 4, cq_rs, cq_cs))
-                return IROTAVG_ERR_BAD_ARG;
-        }
-        if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
-        int device = 0;
-        IRH_CHECK(hipGetDevice(&device));
-        if (!win_arrays_dev_ok(I_dev, QQ_dev, qq_rs, qq_cs, Q_dev, q_rs, q_cs, weights_dev, plan.sum_m, plan.sum_n, device))
-            return IROTAVG_ERR_BAD_ARG;
-        if (sum_c > 0) {
-            if (!dev_ptr_ok(cand_I_dev, device) || !dev_ptr_ok(cand_I_dev + 2 * sum_c - 1, device) ||
-                !dev_matrix_ok(cand_QQ_dev, sum_c, 4, cq_rs, cq_cs, device))
-                return IROTAVG_ERR_BAD_ARG;
-            for (double *p : per_cand)
-                if (p && !dev_vector_ok(p, sum_c, device)) return IROTAVG_ERR_BAD_ARG;
+                if (!aligned8(p)) return IROTAVG_ERR_BAD_ARG;
+            if (!aligned8(cand_I_dev) || !aligned8(cand_QQ_dev) || !strides_ok(sum_c, 4, cq_rs, cq_cs)) return IROTAVG_ERR_BAD_ARG;
         }
         WinCovArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs, weights_dev,
                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        int device = 0;
+        if (const int rc = win_arrays_check(A, plan.sum_m, plan.sum_n, device); rc != IROTAVG_OK) return rc;
         A.gate = true;
         if (sum_c > 0) {  // (without candidates the kernel is handed no candidate array at all)
+            if (!dev_index_ok(cand_I_dev, sum_c, device) || !dev_matrix_ok(cand_QQ_dev, sum_c, 4, cq_rs, cq_cs, device))
+                return IROTAVG_ERR_BAD_ARG;
+            for (double *p : per_cand)
+                if (p && !dev_vector_ok(p, sum_c, device)) return IROTAVG_ERR_BAD_ARG;
             A.cand = cand_I_dev;
             A.cand_QQ = cand_QQ_dev;
             A.cq_rs = (long long)cq_rs;
@@ -521,20 +522,17 @@ int irotavg_cycle_check_dev(int64_t m, int64_t n_total, const int32_t *I_dev, co
                             int64_t qq_cs, double threshold, int32_t *tri_count_dev, int32_t *tri_ok_dev,
                             double *tri_min_dev, int64_t summary[4], void *stream) {
     if (!I_dev || !QQ_dev || !cycle_sizes_ok(m, n_total, threshold) || !strides_ok(m, 4, qq_rs, qq_cs)) return IROTAVG_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(I_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(QQ_dev) & 7) != 0 ||
-        (reinterpret_cast<uintptr_t>(tri_min_dev) & 7) != 0 || (reinterpret_cast<uintptr_t>(tri_count_dev) & 3) != 0 ||
+    if (!aligned8(I_dev) || !aligned8(QQ_dev) || !aligned8(tri_min_dev) || (reinterpret_cast<uintptr_t>(tri_count_dev) & 3) != 0 ||
         (reinterpret_cast<uintptr_t>(tri_ok_dev) & 3) != 0)
         return IROTAVG_ERR_BAD_ARG;
     if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
     return guarded([&]() -> int {
         int device = 0;
         IRH_CHECK(hipGetDevice(&device));
-        if (!dev_ptr_ok(I_dev, device) || !dev_ptr_ok(I_dev + 2 * m - 1, device) ||
-            !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device))
-            return IROTAVG_ERR_BAD_ARG;
+        if (!dev_index_ok(I_dev, m, device) || !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device)) return IROTAVG_ERR_BAD_ARG;
         int32_t *const counts[2] = {tri_count_dev, tri_ok_dev};
         for (int32_t *p : counts)
-            if (p && (!dev_ptr_ok(p, device) || !dev_ptr_ok(p + m - 1, device))) return IROTAVG_ERR_BAD_ARG;
+            if (p && !dev_span_ok(p, p + m - 1, device)) return IROTAVG_ERR_BAD_ARG;
         if (tri_min_dev && !dev_vector_ok(tri_min_dev, m, device)) return IROTAVG_ERR_BAD_ARG;
         const CycleArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, tri_count_dev, tri_ok_dev, tri_min_dev};
         return cycle_check_dev(m, n_total, A, threshold, summary, static_cast<hipStream_t>(stream));

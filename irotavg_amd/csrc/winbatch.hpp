@@ -88,6 +88,24 @@ inline void matrix_span(int64_t rows, int cols, int64_t rs, int64_t cs, int64_t 
     hi = (r > 0 ? r : 0) + (c > 0 ? c : 0);
 }
 
+// Are the bytes [first, end) covered by allocations without a gap? range(at, base, size) names the allocation around
+// the address `at` (false: the asked party knows none). 1: yes, the allocation around `first` reaches `end`, or
+// allocations that follow it without a gap do (a reservation mapped piece by piece; at most 64 of them); 0: no, a gap or
+// nothing known before `end`, or end <= first; -1: not even the allocation around `first` could be named.
+template <class Range>
+inline int span_covered(uintptr_t first, uintptr_t end, Range &&range) {
+    if (end <= first) return 0;
+    uintptr_t at = first;
+    for (int hops = 0; hops < 64; hops++) {
+        uintptr_t base = 0;
+        size_t size = 0;
+        if (!range(at, base, size) || base > at || size <= at - base) return hops == 0 ? -1 : 0;
+        if (end - base <= size) return 1;
+        at = base + size;
+    }
+    return 0;
+}
+
 // one problem of a batch as its workgroup reads it: sizes, first row of its edges / views in the packed arrays, and its
 // place in the caller's order (the row of `results`)
 struct WinDesc {
@@ -131,6 +149,15 @@ inline bool winbatch_plan(int64_t nb, const int32_t *sizes, int kernel, WinBatch
     out.sum_m = eoff;
     out.sum_n = voff;
     return true;
+}
+
+// The pinned block of a batched call on device arrays (batchdev.hpp): nb result records of `rec` bytes, then nb
+// descriptors of `desc` bytes at oD. A block that has to grow is allocated with half as much again.
+struct BatchBlock {
+    size_t oD, bytes, headroom;
+};
+constexpr BatchBlock batch_block(size_t rec, size_t desc, size_t nb) {
+    return BatchBlock{rec * nb, (rec + desc) * nb, (rec + desc) * nb / 2};
 }
 
 // ---- the uncertainty of such problems: k_window_cov / k_window_cov_user (wincov.hip), irotavg_window_uncertainty[_batch_dev]

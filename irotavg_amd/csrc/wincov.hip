@@ -24,8 +24,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 
+#include "batchdev.hpp"  // the host's side of the two batched calls: block, sequence number, lock, wait
 #include "graph.hpp"
 #include "kernels.hpp"
 #include "winbatch.hpp"  // the limits, wincov_lds, WinCovResult, the plan of a batch, rows16
@@ -529,33 +529,17 @@ int wincov_query(WinCov &wc, WinCovQuery &q) {
 }
 
 // ---- irotavg_window_uncertainty_batch_dev: many problems on the caller's device arrays ------------------------------
-// As window.hip's WinBatchDev: one object per process, the pinned, device-visible block [nb result records | nb
-// descriptors], the sequence number of the last call, and a mutex that serialises the calls.
-struct WinCovBatchDev {
-    std::mutex mu;
-    MappedBlock blk;  // portable: the callers' current devices may differ
-    int seq = 0;
-    int attr_device[2] = {-1, -1};  // k_window_cov_user / k_window_gate_user may use the LDS of a problem at the limits there
-};
-static WinCovBatchDev &wincov_batch_state() {
-    static WinCovBatchDev *w = new WinCovBatchDev();  // (never destroyed: no HIP call at process exit)
-    return *w;
-}
+// The block of records and descriptors, the sequence number and the lock: batchdev.hpp (one instance for both calls).
+// k_window_cov_user / k_window_gate_user may use the LDS of a problem at the limits on this device (under the driver's lock)
+static int wincov_attr_device[2] = {-1, -1};
 
 // the arguments have been checked (devapi.hip) and `plan` made from the caller's sizes and pair counts (winbatch.hpp)
 int wincov_batch_dev(const WinCovPlan &plan, int device, const WinCovArrays &A, double sigma, double *scale, int32_t *results,
                      hipStream_t stream) {
-    WinCovBatchDev &wb = wincov_batch_state();
-    std::lock_guard<std::mutex> lock(wb.mu);
+    auto &drv = BatchDev<WinCovResult, WinCovDesc>::get();
     const size_t nb = plan.desc.size();
-    const size_t oD = sizeof(WinCovResult) * nb, total = oD + sizeof(WinCovDesc) * nb;
-    static_assert(sizeof(WinCovResult) % 8 == 0, "the descriptors behind the records hold 8-byte offsets");
-    wb.blk.reserve(total, total / 2, hipHostMallocPortable);
-    wb.blk.map();  // on every call: the current device can differ from the last call's
-    WinCovResult *R = reinterpret_cast<WinCovResult *>(wb.blk.host);
-    std::memcpy(wb.blk.host + oD, plan.desc.data(), sizeof(WinCovDesc) * nb);
-    for (size_t b = 0; b < nb; b++) R[b].seq = 0;
-    const WinCovParams P{0, 0, 0, 0, 0, next_seq(wb.seq), 1, A.weights ? 1 : 0, sigma};
+    const auto s = drv.stage(plan.desc.data(), nb);
+    const WinCovParams P{0, 0, 0, 0, 0, s.seq, 1, A.weights ? 1 : 0, sigma};
     const WinCovUser U{reinterpret_cast<const int2 *>(A.I), A.QQ, A.qq_rs, A.qq_cs, A.Q, A.q_rs, A.q_cs, A.weights, A.var,
                        reinterpret_cast<const int2 *>(A.pairs), A.pair_var, A.edge_var, A.leverage, A.chi2,
                        rows16(reinterpret_cast<uintptr_t>(A.QQ), A.qq_rs, A.qq_cs),
@@ -563,24 +547,18 @@ int wincov_batch_dev(const WinCovPlan &plan, int device, const WinCovArrays &A, 
                        reinterpret_cast<const int2 *>(A.cand), A.cand_QQ, A.cq_rs, A.cq_cs, A.angle, A.cand_var, A.cand_chi2,
                        A.cand_QQ ? rows16(reinterpret_cast<uintptr_t>(A.cand_QQ), A.cq_rs, A.cq_cs) : 0};
     const auto kernel = A.gate ? k_window_gate_user : k_window_cov_user;
-    if (wb.attr_device[A.gate] != device) {
+    if (wincov_attr_device[A.gate] != device) {
         const size_t most = wincov_lds(WC_MAX_NV, WC_MAX_NE, WC_MAX_NU, true, A.gate ? WINCOV_CAND_CHUNK : 0).bytes;
         IRH_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-        wb.attr_device[A.gate] = device;
+        wincov_attr_device[A.gate] = device;
     }
     // the LDS of the largest problem of THIS batch: small problems share a compute unit
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(WC_THREADS), plan.lds, stream, P,
-                       reinterpret_cast<const WinCovDesc *>(wb.blk.hdev + oD), U, reinterpret_cast<WinCovResult *>(wb.blk.hdev));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(WC_THREADS), plan.lds, stream, P, s.D, U, s.Rd);
     IRH_CHECK(hipGetLastError());
-    // 5 ms: long batches, inputs still in flight on the caller's stream, a kernel that died
-    if (!wait_seq(&R[0].seq, sizeof(WinCovResult), nb, P.seq, 5e-3)) IRH_CHECK(hipStreamSynchronize(stream));
-    int rc = IROTAVG_OK;
-    for (size_t b = 0; b < nb; b++) {  // (record b is problem b: the plan keeps the caller's order)
-        if (R[b].status != IROTAVG_OK && rc == IROTAVG_OK) rc = R[b].status;
-        if (results) results[b] = R[b].status;
-        if (scale && R[b].status == IROTAVG_OK) scale[b] = R[b].s2;
-    }
-    return rc;
+    return drv.finish(s, stream, nb, [&](size_t b, const WinCovResult &r) {  // (record b is problem b: the plan keeps the caller's order)
+        if (results) results[b] = r.status;
+        if (scale && r.status == IROTAVG_OK) scale[b] = r.s2;
+    });
 }
 
 }  // namespace irh

@@ -9,8 +9,7 @@
 // multi-kernel path runs (kernels.hpp: edge_log, robust_weight, step_quat; common.hpp: edge_flags);
 // the primal-dual LP follows the same reference statements as l1pd.hip; the linear solves are exact
 // (dense Gauss-Jordan in LDS, dead pivots -> 0 like the oracle).
-#include <mutex>
-
+#include "batchdev.hpp"  // the host's side of irotavg_window_solve_batch_dev: block, sequence number, lock, wait
 #include "graph.hpp"
 #include "kernels.hpp"
 #include "winbatch.hpp"  // the size limits (WIN_MAX_*, SM_MAX_*), win_lds_bytes, WinParams / WinResult, the staging layout, the plan of a batch
@@ -1282,61 +1281,38 @@ int window_solve_batch(WindowSolver &ws, int nb, WinBatchItem *items, int l1_max
 }
 
 // ---- irotavg_window_solve_batch_dev: many problems on the caller's device arrays ------------------------------------
-// One object per process: the pinned, device-visible block [nb result records | nb descriptors] that the kernels read
-// their problem from and leave their result in, and the sequence number of the last call. A mutex serialises the calls.
-struct WinBatchDev {
-    std::mutex mu;
-    MappedBlock blk;  // portable: the callers' current devices may differ
-    int seq = 0;
-    int attr_device = -1;  // k_window_solve_user may use 160 KB of dynamic LDS on this device
-};
-static WinBatchDev &win_batch_dev() {
-    static WinBatchDev *w = new WinBatchDev();  // (never destroyed: no HIP call at process exit)
-    return *w;
-}
+// The block of records and descriptors, the sequence number and the lock: batchdev.hpp (the family's own instance).
+static int win_attr_device = -1;  // k_window_solve_user may use 160 KB of dynamic LDS on this device (under the driver's lock)
 
 // the arguments have been checked (devapi.hip) and `plan` made from the caller's sizes (winbatch.hpp)
 int window_solve_batch_dev(const WinBatchPlan &plan, int device, const WinBatchArrays &A, int cost, double sigma,
                            int l1_max, int irls_max, double change_th, int32_t *results, hipStream_t stream) {
-    WinBatchDev &wb = win_batch_dev();
-    std::lock_guard<std::mutex> lock(wb.mu);
+    auto &drv = BatchDev<WinResult, WinDesc>::get();
     const size_t nb = plan.desc.size(), nw = (size_t)plan.nwave, ng = nb - nw;
-    const size_t oD = sizeof(WinResult) * nb, total = oD + sizeof(WinDesc) * nb;
-    wb.blk.reserve(total, total / 2, hipHostMallocPortable);
-    wb.blk.map();  // on every call: the current device can differ from the last call's
-    WinResult *R = reinterpret_cast<WinResult *>(wb.blk.host);
-    std::memcpy(wb.blk.host + oD, plan.desc.data(), sizeof(WinDesc) * nb);
-    for (size_t b = 0; b < nb; b++) R[b].seq = 0;
-    const WinParams P{0, 0, 0, l1_max, irls_max, cost, change_th, sigma, next_seq(wb.seq)};
+    const auto s = drv.stage(plan.desc.data(), nb);
+    const WinParams P{0, 0, 0, l1_max, irls_max, cost, change_th, sigma, s.seq};
     const WinUser U{reinterpret_cast<const int2 *>(A.I), A.QQ, A.qq_rs, A.qq_cs, A.Q, A.q_rs, A.q_cs, A.weights,
                     rows16(reinterpret_cast<uintptr_t>(A.QQ), A.qq_rs, A.qq_cs),
                     rows16(reinterpret_cast<uintptr_t>(A.Q), A.q_rs, A.q_cs)};
-    const WinDesc *D = reinterpret_cast<const WinDesc *>(wb.blk.hdev + oD);
-    WinResult *Rd = reinterpret_cast<WinResult *>(wb.blk.hdev);
     if (nw) {
-        hipLaunchKernelGGL(k_window_wave_user, dim3((unsigned)nw), dim3(SM_THREADS), 0, stream, P, D, U, Rd);
+        hipLaunchKernelGGL(k_window_wave_user, dim3((unsigned)nw), dim3(SM_THREADS), 0, stream, P, s.D, U, s.Rd);
         IRH_CHECK(hipGetLastError());
     }
     if (ng) {
-        if (wb.attr_device != device) {
+        if (win_attr_device != device) {
             IRH_CHECK(hipFuncSetAttribute((const void *)k_window_solve_user, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)WIN_MAX_LDS));
-            wb.attr_device = device;
+            win_attr_device = device;
         }
-        hipLaunchKernelGGL(k_window_solve_user, dim3((unsigned)ng), dim3(WIN_THREADS), plan.lds, stream, P, D + nw, U, Rd);
+        hipLaunchKernelGGL(k_window_solve_user, dim3((unsigned)ng), dim3(WIN_THREADS), plan.lds, stream, P, s.D + nw, U, s.Rd);
         IRH_CHECK(hipGetLastError());
     }
-    // 5 ms: long batches, inputs still in flight on the caller's stream, a kernel that died
-    if (!wait_seq(&R[0].seq, sizeof(WinResult), nb, P.seq, 5e-3)) IRH_CHECK(hipStreamSynchronize(stream));
-    int rc = IROTAVG_OK;
-    for (size_t b = 0; b < nb; b++) {
-        const WinResult &r = take_result(R + b, rc);
-        if (results) {
-            results[4 * b] = r.status;
-            results[4 * b + 1] = r.l1_iters;
-            results[4 * b + 2] = r.irls_iters;
-        }
-    }
+    const int rc = drv.finish(s, stream, nb, [&](size_t b, const WinResult &r) {
+        if (!results) return;
+        results[4 * b] = r.status;
+        results[4 * b + 1] = r.l1_iters;
+        results[4 * b + 2] = r.irls_iters;
+    });
     if (results)
         for (size_t i = 0; i < nb; i++) results[4 * (size_t)plan.desc[i].idx + 3] = i < nw ? 2 : 1;
     return rc;

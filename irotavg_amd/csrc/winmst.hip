@@ -19,8 +19,8 @@
 // Fixed rows are never written; free rows are never read (each is written in LDS before it is used).
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 
+#include "batchdev.hpp"  // the host's side of the call: block, sequence number, lock, wait
 #include "graph.hpp"
 #include "winbatch.hpp"  // WinDesc, the plan of a batch, rows16
 #include "winio.hpp"     // ld_row / st_row
@@ -195,51 +195,26 @@ __global__ __launch_bounds__(WM_THREADS) void k_window_mst_user(int seq, const W
 
 }  // namespace
 
-// As window.hip's WinBatchDev: one object per process, the pinned, device-visible block [nb result records | nb
-// descriptors], the sequence number of the last call, and a mutex that serialises the calls.
-struct WinMstBatchDev {
-    std::mutex mu;
-    MappedBlock blk;  // portable: the callers' current devices may differ
-    int seq = 0;
-};
-static WinMstBatchDev &winmst_batch_state() {
-    static WinMstBatchDev *w = new WinMstBatchDev();  // (never destroyed: no HIP call at process exit)
-    return *w;
-}
-
-// the arguments have been checked (devapi.hip) and `plan` made from the caller's sizes (winbatch.hpp: kernel 1, so one
+// The block of records and descriptors, the sequence number and the lock: batchdev.hpp (the family's own instance).
+// The arguments have been checked (devapi.hip) and `plan` made from the caller's sizes (winbatch.hpp: kernel 1, so one
 // list in the caller's order)
 int window_init_mst_batch_dev(const WinBatchPlan &plan, int device, const WinBatchArrays &A, int32_t *results, hipStream_t stream) {
     (void)device;
-    WinMstBatchDev &wb = winmst_batch_state();
-    std::lock_guard<std::mutex> lock(wb.mu);
+    auto &drv = BatchDev<WinMstResult, WinDesc>::get();
     const size_t nb = plan.desc.size();
-    const size_t oD = sizeof(WinMstResult) * nb, total = oD + sizeof(WinDesc) * nb;
-    static_assert(sizeof(WinMstResult) % 8 == 0, "the descriptors behind the records hold 8-byte offsets");
     static_assert(winmst_lds_bytes(WIN_MAX_NV, WIN_MAX_NE) <= 20 * 1024, "many problems share a compute unit");
     static_assert(WIN_MAX_NE <= MST_STRIDE && (uint64_t)WIN_MAX_NV * MST_STRIDE < (1ull << 31), "labels: one stride per sweep, 32 bits");
     size_t lds = 0;  // the largest problem of THIS batch
     for (const WinDesc &d : plan.desc) lds = std::max(lds, winmst_lds_bytes(d.nv, d.ne));
-    wb.blk.reserve(total, total / 2, hipHostMallocPortable);
-    wb.blk.map();  // on every call: the current device can differ from the last call's
-    WinMstResult *R = reinterpret_cast<WinMstResult *>(wb.blk.host);
-    std::memcpy(wb.blk.host + oD, plan.desc.data(), sizeof(WinDesc) * nb);
-    for (size_t b = 0; b < nb; b++) R[b].seq = 0;
-    const int seq = next_seq(wb.seq);
+    const auto s = drv.stage(plan.desc.data(), nb);
     const WinMstUser U{reinterpret_cast<const int2 *>(A.I), A.QQ, A.qq_rs, A.qq_cs, A.Q, A.q_rs, A.q_cs,
                        rows16(reinterpret_cast<uintptr_t>(A.QQ), A.qq_rs, A.qq_cs),
                        rows16(reinterpret_cast<uintptr_t>(A.Q), A.q_rs, A.q_cs)};
-    hipLaunchKernelGGL(k_window_mst_user, dim3((unsigned)nb), dim3(WM_THREADS), lds, stream, seq,
-                       reinterpret_cast<const WinDesc *>(wb.blk.hdev + oD), U, reinterpret_cast<WinMstResult *>(wb.blk.hdev));
+    hipLaunchKernelGGL(k_window_mst_user, dim3((unsigned)nb), dim3(WM_THREADS), lds, stream, s.seq, s.D, U, s.Rd);
     IRH_CHECK(hipGetLastError());
-    // 5 ms: long batches, inputs still in flight on the caller's stream, a kernel that died
-    if (!wait_seq(&R[0].seq, sizeof(WinMstResult), nb, seq, 5e-3)) IRH_CHECK(hipStreamSynchronize(stream));
-    int rc = IROTAVG_OK;
-    for (size_t b = 0; b < nb; b++) {  // (record b is problem b: the plan keeps the caller's order)
-        if (R[b].status != IROTAVG_OK && rc == IROTAVG_OK) rc = R[b].status;
-        if (results) results[b] = R[b].status;
-    }
-    return rc;
+    return drv.finish(s, stream, nb, [&](size_t b, const WinMstResult &r) {  // (record b is problem b: the plan keeps the caller's order)
+        if (results) results[b] = r.status;
+    });
 }
 
 }  // namespace irh

@@ -36,6 +36,31 @@ def _check(t, name, dtypes, shape, device=None, placed=True):
     return t
 
 
+def _vector(t, name, n, device, dtype=torch.float64):
+    """_check of n entries on `device`, and contiguous."""
+    _check(t, name, (dtype,), (n,), device)
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    return t
+
+
+def _output(want, name, n, device, dtype=torch.float64, fill=None):
+    """An output argument: True -> a new tensor of n entries (preset to `fill`, or uninitialised), False / None -> None,
+    a tensor -> itself once _vector accepts it."""
+    if want is True:
+        return torch.empty(n, dtype=dtype, device=device) if fill is None else torch.full((n,), fill, dtype=dtype, device=device)
+    if want is False or want is None:
+        return None
+    return _vector(want, name, n, device, dtype)
+
+
+def _allowed(rc, name, allow_rc):
+    """rc, or IrotavgError for anything but OK that allow_rc does not list."""
+    if rc != capi.OK and rc not in allow_rc:
+        raise capi.IrotavgError(rc, name)
+    return rc
+
+
 def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -125,30 +150,18 @@ class TorchGraph(capi.Graph):
         if not var.is_contiguous():
             raise ValueError("out must be contiguous")
         scale = C.c_double(float("nan"))
-        rc = self._call("irotavg_graph_rotation_variance_dev", _ptr(var), C.byref(scale))
-        if rc != capi.OK and rc not in allow_rc:
-            raise capi.IrotavgError(rc, "irotavg_graph_rotation_variance_dev")
+        rc = _allowed(self._call("irotavg_graph_rotation_variance_dev", _ptr(var), C.byref(scale)),
+                      "irotavg_graph_rotation_variance_dev", allow_rc)
         return dict(rc=rc, var=var, scale=scale.value)
 
     def edge_diagnostics(self, edge_var=True, leverage=True, chi2=True, allow_rc=()):
         """irotavg_graph_edge_diagnostics_dev: dict(rc, edge_var, leverage, chi2 (m each on the device, or None), scale).
         Each argument is True (a new tensor), False (not computed) or a contiguous float64 tensor of m entries to fill."""
-        outs = []
-        for name, want in (("edge_var", edge_var), ("leverage", leverage), ("chi2", chi2)):
-            if want is True:
-                outs.append(self._new(self.m))
-            elif want is False or want is None:
-                outs.append(None)
-            else:
-                _check(want, name, (torch.float64,), (self.m,), self.device)
-                if not want.is_contiguous():
-                    raise ValueError("%s must be contiguous" % name)
-                outs.append(want)
+        outs = [_output(want, name, self.m, self.device)
+                for name, want in (("edge_var", edge_var), ("leverage", leverage), ("chi2", chi2))]
         scale = C.c_double(float("nan"))
-        rc = self._call("irotavg_graph_edge_diagnostics_dev", *[None if t is None else _ptr(t) for t in outs],
-                        C.byref(scale))
-        if rc != capi.OK and rc not in allow_rc:
-            raise capi.IrotavgError(rc, "irotavg_graph_edge_diagnostics_dev")
+        rc = _allowed(self._call("irotavg_graph_edge_diagnostics_dev", *[None if t is None else _ptr(t) for t in outs],
+                                 C.byref(scale)), "irotavg_graph_edge_diagnostics_dev", allow_rc)
         return dict(rc=rc, edge_var=outs[0], leverage=outs[1], chi2=outs[2], scale=scale.value)
 
     def cycle_check(self, edge_index, QQ, threshold=5 * 3.141592653589793 / 180, **kw):
@@ -185,6 +198,34 @@ def batch_offsets(sizes):
     return np.ascontiguousarray(s, dtype=np.int32), eoff, voff, int(s64[:, 2].sum()), int(s64[:, 0].sum())
 
 
+_IDS, _F64 = (torch.int32, torch.int64), (torch.float64,)
+
+
+def _batch_tensors(sizes, edge_index, QQ, Q):
+    """batch_offsets(sizes) and the first round of the checks every batched call makes of its packed tensors: dtype and
+    shape, of all of them before the placement of any. Returns (sizes as int32, sum m, sum n_total, the (tensor, name,
+    dtypes, shape) of the three): the call checks its further tensors with _shapes, appends them, then calls _placed."""
+    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
+    specs = [(edge_index, "edge_index", _IDS, (sum_m, 2)), (QQ, "QQ", _F64, (sum_m, 4)), (Q, "Q", _F64, (sum_n, 4))]
+    _shapes(specs)
+    return s32, sum_m, sum_n, specs
+
+
+def _shapes(specs):
+    for spec in specs:
+        _check(*spec, placed=False)
+    return specs
+
+
+def _placed(specs):
+    """the second round: the first tensor on the ROCm device, the others on the same one -> that device"""
+    _check(*specs[0])
+    device = specs[0][0].device
+    for spec in specs[1:]:
+        _check(*spec, device)
+    return device
+
+
 def window_solve_batch(sizes, edge_index, QQ, Q, cost=4, sigma=5 * 3.141592653589793 / 180, l1_iters=100, irls_iters=100,
                        change_th=1e-3, kernel=0, weights=True, allow_rc=()):
     """nb independent window-size problems (<= 64 free views, <= 320 views, <= 640 edges each), every one l1ra + irls as
@@ -197,21 +238,9 @@ def window_solve_batch(sizes, edge_index, QQ, Q, cost=4, sigma=5 * 3.14159265358
     are host numpy arrays of nb entries. rc is the first non-zero status in problem order; anything but OK raises unless
     listed in allow_rc."""
     import numpy as np
-    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
-    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2), placed=False)
-    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), placed=False)
-    _check(Q, "Q", (torch.float64,), (sum_n, 4), placed=False)
-    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2))
-    device = edge_index.device
-    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), device)
-    _check(Q, "Q", (torch.float64,), (sum_n, 4), device)
-    w = None
-    if weights is True:
-        w = torch.empty(sum_m, dtype=torch.float64, device=device)
-    elif weights is not False and weights is not None:
-        w = _check(weights, "weights", (torch.float64,), (sum_m,), device)
-        if not w.is_contiguous():
-            raise ValueError("weights must be contiguous")
+    s32, sum_m, sum_n, specs = _batch_tensors(sizes, edge_index, QQ, Q)
+    device = _placed(specs)
+    w = _output(weights, "weights", sum_m, device)
     nb = len(s32)
     res = np.zeros((nb, 4), dtype=np.int32)
     with torch.cuda.device(device):
@@ -220,8 +249,7 @@ def window_solve_batch(sizes, edge_index, QQ, Q, cost=4, sigma=5 * 3.14159265358
             nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(Q),
             *matrix_strides(Q), int(cost), float(sigma), int(l1_iters), int(irls_iters), float(change_th),
             None if w is None else _ptr(w), res.ctypes.data_as(C.POINTER(C.c_int32)), int(kernel), _stream(device))
-    if rc != capi.OK and rc not in allow_rc:
-        raise capi.IrotavgError(rc, "irotavg_window_solve_batch_dev")
+    _allowed(rc, "irotavg_window_solve_batch_dev", allow_rc)
     return dict(rc=rc, Q=Q, weights=w, status=res[:, 0].copy(), l1_iters=res[:, 1].copy(), irls_iters=res[:, 2].copy(),
                 kernel=res[:, 3].copy())
 
@@ -262,39 +290,20 @@ def window_uncertainty_batch(sizes, edge_index, QQ, Q, weights=None, sigma=5 * 3
     arrays of nb entries (scale NaN where the problem failed). rc is the first non-zero status in problem order; anything
     but OK raises unless listed in allow_rc. A problem that fails leaves its rows of every output as they were."""
     import numpy as np
-    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
+    s32, sum_m, sum_n, specs = _batch_tensors(sizes, edge_index, QQ, Q)
     nb = len(s32)
-    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2), placed=False)
-    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), placed=False)
-    _check(Q, "Q", (torch.float64,), (sum_n, 4), placed=False)
     if (pairs is None) != (npairs is None):
         raise ValueError("pairs and npairs go together")
     np32, _, sum_p = pair_offsets(npairs, nb)
     if pairs is not None:
-        _check(pairs, "pairs", (torch.int32, torch.int64), (sum_p, 2), placed=False)
-    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2))
-    device = edge_index.device
-    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), device)
-    _check(Q, "Q", (torch.float64,), (sum_n, 4), device)
-    if pairs is not None:
-        _check(pairs, "pairs", (torch.int32, torch.int64), (sum_p, 2), device)
-
-    def vector(t, name, n):
-        _check(t, name, (torch.float64,), (n,), device)
-        if not t.is_contiguous():
-            raise ValueError("%s must be contiguous" % name)
-        return t
-    w = None if weights is None else vector(weights, "weights", sum_m)
-    outs = {}
-    for name, want, n in (("var", var, sum_n), ("edge_var", edge_var, sum_m), ("leverage", leverage, sum_m),
-                          ("chi2", chi2, sum_m)):
-        if want is True:
-            outs[name] = torch.full((n,), float("nan"), dtype=torch.float64, device=device)
-        elif want is False or want is None:
-            outs[name] = None
-        else:
-            outs[name] = vector(want, name, n)
-    pv = torch.full((sum_p,), float("nan"), dtype=torch.float64, device=device) if sum_p else None
+        specs += _shapes([(pairs, "pairs", _IDS, (sum_p, 2))])
+    device = _placed(specs)
+    w = None if weights is None else _vector(weights, "weights", sum_m, device)
+    nan = float("nan")
+    outs = {name: _output(want, name, n, device, fill=nan)
+            for name, want, n in (("var", var, sum_n), ("edge_var", edge_var, sum_m), ("leverage", leverage, sum_m),
+                                  ("chi2", chi2, sum_m))}
+    pv = torch.full((sum_p,), nan, dtype=torch.float64, device=device) if sum_p else None
     scale = np.full(nb, np.nan)
     status = np.zeros(nb, dtype=np.int32)
     opt = lambda t: None if t is None else _ptr(t)
@@ -307,8 +316,7 @@ def window_uncertainty_batch(sizes, edge_index, QQ, Q, weights=None, sigma=5 * 3
             None if np32 is None else np32.ctypes.data_as(C.POINTER(C.c_int32)), opt(pr), opt(pv), opt(outs["edge_var"]),
             opt(outs["leverage"]), opt(outs["chi2"]), scale.ctypes.data_as(C.POINTER(C.c_double)),
             status.ctypes.data_as(C.POINTER(C.c_int32)), _stream(device))
-    if rc != capi.OK and rc not in allow_rc:
-        raise capi.IrotavgError(rc, "irotavg_window_uncertainty_batch_dev")
+    _allowed(rc, "irotavg_window_uncertainty_batch_dev", allow_rc)
     return dict(rc=rc, pair_var=pv, scale=scale, status=status, **outs)
 
 
@@ -326,37 +334,16 @@ def window_gate_batch(sizes, edge_index, QQ, Q, cand_index, cand_QQ, ncand, weig
     first non-zero status in problem order; anything but OK raises unless listed in allow_rc. A problem that fails leaves
     its rows of every output as they were."""
     import numpy as np
-    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
+    s32, sum_m, sum_n, specs = _batch_tensors(sizes, edge_index, QQ, Q)
     nb = len(s32)
-    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2), placed=False)
-    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), placed=False)
-    _check(Q, "Q", (torch.float64,), (sum_n, 4), placed=False)
     if ncand is None:
         raise ValueError("ncand is needed: one count per problem")
     nc32, _, sum_c = pair_offsets(ncand, nb, "ncand")
-    _check(cand_index, "cand_index", (torch.int32, torch.int64), (sum_c, 2), placed=False)
-    _check(cand_QQ, "cand_QQ", (torch.float64,), (sum_c, 4), placed=False)
-    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2))
-    device = edge_index.device
-    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), device)
-    _check(Q, "Q", (torch.float64,), (sum_n, 4), device)
-    _check(cand_index, "cand_index", (torch.int32, torch.int64), (sum_c, 2), device)
-    _check(cand_QQ, "cand_QQ", (torch.float64,), (sum_c, 4), device)
-
-    def vector(t, name, n):
-        _check(t, name, (torch.float64,), (n,), device)
-        if not t.is_contiguous():
-            raise ValueError("%s must be contiguous" % name)
-        return t
-    w = None if weights is None else vector(weights, "weights", sum_m)
-    outs = {}
-    for name, want in (("angle", angle), ("pair_var", pair_var), ("chi2", chi2)):
-        if want is True:
-            outs[name] = torch.full((sum_c,), float("nan"), dtype=torch.float64, device=device)
-        elif want is False or want is None:
-            outs[name] = None
-        else:
-            outs[name] = vector(want, name, sum_c)
+    specs += _shapes([(cand_index, "cand_index", _IDS, (sum_c, 2)), (cand_QQ, "cand_QQ", _F64, (sum_c, 4))])
+    device = _placed(specs)
+    w = None if weights is None else _vector(weights, "weights", sum_m, device)
+    outs = {name: _output(want, name, sum_c, device, fill=float("nan"))
+            for name, want in (("angle", angle), ("pair_var", pair_var), ("chi2", chi2))}
     scale = np.full(nb, np.nan)
     status = np.zeros(nb, dtype=np.int32)
     opt = lambda t: None if t is None or t.numel() == 0 else _ptr(t)
@@ -368,8 +355,7 @@ def window_gate_batch(sizes, edge_index, QQ, Q, cand_index, cand_QQ, ncand, weig
             *matrix_strides(Q), None if w is None else _ptr(w), float(sigma), nc32.ctypes.data_as(C.POINTER(C.c_int32)),
             opt(ci), opt(cand_QQ), *matrix_strides(cand_QQ), opt(outs["angle"]), opt(outs["pair_var"]), opt(outs["chi2"]),
             scale.ctypes.data_as(C.POINTER(C.c_double)), status.ctypes.data_as(C.POINTER(C.c_int32)), _stream(device))
-    if rc != capi.OK and rc not in allow_rc:
-        raise capi.IrotavgError(rc, "irotavg_window_gate_batch_dev")
+    _allowed(rc, "irotavg_window_gate_batch_dev", allow_rc)
     return dict(rc=rc, scale=scale, status=status, **outs)
 
 
@@ -386,14 +372,8 @@ def window_init_mst_batch(sizes, edge_index, QQ, Q, allow_rc=()):
     that fails keeps its rows of Q as they were. On success the rows are bitwise those of capi.init_mst on each problem
     alone."""
     import numpy as np
-    s32, _, _, sum_m, sum_n = batch_offsets(sizes)
-    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2), placed=False)
-    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), placed=False)
-    _check(Q, "Q", (torch.float64,), (sum_n, 4), placed=False)
-    _check(edge_index, "edge_index", (torch.int32, torch.int64), (sum_m, 2))
-    device = edge_index.device
-    _check(QQ, "QQ", (torch.float64,), (sum_m, 4), device)
-    _check(Q, "Q", (torch.float64,), (sum_n, 4), device)
+    s32, _, _, specs = _batch_tensors(sizes, edge_index, QQ, Q)
+    device = _placed(specs)
     nb = len(s32)
     status = np.zeros(nb, dtype=np.int32)
     with torch.cuda.device(device):
@@ -401,8 +381,7 @@ def window_init_mst_batch(sizes, edge_index, QQ, Q, allow_rc=()):
         rc = capi.lib().irotavg_window_init_mst_batch_dev(
             nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(Q),
             *matrix_strides(Q), status.ctypes.data_as(C.POINTER(C.c_int32)), _stream(device))
-    if rc != capi.OK and rc not in allow_rc:
-        raise capi.IrotavgError(rc, "irotavg_window_init_mst_batch_dev")
+    _allowed(rc, "irotavg_window_init_mst_batch_dev", allow_rc)
     return dict(rc=rc, Q=Q, status=status)
 
 
@@ -436,24 +415,13 @@ def cycle_check(edge_index, QQ, n_total, threshold=5 * 3.141592653589793 / 180, 
     _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
     device = edge_index.device
     _check(QQ, "QQ", (torch.float64,), (m, 4), device)
-    outs = []
-    for name, want, dt in wants:
-        if want is True:
-            outs.append(torch.empty(m, dtype=dt, device=device))
-        elif want is False or want is None:
-            outs.append(None)
-        else:
-            _check(want, name, (dt,), (m,), device)
-            if not want.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-            outs.append(want)
+    outs = [_output(want, name, m, device, dt) for name, want, dt in wants]
     s = (C.c_int64 * 4)(-1, -1, -1, -1)
     with torch.cuda.device(device):
         ei = _narrow(edge_index)
         rc = capi.lib().irotavg_cycle_check_dev(m, n_total, _ptr(ei), _ptr(QQ), *matrix_strides(QQ), threshold,
                                                 *[None if t is None else _ptr(t) for t in outs], s if summary else None,
                                                 _stream(device))
-    if rc != capi.OK and rc not in allow_rc:
-        raise capi.IrotavgError(rc, "irotavg_cycle_check_dev")
+    _allowed(rc, "irotavg_cycle_check_dev", allow_rc)
     return dict(rc=rc, tri_count=outs[0], tri_ok=outs[1], tri_min=outs[2],
                 summary=dict(zip(capi.SUMMARY_FIELDS, (int(v) for v in s))) if summary and rc == capi.OK else None)

@@ -279,6 +279,67 @@ int main() {
         EXPECT(!wingate_asked(-1, true, true, true, true, true) && !wingate_asked(lmin, true, true, true, true, true));
         EXPECT(wingate_asked(lmax, true, true, false, false, false));
     }
+    // ---- the pinned block of a batched call (batchdev.hpp): records, then descriptors on 8 bytes; what reserve is asked for
+    {
+        const size_t recs[3] = {sizeof(WinResult), sizeof(WinCovResult), 8}, descs[2] = {sizeof(WinDesc), sizeof(WinCovDesc)};
+        for (size_t rec : recs)
+            for (size_t desc : descs)
+                for (size_t nb : {(size_t)1, (size_t)3, (size_t)70, (size_t)WIN_BATCH_MAX}) {
+                    const BatchBlock L = batch_block(rec, desc, nb);
+                    EXPECT(L.oD == rec * nb && L.oD % 8 == 0 && L.bytes == L.oD + desc * nb && L.headroom == L.bytes / 2);
+                    // the next size the block serves without growing again
+                    EXPECT(batch_block(rec, desc, nb + nb / 2).bytes <= L.bytes + L.headroom);
+                }
+    }
+    // ---- the coverage rule of the `_dev` argument checks (span_covered): a made-up address space of three allocations,
+    // B directly behind A, then a gap, then C
+    {
+        struct Alloc {
+            uintptr_t base;
+            size_t size;
+        };
+        const Alloc A{0x10000, 0x1000}, B{0x11000, 0x800}, C{0x20000, 0x4000}, top{~(uintptr_t)0xfff, 0x1000};
+        int asked = 0;
+        auto range = [&](uintptr_t at, uintptr_t &base, size_t &size) {
+            asked++;
+            for (const Alloc &a : {A, B, C, top})
+                if (at >= a.base && at - a.base < a.size) {
+                    base = a.base;
+                    size = a.size;
+                    return true;
+                }
+            return false;
+        };
+        EXPECT(span_covered(0x10000, 0x11000, range) == 1 && asked == 1);  // all of A: one question
+        EXPECT(span_covered(0x10ff8, 0x11000, range) == 1 && span_covered(0x10010, 0x10018, range) == 1);
+        EXPECT(span_covered(0x10000, 0x11001, range) == 1);   // one byte into B, which follows A without a gap
+        EXPECT(span_covered(0x10800, 0x11800, range) == 1);   // up to the end of B
+        EXPECT(span_covered(0x10800, 0x11801, range) == 0);   // one byte past it: the gap
+        EXPECT(span_covered(0x10000, 0x20008, range) == 0);   // claimed to end inside C: both ends are somebody's, the gap is not
+        EXPECT(span_covered(0x11000, 0x24000, range) == 0 && span_covered(0x20000, 0x24000, range) == 1);
+        EXPECT(span_covered(0x20000, 0x24001, range) == 0);
+        EXPECT(span_covered(0x18000, 0x18008, range) == -1 && span_covered(0x8, 0x10, range) == -1);  // the first byte is nobody's
+        EXPECT(span_covered(0x10010, 0x10010, range) == 0 && span_covered(0x10010, 0x10008, range) == 0);  // empty, wrapped
+        EXPECT(span_covered(0x10010, 0x8, range) == 0);
+        EXPECT(span_covered(~(uintptr_t)0xfff, ~(uintptr_t)0, range) == 1);  // at the top of the address space: no overflow
+        auto liar = [](uintptr_t at, uintptr_t &base, size_t &size) {  // an allocation that does not contain the address asked about
+            base = at + 8;
+            size = 64;
+            return true;
+        };
+        auto empty = [](uintptr_t at, uintptr_t &base, size_t &size) {
+            base = at;
+            size = 0;
+            return true;
+        };
+        EXPECT(span_covered(0x1000, 0x1010, liar) == -1 && span_covered(0x1000, 0x1010, empty) == -1);
+        auto crumbs = [](uintptr_t at, uintptr_t &base, size_t &size) {  // 8-byte pieces without end: the walk is bounded
+            base = at;
+            size = 8;
+            return true;
+        };
+        EXPECT(span_covered(0x1000, 0x1000 + 8 * 64, crumbs) == 1 && span_covered(0x1000, 0x1000 + 8 * 64 + 1, crumbs) == 0);
+    }
     if (failures) {
         std::fprintf(stderr, "%d expectation(s) failed\n", failures);
         return 1;
