@@ -290,6 +290,16 @@ int irotavg_graph_direct_residual(irotavg_graph *g, double *relres);
 int irotavg_bcr_rhs_products(int B, const double *Dinv, const double *P, const double *Q, const double *R, int hasP,
                              int hasQ, double *WR, double *Ra, double *Rc);
 
+/* Diagnostic: the wide matrix-core products of ONE block elimination of the direct solver, run by one workgroup of wpe
+ * waves (the column tiles of W are dealt to them) through the device functions every reduction kernel uses (BcrElim in
+ * irotavg_amd/csrc/bcr.hip), on host arrays, all row-major: Dinv (symmetric), P, Q, Dc, Da, fill are B x B, R is B x 3,
+ * W is B x (2 B + 3). B = 24 with wpe = 1 / 2 / 4 or B = 8 with wpe = 1 / 2 -- the block sizes whose eight-row tile runs
+ * as 4 x 4 x 4 products (any other: IROTAVG_ERR_BAD_ARG). On return W = Dinv [P' | Q | R] (the columns of P' are zero if
+ * hasP = 0, those of Q if hasQ = 0); Dc = Dc - Q' W_Q unless hasQ = 0; Da = Da - P W_P and fill = -P W_Q unless
+ * hasP = 0 -- then Da stays as it was and fill = P. */
+int irotavg_bcr_block_products(int B, int wpe, const double *Dinv, const double *P, const double *Q, const double *R,
+                               int hasP, int hasQ, double *Dc, double *Da, double *W, double *fill);
+
 /* Uncertainty of the IRLS solution (docs/rotation_variance.md). M = A' diag(d^2) A with A = irotavg_make_A's
  * incidence (m x nu, nu = n_total - f) and d = the handle's current weights (irotavg_graph_get_weights), Sigma = M^-1:
  *   var[v]      = Sigma_{v-f, v-f} for a free view v, 0 for a fixed one (n_total entries; NULL: not asked for);

@@ -37,7 +37,7 @@ SYMBOLS = [
     "irotavg_dist_irls", "irotavg_dist_get_stats", "irotavg_dist_info", "irotavg_dist_plan", "irotavg_dist_plan_host",
     "irotavg_dist_l1ra", "irotavg_dist_create_hosted",
     "irotavg_graph_direct_info",
-    "irotavg_graph_direct_residual", "irotavg_bcr_rhs_products",
+    "irotavg_graph_direct_residual", "irotavg_bcr_rhs_products", "irotavg_bcr_block_products",
     "irotavg_window_solve", "irotavg_window_solve_kernel", "irotavg_trim_memory", "irotavg_rmat2quat", "irotavg_quat2rmat", "irotavg_viewgraph_save_poses",
     "irotavg_oneshot_cache", "irotavg_oneshot_cache_clear", "irotavg_oneshot_cache_stats",
     "irotavg_dist_timing",
@@ -154,6 +154,7 @@ def lib():
     L.irotavg_graph_direct_info.argtypes = [vp, _i64p, C.c_int]
     L.irotavg_graph_direct_residual.argtypes = [vp, _dp]
     L.irotavg_bcr_rhs_products.argtypes = [C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]
+    L.irotavg_bcr_block_products.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.irotavg_graph_rotation_variance.argtypes = [vp, _dp, C.c_int64, _ip, _dp, _dp]
     L.irotavg_rotation_variance.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp,
                                             _dp, C.c_int64, _ip, _dp, _dp]
@@ -556,6 +557,24 @@ def bcr_rhs_products(Dinv, P, Q, R, hasP=True, hasQ=True, Ra=None, Rc=None):
     check(lib().irotavg_bcr_rhs_products(B, _d(Dinv), _d(P), _d(Q), _d(R), 1 if hasP else 0, 1 if hasQ else 0, _d(WR),
                                          _d(Ra), _d(Rc)), "irotavg_bcr_rhs_products")
     return dict(WR=WR, Ra=Ra, Rc=Rc)
+
+
+def bcr_block_products(Dinv, P, Q, R, wpe=1, hasP=True, hasQ=True, Dc=None, Da=None):
+    """irotavg_bcr_block_products (a diagnostic): the wide products of one block elimination of the direct solver by a
+    workgroup of wpe waves -- dict(W = Dinv [P' | Q | R], Dc = Dc - Q' W_Q, Da = Da - P W_P, fill = -P W_Q); Dc / Da start
+    from zeros unless given; hasQ false leaves Dc, hasP false leaves Da and returns fill = P. Dinv (symmetric), P, Q:
+    B x B, R: B x 3, B = 24 (wpe 1 / 2 / 4) or 8 (wpe 1 / 2)."""
+    Dinv, P, Q, R = (np.ascontiguousarray(a, dtype=np.float64) for a in (Dinv, P, Q, R))
+    B = Dinv.shape[0]
+    if Dinv.shape != (B, B) or P.shape != (B, B) or Q.shape != (B, B) or R.shape != (B, 3):
+        raise ValueError("shapes")
+    W = np.full((B, 2 * B + 3), np.nan)
+    fill = np.full((B, B), np.nan)
+    Dc = np.zeros((B, B)) if Dc is None else np.array(Dc, dtype=np.float64, order="C").reshape(B, B)
+    Da = np.zeros((B, B)) if Da is None else np.array(Da, dtype=np.float64, order="C").reshape(B, B)
+    check(lib().irotavg_bcr_block_products(B, int(wpe), _d(Dinv), _d(P), _d(Q), _d(R), 1 if hasP else 0, 1 if hasQ else 0,
+                                           _d(Dc), _d(Da), _d(W), _d(fill)), "irotavg_bcr_block_products")
+    return dict(W=W, Dc=Dc, Da=Da, fill=fill)
 
 
 def oneshot_cache(enable):

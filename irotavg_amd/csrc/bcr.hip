@@ -20,7 +20,8 @@
 // LDS -- with vector FMAs every value of P, Q and D^-1 would have to reach all 64 lanes, and eight waves
 // per CU saturate the LDS port with that); the accumulator layout of one product IS the B-operand layout
 // of the next (row = 4 reg + lane / 16), so W never leaves the registers between the two (the right-hand sides, three
-// columns of a sixteen-column tile, run on v_mfma_f64_4x4x4_4b_f64 instead: BcrRs). D_i^-1 is
+// columns of a sixteen-column tile, run on v_mfma_f64_4x4x4_4b_f64 instead: BcrRs; so do the last eight rows of a block of
+// 24 or 8, half a sixteen-row tile, into the very accumulator registers of that tile: BcrAop). D_i^-1 is
 // formed by a symmetric sweep (Gauss-Jordan without pivoting: SPD), a column per lane, the pivot row
 // broadcast through LDS (bcr_invert). A pivot not above kDeadTol x its original diagonal entry is dead
 // (an isolated view, a floating component): its unknown solves to 0, as everywhere else in this library.
@@ -329,29 +330,67 @@ struct BcrDim {
     static constexpr int NT0 = B / 16;          // first column tile that holds a column of W_Q
 };
 
-// A-operand of the 16x16x4 product for row tile mt, k-step s: element (16 mt + lane % 16, 4 s + lane / 16) of the
-// row-major B x B matrix M, or of its transpose; rows beyond B read as zero.
-template <int B, bool TRANS>
-__device__ __forceinline__ void bcr_load_a(const double *M, int lane, double (&aop)[BcrDim<B>::MT][BcrDim<B>::KS]) {
-    const int li = lane & 15, lk = lane >> 4;
+// The A-operands of a wide product (sixteen columns per instruction), all row tiles and k-steps of the row-major B x B
+// matrix M or of its transpose: a[mt][s] = element (16 mt + lane % 16, 4 s + lane / 16), the 16x16x4 operand. With
+// B % 16 == 8 (B = 24, 8) the last row tile holds eight rows and eight rows of zeros: 64 pipe clocks for half a tile.
+// That tile runs as TWO v_mfma_f64_4x4x4_4b_f64 per column tile and k-step instead (2 x ~18 clocks), one per group g of
+// four rows, whose four blocks share the same A and are the four column groups of the 16-column tile (the layout: BcrRs
+// below, tools/micro/mfma_f64_4x4x4_layout.hip prints this use as well):
+//   A  M[16 (MT - 1) + 4 g + lane % 4][4 s + lane / 16] in every block -- the operand loaded here (a4);
+//   B  B[k][4 block + j] in lane 16 k + 4 block + j: lane for lane the 16x16x4 B-operand, unchanged;
+//   D  D[i][4 block + j] in lane 16 i + 4 block + j: register g of the 16x16x4 accumulator tile of that row tile (rows
+//      16 (MT - 1) + 4 g + lane / 16). Registers 2 and 3 of the tile stay zero; they hold rows >= B, which nobody reads.
+// So stores, puts and the use of an accumulator tile as the next product's B-operand are those of the 16x16x4 tile, and
+// the sums are the same four-term k groups in the same order: bit for bit what the padded tile gave.
+template <int B>
+struct BcrAop {
+    typedef BcrDim<B> Dm;
+    static constexpr bool SMALL = B % 16 == 8;
+    static constexpr int MW = SMALL ? Dm::MT - 1 : Dm::MT;  // row tiles on the 16x16x4 product
+    double a[MW > 0 ? MW : 1][Dm::KS];
+    double a4[2][Dm::KS];
+    template <bool TRANS>
+    __device__ __forceinline__ void load(const double *M, int lane) {
+        const int li = lane & 15, lk = lane >> 4;
 #pragma unroll
-    for (int mt = 0; mt < BcrDim<B>::MT; mt++) {
-        const int i = 16 * mt + li;
-        const int ic = i < B ? i : B - 1;
+        for (int mt = 0; mt < MW; mt++) {
+            // (rows beyond B read as zero)
+            const int i = 16 * mt + li;
+            const int ic = i < B ? i : B - 1;
 #pragma unroll
-        for (int s = 0; s < BcrDim<B>::KS; s++) {
-            const int k = 4 * s + lk;
-            const double v = TRANS ? M[k * B + ic] : M[ic * B + k];
-            aop[mt][s] = i < B ? v : 0.0;
+            for (int s = 0; s < Dm::KS; s++) {
+                const int k = 4 * s + lk;
+                const double v = TRANS ? M[k * B + ic] : M[ic * B + k];
+                a[mt][s] = i < B ? v : 0.0;
+            }
+        }
+        if constexpr (SMALL) {
+#pragma unroll
+            for (int g = 0; g < 2; g++) {
+                const int i = 16 * MW + 4 * g + (lane & 3);
+#pragma unroll
+                for (int s = 0; s < Dm::KS; s++) {
+                    const int k = 4 * s + lk;
+                    a4[g][s] = TRANS ? M[k * B + i] : M[i * B + k];
+                }
+            }
         }
     }
-}
+    // acc (the accumulator tile of row tile mt) += A(mt, k-step s) x bop
+    __device__ __forceinline__ void mul(int mt, int s, double bop, v4d &acc) const {
+        if (SMALL && mt == MW) {
+            acc[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a4[0][s], bop, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a4[1][s], bop, acc[1], 0, 0, 0);
+        } else {
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mt][s], bop, acc, 0, 0, 0);
+        }
+    }
+};
 
 // out[mt][nt] += A (registers) x W (accumulator tiles of a previous product used as B-operands: register r of
 // tile (mt, nt) holds the rows 16 mt + 4 r + lane / 16, i.e. k-step 4 mt + r)
 template <int B, int NTA>
-__device__ __forceinline__ void bcr_mul_w(const double (&aop)[BcrDim<B>::MT][BcrDim<B>::KS],
-                                          const v4d (&w)[BcrDim<B>::MT][BcrDim<B>::NT],
+__device__ __forceinline__ void bcr_mul_w(const BcrAop<B> &aop, const v4d (&w)[BcrDim<B>::MT][BcrDim<B>::NT],
                                           v4d (&out)[BcrDim<B>::MT][BcrDim<B>::NT]) {
     typedef BcrDim<B> Dm;
 #pragma unroll
@@ -360,8 +399,7 @@ __device__ __forceinline__ void bcr_mul_w(const double (&aop)[BcrDim<B>::MT][Bcr
         for (int s = 0; s < Dm::KS; s++) {
             const double bop = w[s >> 2][nt][s & 3];
 #pragma unroll
-            for (int mt = 0; mt < Dm::MT; mt++)
-                out[mt][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[mt][s], bop, out[mt][nt], 0, 0, 0);
+            for (int mt = 0; mt < Dm::MT; mt++) aop.mul(mt, s, bop, out[mt][nt]);
         }
 }
 
@@ -483,6 +521,7 @@ __device__ __noinline__ v2d bcr_rs_pw_call(const double *P, const double *Wr, in
 template <int B, int NR, int NTPW, bool RSCALL = false>
 struct BcrElim {
     typedef BcrDim<B, NR> Dm;
+    typedef BcrAop<B> Aop;
     v4d w[Dm::MT][NTPW];
     // the last column tile holds W_R alone: its owner runs it as small products (BcrRs), in every phase. With WPE waves
     // per elimination that is the wave of part (NT - 1) % WPE, in its slot (NT - 1) / WPE -- the same in all four functions
@@ -523,10 +562,10 @@ struct BcrElim {
             // has no registers to spare)
             __builtin_amdgcn_sched_barrier(0);
         }
-        double aop[Dm::MT][Dm::KS];
+        Aop aop;
         // (the inverse is symmetric: read by columns -- consecutive lanes, consecutive words -- instead of by rows, whose
         // stride of 2 B words puts sixteen lanes on four banks)
-        bcr_load_a<B, true>(Di, lane, aop);
+        aop.template load<true>(Di, lane);
         const int lj = lane & 15, lk = lane >> 4;
         const double *base[NS];
         int stride[NS];
@@ -566,8 +605,7 @@ struct BcrElim {
             for (int sl = 0; sl < NS; sl++) {
                 if (IRH_RS_SKIP(sl)) continue;
 #pragma unroll
-                for (int mt = 0; mt < Dm::MT; mt++)
-                    w[mt][sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[mt][s], bop[sl], w[mt][sl], 0, 0, 0);
+                for (int mt = 0; mt < Dm::MT; mt++) aop.mul(mt, s, bop[sl], w[mt][sl]);
             }
         }
         if (Wg) {
@@ -585,7 +623,7 @@ struct BcrElim {
             }
         }
         if (!hasQ) return;
-        bcr_load_a<B, true>(Q, lane, aop);
+        aop.template load<true>(Q, lane);
         v4d out[Dm::MT][NS];
 #pragma unroll
         for (int sl = 0; sl < NS; sl++)
@@ -598,8 +636,7 @@ struct BcrElim {
                 const int nt = part + sl * WPE;
                 if (nt >= Dm::NT || nt < Dm::NT0 || IRH_RS_SKIP(sl)) continue;
 #pragma unroll
-                for (int mt = 0; mt < Dm::MT; mt++)
-                    out[mt][sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[mt][s], w[s >> 2][sl][s & 3], out[mt][sl], 0, 0, 0);
+                for (int mt = 0; mt < Dm::MT; mt++) aop.mul(mt, s, w[s >> 2][sl][s & 3], out[mt][sl]);
             }
 #pragma unroll
         for (int sl = 0; sl < NS; sl++) {
@@ -677,8 +714,8 @@ struct BcrElim {
             if (NS == 1) return;
             __builtin_amdgcn_sched_barrier(0);
         }
-        double aop[Dm::MT][Dm::KS];
-        bcr_load_a<B, false>(P, lane, aop);
+        Aop aop;
+        aop.template load<false>(P, lane);
 #pragma unroll
         for (int sl = 0; sl < NS; sl++) {
             if (IRH_RS_SKIP(sl)) continue;
@@ -691,8 +728,7 @@ struct BcrElim {
             for (int sl = 0; sl < NS; sl++) {
                 if (part + sl * WPE >= Dm::NT || IRH_RS_SKIP(sl)) continue;
 #pragma unroll
-                for (int mt = 0; mt < Dm::MT; mt++)
-                    out[mt][sl] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[mt][s], w[s >> 2][sl][s & 3], out[mt][sl], 0, 0, 0);
+                for (int mt = 0; mt < Dm::MT; mt++) aop.mul(mt, s, w[s >> 2][sl][s & 3], out[mt][sl]);
             }
     }
     // second half: D_a -= P W_P (assigned when `assign`: the chunk's first contribution to the separator before
@@ -3990,6 +4026,87 @@ int bcr_rhs_products(int B, const double *Dinv, const double *P, const double *Q
     IRH_CHECK(hipMemcpyAsync(WR, d.p + 3 * BB + XB, XB * sizeof(double), hipMemcpyDeviceToHost, s));
     IRH_CHECK(hipMemcpyAsync(Ra, d.p + 3 * BB + 2 * XB, XB * sizeof(double), hipMemcpyDeviceToHost, s));
     IRH_CHECK(hipMemcpyAsync(Rc, d.p + 3 * BB + 3 * XB, XB * sizeof(double), hipMemcpyDeviceToHost, s));
+    IRH_CHECK(hipStreamSynchronize(s));
+    return IROTAVG_OK;
+}
+
+// diagnostic (irotavg_bcr_block_products): ONE elimination's wide products by a workgroup of WPE waves, through the
+// member functions of BcrElim the reduction kernels call, operands in LDS as there: W = D^-1 [P' | Q | R] (to memory),
+// D_c -= Q' W_Q, D_a -= P W_P, the fill A[a, c] = -P W_Q over P
+template <int B, int WPE>
+__global__ __launch_bounds__(64 * WPE) void k_bcr_block_products(const double *__restrict__ Dinv, double *__restrict__ P,
+                                                                 const double *__restrict__ Q, const double *__restrict__ R,
+                                                                 int hasP, int hasQ, double *__restrict__ Dc,
+                                                                 double *__restrict__ Da, double *__restrict__ W) {
+    constexpr int NR = 3, BB = B * B, XB = B * NR;
+    typedef BcrDim<B, NR> Dm;
+    static_assert(WPE <= Dm::NT, "a wave per column tile at the most");
+    constexpr int NTPW = (Dm::NT + WPE - 1) / WPE;
+    __shared__ double sD[3][BB], sG[2][BB], sR[3][XB], sZ[2];  // D^-1, D_c, D_a | P, Q | R, R_c, R_a
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int e = tid; e < BB; e += 64 * WPE) {
+        sD[0][e] = Dinv[e];
+        sD[1][e] = Dc[e];
+        sD[2][e] = Da[e];
+        sG[0][e] = P[e];
+        sG[1][e] = Q[e];
+    }
+    for (int e = tid; e < XB; e += 64 * WPE) {
+        sR[0][e] = R[e];
+        sR[1][e] = 0.0;
+        sR[2][e] = 0.0;
+    }
+    if (tid < 2) sZ[tid] = 0.0;
+    __syncthreads();
+    BcrElim<B, NR, NTPW> E;
+    v4d out[Dm::MT][NTPW];
+    E.template phase1<WPE>(wave, sD[0], sG[0], hasP != 0, sG[1], sR[0], sD[1], sR[1], W, sZ, lane, hasQ != 0);
+    __syncthreads();
+    if (hasP) E.template phase2_mul<WPE>(wave, sG[0], sR[0], out, lane);
+    __syncthreads();
+    if (hasP) E.template phase2_put<WPE>(wave, out, sG[0], sD[2], false, sR[2], lane);
+    __syncthreads();
+    for (int e = tid; e < BB; e += 64 * WPE) {
+        Dc[e] = sD[1][e];
+        Da[e] = sD[2][e];
+        P[e] = sG[0][e];
+    }
+}
+template <int B, int WPE>
+static void bcr_block_products_run(double *d, int hasP, int hasQ, hipStream_t s) {
+    constexpr int BB = B * B;
+    static_assert(BcrAop<B>::SMALL, "block size");
+    k_bcr_block_products<B, WPE><<<1, 64 * WPE, 0, s>>>(d, d + BB, d + 2 * BB, d + 5 * BB, hasP, hasQ, d + 3 * BB, d + 4 * BB,
+                                                       d + 5 * BB + 3 * B);
+    IRH_CHECK(hipGetLastError());
+}
+int bcr_block_products(int B, int wpe, const double *Dinv, const double *P, const double *Q, const double *R, int hasP,
+                       int hasQ, double *Dc, double *Da, double *W, double *fill) {
+    // (the block sizes whose last row tile runs as small products; two column tiles at B = 8)
+    if (!((B == 24 && (wpe == 1 || wpe == 2 || wpe == 4)) || (B == 8 && (wpe == 1 || wpe == 2)))) return IROTAVG_ERR_BAD_ARG;
+    hipStream_t s = nullptr;
+    const size_t BB = (size_t)B * B, XB = (size_t)B * 3, WB = (size_t)B * (2 * B + 3);
+    DevBuf<double> d;  // D^-1 | P | Q | D_c | D_a | R | W
+    d.alloc(5 * BB + XB + WB);
+    IRH_CHECK(hipMemcpyAsync(d.p, Dinv, BB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + BB, P, BB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + 2 * BB, Q, BB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + 3 * BB, Dc, BB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + 4 * BB, Da, BB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemcpyAsync(d.p + 5 * BB, R, XB * sizeof(double), hipMemcpyHostToDevice, s));
+    IRH_CHECK(hipMemsetAsync(d.p + 5 * BB + XB, 0xff, WB * sizeof(double), s));  // (NaN: every entry of W is written)
+    if (B == 24) {
+        if (wpe == 1) bcr_block_products_run<24, 1>(d.p, hasP, hasQ, s);
+        else if (wpe == 2) bcr_block_products_run<24, 2>(d.p, hasP, hasQ, s);
+        else bcr_block_products_run<24, 4>(d.p, hasP, hasQ, s);
+    } else {
+        if (wpe == 1) bcr_block_products_run<8, 1>(d.p, hasP, hasQ, s);
+        else bcr_block_products_run<8, 2>(d.p, hasP, hasQ, s);
+    }
+    IRH_CHECK(hipMemcpyAsync(fill, d.p + BB, BB * sizeof(double), hipMemcpyDeviceToHost, s));
+    IRH_CHECK(hipMemcpyAsync(Dc, d.p + 3 * BB, BB * sizeof(double), hipMemcpyDeviceToHost, s));
+    IRH_CHECK(hipMemcpyAsync(Da, d.p + 4 * BB, BB * sizeof(double), hipMemcpyDeviceToHost, s));
+    IRH_CHECK(hipMemcpyAsync(W, d.p + 5 * BB + XB, WB * sizeof(double), hipMemcpyDeviceToHost, s));
     IRH_CHECK(hipStreamSynchronize(s));
     return IROTAVG_OK;
 }

@@ -435,6 +435,14 @@ int irotavg_bcr_rhs_products(int B, const double *Dinv, const double *P, const d
     API_CATCH
 }
 
+int irotavg_bcr_block_products(int B, int wpe, const double *Dinv, const double *P, const double *Q, const double *R,
+                               int hasP, int hasQ, double *Dc, double *Da, double *W, double *fill) {
+    if (!Dinv || !P || !Q || !R || !Dc || !Da || !W || !fill) return IROTAVG_ERR_BAD_ARG;
+    API_TRY
+    return bcr_block_products(B, wpe, Dinv, P, Q, R, hasP, hasQ, Dc, Da, W, fill);
+    API_CATCH
+}
+
 int irotavg_graph_direct_residual(irotavg_graph *h, double *relres) {
     if (!h || !relres) return IROTAVG_ERR_BAD_ARG;
     API_TRY

@@ -415,6 +415,9 @@ int bcr_stamps_up(Graph &g, double *out);                      // development ai
 // diagnostic (irotavg_bcr_rhs_products): one wave through the right-hand-side products of an elimination, host arrays
 int bcr_rhs_products(int B, const double *Dinv, const double *P, const double *Q, const double *R, int hasP, int hasQ,
                      double *WR, double *Ra, double *Rc);
+// diagnostic (irotavg_bcr_block_products): the wide products of one elimination by a workgroup of wpe waves, host arrays
+int bcr_block_products(int B, int wpe, const double *Dinv, const double *P, const double *Q, const double *R, int hasP,
+                       int hasQ, double *Dc, double *Da, double *W, double *fill);
 // the last direct solve went through the single-launch upper reduction and a workgroup of it gave up waiting (its solution
 // is all NaN): clears the word, switches the handle to level-by-level launches and says so (one small synchronous read)
 bool bcr_up_failed(Graph &g);

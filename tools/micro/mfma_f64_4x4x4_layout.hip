@@ -2,7 +2,10 @@
 // per lane for A, B and the accumulator) keeps its operands on gfx950. One wave per pair (la, lb): A is 1 in lane la alone,
 // B is 1 in lane lb alone, and the wave reports which lanes of D are not zero. Printed: for every block, the 16 x 16 table
 // "D lane of (A lane, B lane)" (-1: the two do not meet), then the same with the A-broadcast cbsz = 2, abid = 1 (block 1's
-// A lanes feed all four blocks).
+// A lanes feed all four blocks). Last, the SHARED-A, 16-column use of the direct solver's eight-row tile (bcr.hip, BcrAop): the
+// same 4 x 4 matrix A in all four blocks, a = A[lane % 4][lane / 16], against a 4 x 16 matrix X held as the 16x16x4
+// B-operand, b = X[lane / 16][lane % 16]; the product A X is expected in lane 16 i + c for entry (i, c) -- register g of a
+// 16x16x4 accumulator tile when A is row group g of a row tile. Integer entries: the comparison is for equality.
 //   hipcc --offload-arch=gfx950 -O3 tools/micro/mfma_f64_4x4x4_layout.hip -o build/micro/mfma_f64_4x4x4_layout
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -13,6 +16,10 @@ __global__ __launch_bounds__(64) void k(unsigned long long *mask) {
     const double d = __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, 0.0, CBSZ, ABID, 0);
     const unsigned long long m = __ballot(d != 0.0);
     if (lane == 0) mask[blockIdx.x] = m;
+}
+__global__ __launch_bounds__(64) void k_shared_a(const double *A, const double *X, double *D) {
+    const int lane = threadIdx.x;
+    D[lane] = __builtin_amdgcn_mfma_f64_4x4x4f64(A[(lane & 3) * 4 + (lane >> 4)], X[(lane >> 4) * 16 + (lane & 15)], 0.0, 0, 0, 0);
 }
 static void show(const char *what, const unsigned long long *h) {
     printf("== %s\n", what);
@@ -59,5 +66,27 @@ int main() {
         if ((la >> 4) != 1)
             for (int lb = 0; lb < 64; lb++) other += h[la * 64 + lb] != 0;
     printf("A lanes outside block 1 that reach D: %d\n", other);
+    double hA[16], hX[64], hD[64], *dA, *dX, *dD;
+    for (int e = 0; e < 16; e++) hA[e] = 1 + e;            // A[i][k] = 1 + 4 i + k
+    for (int e = 0; e < 64; e++) hX[e] = 100 + 7 * e;      // X[k][c] = 100 + 7 (16 k + c)
+    if (hipMalloc(&dA, sizeof(hA)) != hipSuccess || hipMalloc(&dX, sizeof(hX)) != hipSuccess ||
+        hipMalloc(&dD, sizeof(hD)) != hipSuccess)
+        return 1;
+    if (hipMemcpy(dA, hA, sizeof(hA), hipMemcpyHostToDevice) != hipSuccess) return 1;
+    if (hipMemcpy(dX, hX, sizeof(hX), hipMemcpyHostToDevice) != hipSuccess) return 1;
+    k_shared_a<<<1, 64>>>(dA, dX, dD);
+    if (hipMemcpy(hD, dD, sizeof(hD), hipMemcpyDeviceToHost) != hipSuccess) return 1;
+    printf("== shared A, sixteen columns: lane 16 i + c (row i of the table, column c) against (A X)[i][c]\n");
+    int wrong = 0;
+    for (int i = 0; i < 4; i++) {
+        for (int c = 0; c < 16; c++) {
+            double want = 0.0;
+            for (int kk = 0; kk < 4; kk++) want += hA[i * 4 + kk] * hX[kk * 16 + c];
+            wrong += hD[16 * i + c] != want;
+            printf(" %6.0f%c", hD[16 * i + c], hD[16 * i + c] == want ? ' ' : '!');
+        }
+        printf("\n");
+    }
+    printf("entries that differ from A X: %d\n", wrong);
     return 0;
 }
