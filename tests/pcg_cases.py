@@ -175,6 +175,21 @@ def operator(case, dtype):
 
 
 # ---- the reference --------------------------------------------------------------------------------------------------
+def spd_inverse(sub, dtype):
+    """The explicit inverse of a live last level (also of stale_cases.py): numpy.linalg.inv in float64, a long-double
+    Cholesky + refinement in long double."""
+    if dtype is not LD:
+        return np.linalg.inv(sub)
+    if len(sub) <= 200:
+        return chol_solve_ld(sub, np.eye(len(sub)))
+    # (only the family that leaves mg_dense_max to the build has a last level this large, where the Cholesky's Python
+    # loops take ten seconds) one Newton step on LAPACK's inverse: the residual I - C X is squared
+    inv = np.asarray(np.linalg.inv(np.asarray(sub, dtype=np.float64)), dtype=LD)
+    R = np.eye(len(sub), dtype=LD) - sub @ inv
+    assert np.abs(R).max() < 1e-9
+    return inv + inv @ R
+
+
 class Reference:
     def __init__(self, case, dtype, levels=None, kc=None, omega=OMEGA, additive=None, mutant=None):
         """levels / kc / additive: what the handle reports (default: what the case's options are expected to give)."""
@@ -221,20 +236,8 @@ class Reference:
         if self.dense:
             C = self.L[-1]
             live = np.nonzero(np.diag(C) > 0)[0]
-            sub = C[np.ix_(live, live)]
-            if dtype is LD and len(live) <= 200:
-                inv = chol_solve_ld(sub, np.eye(len(live)))
-            elif dtype is LD:
-                # (only the family that leaves mg_dense_max to the build has a last level this large, where the Cholesky's
-                # Python loops take ten seconds) one Newton step on LAPACK's inverse: the residual I - C X is squared
-                inv = np.asarray(np.linalg.inv(np.asarray(sub, dtype=np.float64)), dtype=LD)
-                R = np.eye(len(live), dtype=LD) - sub @ inv
-                assert np.abs(R).max() < 1e-9
-                inv = inv + inv @ R
-            else:
-                inv = np.linalg.inv(sub)
             self.S = np.zeros_like(C)
-            self.S[np.ix_(live, live)] = inv
+            self.S[np.ix_(live, live)] = spd_inverse(C[np.ix_(live, live)], dtype)
 
     # -- the cycle
     def restrict(self, l, v):

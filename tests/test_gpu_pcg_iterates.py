@@ -52,9 +52,9 @@ A dead row (isolated view) inside a live aggregate is not left at 0: up_row adds
 z, p and x carry the aggregate's correction there. Nothing reads it back (the row and column of L are zero); the
 reference does the same and the comparison covers it. A dead row that is an aggregate of its own stays exactly 0.
 
-Out of scope: the sharded PCG (dist.hip), inexact_outer, and the stale-inverse policy (dense_scale != 1, the Woodbury
-repair). The stale-inverse scaling is the next candidate for this method: uniformly scaled weights re-use the inverse
-through dense_scale, and the iterates follow from this reference's by that scale exactly.
+Out of scope: the sharded PCG (dist.hip) and inexact_outer. The stale-inverse policy (dense_scale != 1, the Woodbury
+repair, the re-inversion verdicts) has this method applied to it in test_gpu_stale_inverse.py, with the chained
+reference of stale_cases.py.
 
 Measured on one MI355X: ratio by case and k (bar 16; the case names carry the route and nu, pcg_cases._cases).
 
