@@ -4534,7 +4534,22 @@ void bcr_plan_dev(Graph &g, const DevEdgeSrc &src) {
         const int nl = h[0], uncovered = h[1];
         if (nl > kBcrMaxFar) return;  // (cannot happen: nl <= nfar)
         if (nl > 0) {
-            if (uncovered > 0 || g.sw.bcr_no_closures) return;  // see bcr_plan: the band part must be SPD alone
+            if (g.sw.bcr_no_closures) return;
+            if (uncovered > 0) {
+                // see bcr_plan: the band part must be SPD alone, and the coverage rule is sufficient, not necessary. The
+                // exact test runs on the host (rare: one copy of the edge list, in the labels the plan uses)
+                std::vector<int32_t> hI((size_t)2 * g.m);
+                IRH_CHECK(hipMemcpyAsync(hI.data(), src.I, sizeof(int32_t) * hI.size(), hipMemcpyDeviceToHost, s));
+                std::vector<int> hrel;
+                if (src.relabel) {
+                    hrel.resize((size_t)g.n_total);
+                    IRH_CHECK(hipMemcpyAsync(hrel.data(), src.relabel, sizeof(int) * hrel.size(), hipMemcpyDeviceToHost, s));
+                }
+                IRH_CHECK(hipStreamSynchronize(s));
+                if (src.relabel)
+                    for (int32_t &v : hI) v = hrel[(size_t)v];  // (k_plan_stats found every index inside [0, n_total))
+                if (!bcr_band_part_anchored(g.m, f, g.no, B, hI.data())) return;
+            }
             std::vector<int> hl((size_t)3 * kBcrMaxFar);
             IRH_CHECK(hipMemcpyAsync(hl.data(), fl.p, sizeof(int) * hl.size(), hipMemcpyDeviceToHost, s));
             IRH_CHECK(hipStreamSynchronize(s));

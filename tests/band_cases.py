@@ -154,7 +154,7 @@ def make_case(name, route, nu, f, bw, fam, *, scale=1.0, weak=None, isolated=(),
     band = min(bw, nu - 1)                                     # the widest span between two free views
     B = block_size(band)
     levels, top16 = expected_levels(nu, B, no_mixed="IROTAVG_BCR_NO_MIXED" in env, no_top16="IROTAVG_BCR_NO_TOP16" in env)
-    return dict(name=name, route=route, nu=nu, n=n, f=f, bw=band, I=I, QQ=QQ, Q0=Q0, w=w, fam=fam, scale=scale, weak=weak,
+    return dict(name=name, route=route, nu=nu, n=n, f=f, bw=band, I=I, QQ=QQ, Q0=Q0, Qgt=Qgt, w=w, fam=fam, scale=scale, weak=weak,
                 isolated=tuple(isolated), env=env, system=system or name, twin=twin, B=B, levels=levels, top16=top16)
 
 
@@ -309,8 +309,8 @@ def _without_dead(S, b):
 
 
 # ---- long-double (or float64) Cholesky in band storage --------------------------------------------------------------
-def band_chol_solve(S, Bm, refine=1):
-    """L^-1 Bm in S's dtype: right-looking Cholesky on the band storage + `refine` rounds of refinement."""
+def band_chol(S):
+    """The right-looking Cholesky factor of S on its band storage, as a function Rm -> L^-1 Rm (no refinement)."""
     nu, W = S.shape
     bw, dt = W // 2, S.dtype
     U = np.zeros((nu + bw, W), dtype=dt)
@@ -335,7 +335,13 @@ def band_chol_solve(S, Bm, refine=1):
         for j in range(nu - 1, -1, -1):
             Y[j] = (Y[j] - U[j, bw + 1:] @ Y[j + 1:j + 1 + bw]) / U[j, bw]
         return Y[:nu]
-    Bm = np.asarray(Bm, dtype=dt)
+    return solve
+
+
+def band_chol_solve(S, Bm, refine=1):
+    """L^-1 Bm in S's dtype: right-looking Cholesky on the band storage + `refine` rounds of refinement."""
+    solve = band_chol(S)
+    Bm = np.asarray(Bm, dtype=S.dtype)
     X = solve(Bm)
     for _ in range(refine):
         X = X + solve(Bm - band_matvec(S, X))
