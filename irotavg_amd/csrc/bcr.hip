@@ -30,6 +30,7 @@
 #include "graph.hpp"
 #include "kernels.hpp"
 #include "asm0w.hpp"
+#include "bcr_route.hpp"
 
 namespace irh {
 // a direct solve with closures is repeated by conjugate gradients on the full operator when its relative residual is above
@@ -63,7 +64,6 @@ typedef IRH_GPTR(const int) gp_ci;
 typedef IRH_GPTR(int) gp_i;
 typedef IRH_GPTR(unsigned) gp_u;
 typedef IRH_GPTR(const double4) gp_cd4;
-constexpr int kUpLevels = 8;
 struct BcrUpLevel {
     int nb, nred, nch;
     gp_cd inD, inR, inXD, inXR, inXG;  // from the level below
@@ -130,11 +130,10 @@ struct BcrUnit {
 struct BcrState {
     BcrUnit unit;
     int B = 0;
-    int NR = 3;    // right-hand-side columns riding along: 3, or 19 with closures
     int nfar = 0;  // long-range edges (loop closures) handled by the Woodbury correction
     std::vector<BcrLevel> lev;
-    DevBuf<double> xtop;  // B x NR: the last separator
-    DevBuf<int> far_i, far_j, far_e;  // rows and edge id of the closures
+    DevBuf<double> xtop;  // B x 3: the last separator
+    DevBuf<int> far_e;    // edge id of the closures
     // the closures' part of a solve (bcr_closures): per level the inverse of every eliminated block, the step programs
     // of the closures' forward eliminations and what they record, the Woodbury system
     std::vector<DevBuf<double>> Dinv;
@@ -153,13 +152,12 @@ struct BcrState {
     DevBuf<int> cl_dense;        // cl_ndense x nfar: the step of closure q on dense elimination d, or -1
     // a shard of a sharded sequence (dist.hip): the separator before the first chunk is the previous rank's
     int ext0 = 0;
-    int dbg_word = -1;         // development aid: the debug word of the NEXT solves of this handle (bcr_stamps*); -1: IROTAVG_BCR_DBG
     DevBuf<long long> stamps;  // development aid: bcr_stamp
     DevBuf<unsigned> up_cnt;   // k_bcr_reduce_up: arrivals per level boundary (they only grow: solve g waits for g x chunks);
                                // word kUpLevels: a wait gave up (bcr_up_failed)
     unsigned up_gen = 0;
     DevBuf<BcrUpArgs> up_args; // k_bcr_reduce_up's arguments (written once)
-    bool up_used = false;      // the last solve went through k_bcr_reduce_up
+    BcrRoute last;             // the route of the most recent whole solve (a phase-1 + phase-2 pair is one solve)
     bool top16 = false;        // the last level is one workgroup of <= 16 blocks that makes its own way back (bcr_top_body)
     BcrTopSched tsched;
     DevBuf<BcrTopSched> tsched_dev;
@@ -1890,7 +1888,7 @@ __device__ __forceinline__ void bcr_back_rounds(const double *sW, double (*sX)[B
     }
 }
 
-// K6 inside the way back (run_irls on the plain direct path; Graph::bcr_apply): the threads that write a view's solution
+// K6 inside the way back (run_irls on the plain direct path; BcrRequest::apply): the threads that write a view's solution
 // row also make its step (step_apply) and sum ||x||; the workgroup's sum goes to slot `slot` of the partial array (a
 // DOUBLE per workgroup, not a row of four: level 0 at 100k views has 512 workgroups and level 1 another 73, the pinned
 // block 512 rows), summed by the host in slot order like k_apply_step's partials.
@@ -2935,8 +2933,6 @@ static void bcr_closure_plan(Graph &g) {
     S.cl_nsteps = (int)steps.size();
     S.cl_nelim = (int)elim.size();
     S.cl_npad = r <= kSolveLdsMax ? r : (r + 63) / 64 * 64;
-    S.far_i.upload(g.bcr_far_i, g.stream);
-    S.far_j.upload(g.bcr_far_j, g.stream);
     S.far_e.upload(g.bcr_far_e, g.stream);
     S.cl_off.upload(off, g.stream);
     S.cl_step.upload(steps, g.stream);
@@ -2976,8 +2972,8 @@ static void bcr_alloc(Graph &g) {
     BcrState &S = *g.bcr;
     S.B = g.bcr_B;
     S.nfar = (int)g.bcr_far_e.size();
-    S.NR = 3;
-    const int B = S.B, NR = S.NR, NC = 2 * B + NR;
+    constexpr int NR = 3;
+    const int B = S.B, NC = 2 * B + NR;
     const int nb0 = (g.levels[0].n + B - 1) / B;
     int nch0 = (nb0 + 7) / 8;
     // The level-0 reduction keeps two workgroups per CU resident (one for B = 32 or with closure columns: LDS). A
@@ -3053,347 +3049,308 @@ static void bcr_alloc(Graph &g) {
     }
 }
 
-// open_top: the last level writes its separator data like every other level instead of solving it (a shard: the
-// separators of all ranks form the top system, bcr_top_solve); xc_top / xext: its solution and the solution of the
-// previous rank's separator for the way back
-template <int B, int NR>
-static void bcr_run(Graph &g, int only, int pass, bool open_top = false, int phase = 0, const double *xc_top = nullptr,
-                    const double *xext = nullptr) {
+// ---------------------------------------------------------------------------------------------
+// One solve on the host: shape -> route (bcr_route.hpp) -> reductions -> ways back. Every function below makes one kind
+// of launch; which of them run, and as which instantiation, is the route's business alone.
+// ---------------------------------------------------------------------------------------------
+static_assert(kBcrMaxLevels == kMaxLevels && kBcrApplySlotsMax == 4 * kMaxParts, "bcr_route.hpp restates these");
+
+BcrShape bcr_shape(const Graph &g) {
+    BcrShape s;
+    s.B = g.bcr_B;
+    s.nfar = (int)g.bcr_far_e.size();
+    s.shard = g.bcr_shard;
+    s.ng = g.ng;
+    s.guard = g.bcr_guard;
+    s.asm_windowed = g.asm_windowed != 0;
+    s.dbg = g.sw.bcr_dbg;
+    s.no_fused_asm = g.sw.bcr_no_fused_asm;
+    s.no_unit_factor = g.sw.bcr_no_unit_factor;
+    s.no_fused_up = g.bcr_no_fused_up;
+    if (g.bcr) {
+        const BcrState &S = *g.bcr;
+        s.nl = (int)S.lev.size();
+        for (int l = 0; l < s.nl; l++) s.nch[l] = S.lev[l].nch;
+        s.top16 = S.top16;
+        s.unit_valid = S.unit.valid;
+    }
+    return s;
+}
+
+// the unit-weight store, allocated by the handle's first filling solve (lazily: a handle that never makes such a solve -- a
+// solver clone, l1ra alone -- keeps nothing)
+static void bcr_unit_alloc(BcrState &S) {
+    BcrUnit &U = S.unit;
+    const int nl = (int)S.lev.size();
+    const size_t B = (size_t)S.B, NC = 2 * B + 3;
+    U.epoch = g_unit_epoch.load(std::memory_order_acquire);
+    U.lev.resize((size_t)nl - 1);
+    size_t words = 0;
+    for (int l = 0; l + 1 < nl; l++) {
+        const size_t ne = (size_t)S.lev[l].nch * 7;
+        U.lev[(size_t)l].Wu.alloc(ne * B * NC);
+        U.lev[(size_t)l].Di.alloc(ne * B * B);
+        U.lev[(size_t)l].P.alloc(ne * B * B);
+        U.lev[(size_t)l].Q.alloc(ne * B * B);
+        words += ne * B * (NC + 3 * B);
+    }
+    U.top.alloc((size_t)(kTopUnitLast + 1) * B * B);
+    words += (size_t)(kTopUnitLast + 1) * B * B;
+    U.bytes = (int64_t)(words * sizeof(double));
+    // (a partial chunk skips its padding positions: their slots are never written, and never read)
+}
+
+// k_bcr_reduce_up's arguments and its arrival counters: written once per handle
+static void bcr_up_args_write(Graph &g) {
     BcrState &S = *g.bcr;
     Level &L0 = g.levels[0];
     hipStream_t st = g.stream;
     const int nl = (int)S.lev.size();
-    // (the stamp helpers steer ONE handle through BcrState::dbg_word instead of rewriting the process environment under
-    // other handles' and threads' solves -- advisor, round 5; the library itself never writes the environment)
-    const int dbg = S.dbg_word >= 0 ? S.dbg_word : g.sw.bcr_dbg;
+    if (S.up_cnt.n < (size_t)kUpLevels + 1) {
+        S.up_cnt.alloc(kUpLevels + 1);
+        S.up_cnt.zero(st);
+        S.up_gen = 0;
+    }
+    if (S.up_args.p) return;
+    BcrUpArgs A;
+    memset(&A, 0, sizeof(A));
+    A.nl = nl - 1;
+    for (int i = 0; i < A.nl; i++) {
+        BcrLevel &Li = S.lev[1 + i], &Fi = S.lev[i];
+        A.lev[i] = BcrUpLevel{Li.nb,          Li.nred,        Li.nch,         (gp_cd)Fi.sepD.p, (gp_cd)Fi.sepR.p,
+                              (gp_cd)Fi.extD.p, (gp_cd)Fi.extR.p, (gp_cd)Fi.extG.p, (gp_d)Li.W.p,   (gp_d)Li.sepD.p,
+                              (gp_d)Li.sepR.p, (gp_d)Li.extD.p, (gp_d)Li.extR.p, (gp_d)Li.extG.p};
+    }
+    A.n = L0.n;
+    A.sl_off = (gp_ci)L0.sl_off.p;
+    A.col = (gp_ci)L0.col.p;
+    A.val = (gp_cd)L0.val.p;
+    A.diag = (gp_cd)L0.diag.p;
+    A.rhs = (gp_cd4)L0.b.p;
+    A.xtop = (gp_d)S.xtop.p;
+    A.cnt = (gp_u)S.up_cnt.p;
+    A.top16 = S.top16;
+    A.top = S.tsched;
+    A.xtop_all = (gp_d)S.lev[nl - 1].x.p;
+    A.fail = (gp_i) reinterpret_cast<int *>(S.up_cnt.p + kUpLevels);
+    S.up_args.alloc(1);
+    IRH_CHECK(hipMemcpyAsync(S.up_args.p, &A, sizeof(A), hipMemcpyHostToDevice, st));
+    IRH_CHECK(hipStreamSynchronize(st));  // (A is on this stack)
+}
+// ... and the store's copy: the same arguments with W = the store's and the operand arrays
+static void bcr_up_args_write_unit(BcrState &S, hipStream_t st) {
+    BcrUnit &U = S.unit;
+    if (U.up_args.p) return;
+    BcrUpArgs A;
+    IRH_CHECK(hipMemcpyAsync(&A, S.up_args.p, sizeof(A), hipMemcpyDeviceToHost, st));
+    IRH_CHECK(hipStreamSynchronize(st));
+    for (int i = 0; i + 1 < A.nl; i++) {
+        BcrUnitLevel &Ui = U.lev[(size_t)i + 1];
+        A.lev[i].W = (gp_d)Ui.Wu.p;
+        A.lev[i].stD = (gp_d)Ui.Di.p;
+        A.lev[i].stP = (gp_d)Ui.P.p;
+        A.lev[i].stQ = (gp_d)Ui.Q.p;
+    }
+    A.tst = (gp_d)U.top.p;
+    U.up_args.alloc(1);
+    IRH_CHECK(hipMemcpyAsync(U.up_args.p, &A, sizeof(A), hipMemcpyHostToDevice, st));
+    IRH_CHECK(hipStreamSynchronize(st));  // (A is on this stack)
+}
+
+// the upper launch: the reductions of all levels above level 0 (and, on a sixteen-block top, its way back)
+template <int B, int UF>
+static void bcr_launch_up_as(Graph &g, const BcrUpArgs *args, int dbg) {
+    BcrState &S = *g.bcr;
+    const int nl = (int)S.lev.size();
+    const size_t lds = bcr_up_lds<B>(S.top16 ? S.lev[nl - 1].nb : 0);
+    static std::atomic<size_t> lds_set[16];
+    if (lds_set[g.device & 15].load() < lds) {
+        IRH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bcr_reduce_up<B, UF>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set[g.device & 15].store(lds);
+    }
+    hipLaunchKernelGGL((k_bcr_reduce_up<B, UF>), dim3(S.lev[1].nch), dim3(512), lds, g.stream, args, ++S.up_gen, dbg,
+                       (dbg & 128) ? S.stamps.p : (long long *)nullptr);
+}
+template <int B>
+static void bcr_launch_up(Graph &g, const BcrRoute &R, int dbg) {
+    if constexpr (B <= 24) {
+        BcrState &S = *g.bcr;
+        bcr_up_args_write(g);
+        // (tests: the give-up path without a second process -- the word is set as if a wait had timed out)
+        if (g.sw.bcr_fake_up_fail && g.stats.direct_up_fallbacks == 0)
+            IRH_CHECK(hipMemsetAsync(S.up_cnt.p + kUpLevels, 1, sizeof(int), g.stream));
+        if constexpr (B == 8 || B == 16 || B == 24) {
+            if (R.uf) {
+                bcr_up_args_write_unit(S, g.stream);
+                if (R.uf == 2) bcr_launch_up_as<B, 2>(g, S.unit.up_args.p, dbg);
+                else bcr_launch_up_as<B, 1>(g, S.unit.up_args.p, dbg);
+                return;
+            }
+        }
+        if (R.uf) throw HipError{hipErrorInvalidValue};
+        return bcr_launch_up_as<B, 0>(g, S.up_args.p, dbg);
+    }
+    throw HipError{hipErrorInvalidValue};  // (the route takes the upper launch for blocks up to 24 only)
+}
+
+// the single-workgroup top in a launch of its own
+template <int B>
+static void bcr_launch_top(Graph &g, int dbg, long long *stamps) {
+    if constexpr (B <= 24) {
+        BcrState &S = *g.bcr;
+        const int l = (int)S.lev.size() - 1;
+        const BcrLevel &F = S.lev[l - 1];
+        const size_t lds = bcr_top_lds(B, S.lev[l].nb);
+        static std::atomic<size_t> lds_set[16];
+        if (lds_set[g.device & 15].load() < lds) {
+            IRH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bcr_top<B>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            lds_set[g.device & 15].store(lds);
+        }
+        hipLaunchKernelGGL((k_bcr_top<B>), dim3(1), dim3(512), lds, g.stream, S.tsched_dev.p, F.sepD.p, F.sepR.p, F.extD.p,
+                           F.extR.p, F.extG.p, S.lev[l].x.p, dbg, stamps);
+        return;
+    }
+    throw HipError{hipErrorInvalidValue};  // (a sixteen-block top: blocks up to 24 only)
+}
+
+// The instantiation of k_bcr_reduce a route entry names, handed to go(kernel, waves). Only these exist: eight waves for
+// blocks up to 24; the assembling launch at level 0 when a chunk's rows are whole slices; the unit-weight factor on the
+// assembling launch below the top for blocks of 8 / 16 / 24. Anything else the route cannot ask for
+// (tools/bcr_route_host_check.cpp) and is an error here.
+template <int B, class Go>
+static void bcr_reduce_kernel(const BcrLaunch &k, Go go) {
+    auto waves = [&](auto l0, auto top, auto as, auto uf) {
+        constexpr bool L = decltype(l0)::value, T = decltype(top)::value, A = decltype(as)::value;
+        constexpr int U = decltype(uf)::value;
+        if constexpr (B <= 24) {
+            if (k.wide) return go(&k_bcr_reduce<B, 3, L, T, 8, A, U>, 8);
+        }
+        if (k.wide) throw HipError{hipErrorInvalidValue};
+        go(&k_bcr_reduce<B, 3, L, T, 4, A, U>, 4);
+    };
+    using Y = std::true_type;
+    using N = std::false_type;
+    using U0 = std::integral_constant<int, 0>;
+    if (k.uf) {
+        if constexpr (B == 8 || B == 16 || B == 24) {
+            if (k.l0 && !k.top && k.assemble && k.uf == 1) return waves(Y(), N(), Y(), std::integral_constant<int, 1>());
+            if (k.l0 && !k.top && k.assemble && k.uf == 2) return waves(Y(), N(), Y(), std::integral_constant<int, 2>());
+        }
+        throw HipError{hipErrorInvalidValue};
+    }
+    if (k.assemble) {
+        if constexpr ((8 * B) % 64 == 0) {
+            if (k.l0) return k.top ? waves(Y(), Y(), Y(), U0()) : waves(Y(), N(), Y(), U0());
+        }
+        throw HipError{hipErrorInvalidValue};
+    }
+    if (k.l0) k.top ? waves(Y(), Y(), N(), U0()) : waves(Y(), N(), N(), U0());
+    else k.top ? waves(N(), Y(), N(), U0()) : waves(N(), N(), N(), U0());
+}
+// one level's reduction in a launch of its own (the closure columns nothing instantiates -- nfar, far_i, far_j -- are literals)
+template <int B>
+static void bcr_reduce_level(Graph &g, const BcrRoute &R, int l, int dbg, long long *stamps) {
+    BcrState &S = *g.bcr;
+    Level &L0 = g.levels[0];
+    BcrLevel &L = S.lev[l];
+    const BcrLevel *F = l > 0 ? &S.lev[l - 1] : nullptr;
+    const BcrLaunch &k = R.own[l];
+    const bool far = S.nfar > 0;
+    // (the unit-weight factor: level 0's W, inverses and operands are the store's)
+    const BcrUnitLevel *U = k.uf ? &S.unit.lev[0] : nullptr;
+    double *W = U ? U->Wu.p : L.W.p, *Dinv = U ? U->Di.p : far ? S.Dinv[(size_t)l].p : nullptr;
+    BcrAsmArgs A{};
+    int grid = L.nch;
+    if (k.assemble) {
+        // level 0 assembles its own slices first: the chunks' workgroups, then one per slice under no chunk
+        A = BcrAsmArgs{L.nch,   L0.nsl,    (long long)g.m, (long long)g.mpad, g.slot_eid.p, g.tile_e0.p, g.beid.p,
+                       g.bflag.p, g.bcr_wsrc, g.er.p,         L0.excess.p,       L0.idg.p,     g.bval.p};
+        grid += std::max(0, L0.nsl - L.nch * (8 * B / 64));
+        if (U) A.stP = U->P.p, A.stQ = U->Q.p;
+    }
+    bcr_reduce_kernel<B>(k, [&](auto kernel, int waves) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), 0, g.stream, L.nb, L.nred, L0.n, L0.sl_off.p, L0.col.p,
+                           L0.val.p, L0.diag.p, L0.b.p, F ? F->sepD.p : nullptr, F ? F->sepR.p : nullptr,
+                           F ? F->extD.p : nullptr, F ? F->extR.p : nullptr, F ? F->extG.p : nullptr, W, L.sepD.p, L.sepR.p,
+                           L.extD.p, L.extR.p, L.extG.p, S.xtop.p, dbg, 0, (const int *)nullptr, (const int *)nullptr, S.ext0,
+                           g.bptr.p, g.bghost.p, g.bval.p, S.ghost_extcol.p, (int)g.bcr_shard, stamps, Dinv,
+                           far ? S.topDinv.p : nullptr, far ? S.dead.p : nullptr, (int)g.bcr_guard, A);
+    });
+}
+
+// the ways back: of the levels above level 0 in one launch (k_bcr_back_top) unless this is a shard or the closures'
+// columns ride along; xc_top / xext (a shard): the solution of its open top and of the previous rank's separator
+template <int B>
+static void bcr_ways_back(Graph &g, const BcrRoute &R, double4 *Xout, const double *xc_top, const double *xext) {
+    BcrState &S = *g.bcr;
+    Level &L0 = g.levels[0];
+    hipStream_t st = g.stream;
+    const int nl = (int)S.lev.size();
+    const BcrUnit &U = S.unit;
+    double4 *Qap = R.apply ? g.Q.p : (double4 *)nullptr;
+    for (int l = nl - 1; l >= 0; l--) {
+        BcrLevel &L = S.lev[l];
+        if (R.back[l] == kBackTop && l == 1) {
+            BcrBackPlan P;
+            for (int k = 0; k < nl; k++) {
+                P.W[k] = R.uf && k + 1 < nl ? U.lev[(size_t)k].Wu.p : S.lev[k].W.p;
+                P.nb[k] = S.lev[k].nb;
+            }
+            P.top = S.top16 ? nl - 2 : nl - 1;
+            P.base = 1;
+            hipLaunchKernelGGL((k_bcr_back_top<B>), dim3(L.nch), dim3(kBackTopThreads), 0, st, P,
+                               S.top16 ? S.lev[nl - 1].x.p : S.xtop.p, L.x.p, Xout, L0.n, L.nred, Qap, g.f, g.part_score.p,
+                               S.lev[0].nch, (int)S.top16);
+        }
+        if (R.back[l] != kBackOwn) continue;
+        const double *xc = l == nl - 1 ? (xc_top ? xc_top : S.xtop.p) : S.lev[l + 1].x.p;
+        if (l == 0)
+            hipLaunchKernelGGL((k_bcr_back<B, 3, true>), dim3(L.nch), dim3(256), 0, st, L.nb, L.nred, L0.n,
+                               R.uf ? U.lev[0].Wu.p : L.W.p, xc, (double *)nullptr, Xout, (double *)nullptr, 0, 0, 0, xext,
+                               (int)g.bcr_shard, Qap, g.f, g.part_score.p, 0);
+        else
+            hipLaunchKernelGGL((k_bcr_back<B, 3, false>), dim3(L.nch), dim3(256), 0, st, L.nb, L.nred, L0.n, L.W.p, xc,
+                               L.x.p, Xout, (double *)nullptr, 0, 0, 0, xext, (int)g.bcr_shard);
+    }
+}
+
+// One pass of a solve (BcrRequest::phase; a solve without closures on one GPU is one pass). The two side effects between
+// the predicates keep their places: the upper launch's share of the device is asked for once it is wanted, a trimmed
+// unit-weight store is released before the route reads whether one is valid, and allocated after it said "fill".
+template <int B>
+static void bcr_pass(Graph &g, const BcrRequest &rq, const double *xc_top = nullptr, const double *xext = nullptr) {
+    BcrState &S = *g.bcr;
+    BcrUnit &U = S.unit;
+    BcrShape sh = bcr_shape(g);
+    const int dbg = bcr_dbg(sh, rq), nl = sh.nl;
     long long *stamps = nullptr;
     if (dbg & 64) {
         if (!S.stamps.p) S.stamps.alloc((size_t)S.lev[0].nch * 16);
         stamps = S.stamps.p;
     }
-    const int nfar = 0;
-    const int *fi = nullptr, *fj = nullptr;
-    (void)pass;
-    // the reductions of all levels above level 0 in one launch (k_bcr_reduce_up): three right-hand sides, blocks up to 24
-    // (the eight-wave workgroups), at least two such levels, level 1 of at most 256 chunks (one workgroup per CU: all
-    // resident), no closures (their inverses and dead-pivot count ride on the separate launches), not a shard, not
-    // when single levels are timed
-    bool fused_up = false;
-    if constexpr (NR == 3 && B <= 24) {
-        fused_up = nl >= 3 && nl - 1 <= kUpLevels && only < 0 && phase == 0 && !open_top && !g.bcr_shard && S.nfar == 0 &&
-                   S.lev[1].nch <= 256 && !(dbg & 64) && !g.bcr_no_fused_up;
+    bool up = bcr_wants_up(sh, rq);
+    if constexpr (B <= 24) {
         if ((dbg & 128) && !S.stamps.p) S.stamps.alloc((size_t)std::max(S.lev[0].nch * 16, 32 * kUpLevels));
-        if (fused_up) fused_up = bcr_up_reserve<B>(g, S.lev[1].nch);
+        if (up) up = bcr_up_reserve<B>(g, S.lev[1].nch);
     }
-    if (only < 0 && phase != 2) S.up_used = false;
-    // The unit-weight factor (BcrUnit). run_irls announces the first solve of a call (Graph::bcr_unit_req = 1); on the plain
-    // route -- level 0 assembling its own slices, the upper levels in one launch, a sixteen-block top, blocks of 8 / 16 / 24, no
-    // debug word, not guarded -- the handle's first such solve is the full reduction with its outputs pointed at the store
-    // (uf = 1), every later one the right-hand-side-only pass (uf = 2). Requests 2 and 3 are time_kernel's: the
-    // right-hand-side-only solve of a handle whose store is valid, and its upper launch alone.
-    int uf = 0;
-    BcrUnit &U = S.unit;
-    if (only < 0 && phase != 2) U.last = 0;
-    if constexpr (NR == 3 && (B == 8 || B == 16 || B == 24)) {
-        const int req = g.bcr_unit_req;
-        if (req && fused_up && S.top16 && dbg == 0 && !g.bcr_guard && !g.bcr_out && !g.sw.bcr_no_unit_factor &&
-            (g.bcr_asm_fused || req == 3)) {
-            if (!U.lev.empty() && U.epoch != g_unit_epoch.load(std::memory_order_acquire)) U.release();
-            uf = U.valid ? 2 : (req == 1 ? 1 : 0);
-            if (uf == 1 && U.lev.empty()) {
-                // (lazily: a handle that never makes such a solve -- a solver clone, l1ra alone -- keeps nothing)
-                constexpr int NC = 2 * B + 3;
-                U.epoch = g_unit_epoch.load(std::memory_order_acquire);
-                U.lev.resize((size_t)nl - 1);
-                size_t words = 0;
-                for (int l = 0; l + 1 < nl; l++) {
-                    const size_t ne = (size_t)S.lev[l].nch * 7;
-                    U.lev[(size_t)l].Wu.alloc(ne * B * NC);
-                    U.lev[(size_t)l].Di.alloc(ne * B * B);
-                    U.lev[(size_t)l].P.alloc(ne * B * B);
-                    U.lev[(size_t)l].Q.alloc(ne * B * B);
-                    words += ne * B * (NC + 3 * B);
-                }
-                U.top.alloc((size_t)(kTopUnitLast + 1) * B * B);
-                words += (size_t)(kTopUnitLast + 1) * B * B;
-                U.bytes = (int64_t)(words * sizeof(double));
-                // (a partial chunk skips its padding positions: their slots are never written, and never read)
-            }
-        }
-        U.last = uf;
+    if (bcr_wants_unit(sh, rq, up)) {
+        if (!U.lev.empty() && U.epoch != g_unit_epoch.load(std::memory_order_acquire)) U.release();
+        sh.unit_valid = U.valid;
     }
-    const bool uf_up_only = uf == 2 && g.bcr_unit_req == 3;
-    for (int l = 0; l < nl && phase != 2; l++) {
-        if (only >= 0 && only != l) continue;
-        if (l == 0 && uf_up_only) continue;
-        if constexpr (NR == 3 && B <= 24) {
-            if (S.top16 && l == nl - 1 && !fused_up) {
-                // the single-workgroup top in a launch of its own
-                const BcrLevel &F = S.lev[l - 1];
-                const size_t lds = bcr_top_lds(B, S.lev[l].nb);
-                static std::atomic<size_t> lds_set[16];
-                if (lds_set[g.device & 15].load() < lds) {
-                    IRH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bcr_top<B>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    lds_set[g.device & 15].store(lds);
-                }
-                hipLaunchKernelGGL((k_bcr_top<B>), dim3(1), dim3(512), lds, st, S.tsched_dev.p, F.sepD.p, F.sepR.p, F.extD.p,
-                                   F.extR.p, F.extG.p, S.lev[l].x.p, dbg, stamps);
-                continue;
-            }
-            if (fused_up && l >= 1) {
-                if (l > 1) continue;
-                if (S.up_cnt.n < (size_t)kUpLevels + 1) {
-                    S.up_cnt.alloc(kUpLevels + 1);
-                    S.up_cnt.zero(st);
-                    S.up_gen = 0;
-                }
-                if (!S.up_args.p) {
-                    // the launch's arguments: written once per handle
-                    BcrUpArgs A;
-                    memset(&A, 0, sizeof(A));
-                    A.nl = nl - 1;
-                    for (int i = 0; i < A.nl; i++) {
-                        BcrLevel &Li = S.lev[1 + i], &Fi = S.lev[i];
-                        A.lev[i] = BcrUpLevel{Li.nb,          Li.nred,        Li.nch,         (gp_cd)Fi.sepD.p, (gp_cd)Fi.sepR.p,
-                                              (gp_cd)Fi.extD.p, (gp_cd)Fi.extR.p, (gp_cd)Fi.extG.p, (gp_d)Li.W.p,   (gp_d)Li.sepD.p,
-                                              (gp_d)Li.sepR.p, (gp_d)Li.extD.p, (gp_d)Li.extR.p, (gp_d)Li.extG.p};
-                    }
-                    A.n = L0.n;
-                    A.sl_off = (gp_ci)L0.sl_off.p;
-                    A.col = (gp_ci)L0.col.p;
-                    A.val = (gp_cd)L0.val.p;
-                    A.diag = (gp_cd)L0.diag.p;
-                    A.rhs = (gp_cd4)L0.b.p;
-                    A.xtop = (gp_d)S.xtop.p;
-                    A.cnt = (gp_u)S.up_cnt.p;
-                    A.top16 = S.top16;
-                    A.top = S.tsched;
-                    A.xtop_all = (gp_d)S.lev[nl - 1].x.p;
-                    A.fail = (gp_i) reinterpret_cast<int *>(S.up_cnt.p + kUpLevels);
-                    S.up_args.alloc(1);
-                    IRH_CHECK(hipMemcpyAsync(S.up_args.p, &A, sizeof(A), hipMemcpyHostToDevice, st));
-                    IRH_CHECK(hipStreamSynchronize(st));  // (A is on this stack)
-                }
-                // (tests: the give-up path without a second process -- the word is set as if a wait had timed out)
-                if (g.sw.bcr_fake_up_fail && g.stats.direct_up_fallbacks == 0)
-                    IRH_CHECK(hipMemsetAsync(S.up_cnt.p + kUpLevels, 1, sizeof(int), st));
-                const size_t lds = bcr_up_lds<B>(S.top16 ? S.lev[nl - 1].nb : 0);
-                static std::atomic<size_t> lds_set[3][16];
-                auto launch_up = [&](auto uf_tag, const BcrUpArgs *args) {
-                    constexpr int UF = decltype(uf_tag)::value;
-                    if (lds_set[UF][g.device & 15].load() < lds) {
-                        IRH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bcr_reduce_up<B, UF>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                        lds_set[UF][g.device & 15].store(lds);
-                    }
-                    hipLaunchKernelGGL((k_bcr_reduce_up<B, UF>), dim3(S.lev[1].nch), dim3(512), lds, st, args, ++S.up_gen, dbg,
-                                       (dbg & 128) ? S.stamps.p : (long long *)nullptr);
-                };
-                if constexpr (B == 8 || B == 16 || B == 24) {
-                    if (uf && !U.up_args.p) {
-                        // the same arguments with W = the store's and the operand arrays
-                        BcrUpArgs A;
-                        IRH_CHECK(hipMemcpyAsync(&A, S.up_args.p, sizeof(A), hipMemcpyDeviceToHost, st));
-                        IRH_CHECK(hipStreamSynchronize(st));
-                        for (int i = 0; i + 1 < A.nl; i++) {
-                            BcrUnitLevel &Ui = U.lev[(size_t)i + 1];
-                            A.lev[i].W = (gp_d)Ui.Wu.p;
-                            A.lev[i].stD = (gp_d)Ui.Di.p;
-                            A.lev[i].stP = (gp_d)Ui.P.p;
-                            A.lev[i].stQ = (gp_d)Ui.Q.p;
-                        }
-                        A.tst = (gp_d)U.top.p;
-                        U.up_args.alloc(1);
-                        IRH_CHECK(hipMemcpyAsync(U.up_args.p, &A, sizeof(A), hipMemcpyHostToDevice, st));
-                        IRH_CHECK(hipStreamSynchronize(st));  // (A is on this stack)
-                    }
-                    if (uf == 2) launch_up(std::integral_constant<int, 2>(), U.up_args.p);
-                    else if (uf == 1) launch_up(std::integral_constant<int, 1>(), U.up_args.p);
-                    else launch_up(std::integral_constant<int, 0>(), S.up_args.p);
-                } else {
-                    launch_up(std::integral_constant<int, 0>(), S.up_args.p);
-                }
-                S.up_used = true;
-                continue;
-            }
-        }
-        BcrLevel &L = S.lev[l];
-        const BcrLevel *F = l > 0 ? &S.lev[l - 1] : nullptr;
-        const bool top = l == nl - 1 && !open_top;
-#define IRH_BCR_ARGS                                                                                             \
-    L.nb, L.nred, L0.n, L0.sl_off.p, L0.col.p, L0.val.p, L0.diag.p, L0.b.p, F ? F->sepD.p : nullptr,             \
-        F ? F->sepR.p : nullptr, F ? F->extD.p : nullptr, F ? F->extR.p : nullptr, F ? F->extG.p : nullptr, Wl, \
-        L.sepD.p, L.sepR.p, L.extD.p, L.extR.p, L.extG.p, S.xtop.p, dbg, nfar, fi, fj, S.ext0, g.bptr.p, g.bghost.p,  \
-        g.bval.p, S.ghost_extcol.p, (int)g.bcr_shard, stamps, Dl,                                                          \
-        S.nfar > 0 ? S.topDinv.p : (double *)nullptr, S.nfar > 0 ? S.dead.p : (int *)nullptr, (int)g.bcr_guard, asmA
-        // (the unit-weight factor: level 0's W and inverses are the store's)
-        double *Wl = L.W.p, *Dl = S.nfar > 0 ? S.Dinv[(size_t)l].p : (double *)nullptr;
-        if (uf && l == 0) {
-            Wl = U.lev[0].Wu.p;
-            Dl = U.lev[0].Di.p;
-        }
-        // eight waves per chunk when every chunk has a CU to itself (see k_bcr_reduce)
-        const bool wide = L.nch <= 256;
-        // level 0 assembles its own slices first (ls_solve asked): the chunks' workgroups, then one per slice under no chunk
-        BcrAsmArgs asmA{};
-        bool asm0 = false;
-        if constexpr (NR == 3 && (8 * B) % 64 == 0) {
-            asm0 = l == 0 && g.bcr_asm_fused && only < 0 && phase == 0 && !open_top && S.nfar == 0 && !g.bcr_shard;
-            if (asm0) {
-                asmA = BcrAsmArgs{L.nch,   L0.nsl,    (long long)g.m, (long long)g.mpad, g.slot_eid.p, g.tile_e0.p, g.beid.p,
-                                  g.bflag.p, g.bcr_wsrc, g.er.p,         L0.excess.p,       L0.idg.p,     g.bval.p};
-                const int extra = std::max(0, L0.nsl - L.nch * (8 * B / 64));
-                bool launched = false;
-                if constexpr (B == 8 || B == 16 || B == 24) {
-                    if (uf) {
-                        asmA.stP = U.lev[0].P.p;
-                        asmA.stQ = U.lev[0].Q.p;
-#define IRH_BCR_LAUNCH_UNIT(UF_)                                                                                          \
-    if (wide)                                                                                                             \
-        hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, false, 8, true, UF_>), dim3(L.nch + extra), dim3(512), 0, st,       \
-                           IRH_BCR_ARGS);                                                                                 \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, false, 4, true, UF_>), dim3(L.nch + extra), dim3(256), 0, st,       \
-                           IRH_BCR_ARGS);
-                        if (uf == 2) {
-                            IRH_BCR_LAUNCH_UNIT(2)
-                        } else {
-                            IRH_BCR_LAUNCH_UNIT(1)
-                        }
-#undef IRH_BCR_LAUNCH_UNIT
-                        launched = true;
-                    }
-                }
-#define IRH_BCR_LAUNCH_ASM(TOP_)                                                                                          \
-    if (B <= 24 && wide)                                                                                                  \
-        hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, TOP_, (B <= 24 ? 8 : 4), true>), dim3(L.nch + extra),               \
-                           dim3(B <= 24 ? 512 : 256), 0, st, IRH_BCR_ARGS);                                               \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((k_bcr_reduce<B, NR, true, TOP_, 4, true>), dim3(L.nch + extra), dim3(256), 0, st, IRH_BCR_ARGS);
-                if (launched) {
-                } else if (top) {
-                    IRH_BCR_LAUNCH_ASM(true)
-                } else {
-                    IRH_BCR_LAUNCH_ASM(false)
-                }
-#undef IRH_BCR_LAUNCH_ASM
-            }
-        }
-        if (asm0) continue;
-#define IRH_BCR_LAUNCH(L0_, TOP_)                                                                                   \
-    if constexpr (B <= 24) {                                                                                        \
-        if (wide)                                                                                                   \
-            hipLaunchKernelGGL((k_bcr_reduce<B, NR, L0_, TOP_, 8>), dim3(L.nch), dim3(512), 0, st, IRH_BCR_ARGS);   \
-        else                                                                                                        \
-            hipLaunchKernelGGL((k_bcr_reduce<B, NR, L0_, TOP_, 4>), dim3(L.nch), dim3(256), 0, st, IRH_BCR_ARGS);   \
-    } else {                                                                                                        \
-        hipLaunchKernelGGL((k_bcr_reduce<B, NR, L0_, TOP_, 4>), dim3(L.nch), dim3(256), 0, st, IRH_BCR_ARGS);       \
-    }
-        if (l == 0 && top) {
-            IRH_BCR_LAUNCH(true, true)
-        } else if (l == 0) {
-            IRH_BCR_LAUNCH(true, false)
-        } else if (top) {
-            IRH_BCR_LAUNCH(false, true)
-        } else {
-            IRH_BCR_LAUNCH(false, false)
-        }
-#undef IRH_BCR_LAUNCH
-#undef IRH_BCR_ARGS
-    }
-    // the ways back of the levels above level 0 in one launch (k_bcr_back_top) unless this is a shard or the closures'
-    // columns ride along
-    double4 *Xout = g.bcr_out ? g.bcr_out : g.X.p + g.ng;
-    bool fused_back = false;
-    // (a single-workgroup top has made its own way back: the levels below it are left)
-    const int ltop = S.top16 ? nl - 2 : nl - 1;
-    if constexpr (NR == 3) fused_back = ltop >= 1 && !g.bcr_shard && !open_top;
-    // K6 inside the ways back (run_irls asked for it and bcr_apply_ok() said yes): every solution row of level 0 is written
-    // by k_bcr_back (level 0's chunks: slots 0 .. nch0 - 1) or, on a mixed level 1, by k_bcr_back_top (slots nch0 ...)
-    const bool apply = NR == 3 && g.bcr_apply && only < 0 && phase == 0 && (fused_back || (S.top16 && nl == 2)) && !g.bcr_out &&
-                       g.ng == 0;
-    g.bcr_applied = apply;
-    for (int l = ltop; l >= 0 && phase != 1 && !uf_up_only; l--) {
-        if (only >= 0 && only != 100 + l) continue;
-        BcrLevel &L = S.lev[l];
-        if constexpr (NR == 3) {
-            if (fused_back && l >= 1) {
-                if (l > 1) continue;
-                BcrBackPlan P;
-                for (int k = 0; k < nl; k++) {
-                    P.W[k] = uf && k + 1 < nl ? U.lev[(size_t)k].Wu.p : S.lev[k].W.p;
-                    P.nb[k] = S.lev[k].nb;
-                }
-                P.top = ltop;
-                P.base = 1;
-                hipLaunchKernelGGL((k_bcr_back_top<B>), dim3(L.nch), dim3(kBackTopThreads), 0, st, P,
-                                   S.top16 ? S.lev[nl - 1].x.p : S.xtop.p, L.x.p, Xout, L0.n, L.nred,
-                                   apply ? g.Q.p : (double4 *)nullptr, g.f, g.part_score.p, S.lev[0].nch, (int)S.top16);
-                continue;
-            }
-        }
-        const double *xc = l == nl - 1 ? (open_top ? xc_top : S.xtop.p) : S.lev[l + 1].x.p;
-        if (l == 0)
-            hipLaunchKernelGGL((k_bcr_back<B, NR, true>), dim3(L.nch), dim3(256), 0, st, L.nb, L.nred, L0.n,
-                               uf ? U.lev[0].Wu.p : L.W.p, xc,
-                               (double *)nullptr, Xout, (double *)nullptr, 0, 0, nfar, xext, (int)g.bcr_shard,
-                               apply ? g.Q.p : (double4 *)nullptr, g.f, g.part_score.p, 0);
-        else
-            hipLaunchKernelGGL((k_bcr_back<B, NR, false>), dim3(L.nch), dim3(256), 0, st, L.nb, L.nred, L0.n, L.W.p, xc,
-                               L.x.p, Xout, (double *)nullptr, 0, 0, nfar, xext, (int)g.bcr_shard);
-    }
-}
-
-template <int B>
-static void bcr_launch_forward(hipStream_t st, const BcrClPlan &P, int r, int nslots, const int *off, const int4 *steps,
-                               const int4 *init, double *recR, double *recW, double *T, const double *slot_init,
-                               const int2 *fin, const int *gid, double *dep, int world, int rank);
-
-template <int B>
-static void bcr_run_all(Graph &g, int only) {
-    BcrState &S = *g.bcr;
-    if (S.nfar == 0 || only >= 0) {
-        bcr_run<B, 3>(g, only, 0);
-        return;
-    }
-    // closures: the reduction (which keeps the inverses of the eliminated blocks), the closures' forward eliminations,
-    // the Woodbury system, the corrected right-hand sides, the ways back
-    hipStream_t st = g.stream;
-    const int r = S.nfar, npad = S.cl_npad, nl = (int)S.lev.size();
-    if (!S.dead_clean) IRH_CHECK(hipMemsetAsync(S.dead.p, 0, sizeof(int), st));
-    S.dead_clean = false;
-    bcr_run<B, 3>(g, -1, 0, false, 1);
-    BcrClPlan P;
+    const BcrRoute R = bcr_route(sh, rq, up);
+    // (ls_solve skipped K3 exactly when it asked level 0 to assemble: both or neither)
+    if (R.asm0 != rq.assemble || (rq.open_top && rq.phase == 2) != (xc_top != nullptr)) throw HipError{hipErrorInvalidValue};
+    if (rq.only < 0 && rq.phase != 2) S.last = R;
+    U.last = R.uf;
+    if (R.uf == 1 && U.lev.empty()) bcr_unit_alloc(S);
     for (int l = 0; l < nl; l++) {
-        P.W[l] = S.lev[l].W.p;
-        P.Wrw[l] = S.lev[l].W.p;
-        P.Dinv[l] = S.Dinv[(size_t)l].p;
+        if (R.red[l] == kRedOwn) bcr_reduce_level<B>(g, R, l, dbg, stamps);
+        else if (R.red[l] == kRedUp && l == 1) bcr_launch_up<B>(g, R, dbg);
+        else if (R.red[l] == kRedTopAlone) bcr_launch_top<B>(g, dbg, stamps);
     }
-    P.topDinv = S.topDinv.p;
-    P.xtop = S.xtop.p;
-    bcr_launch_forward<B>(st, P, r, S.cl_nslots, S.cl_off.p, S.cl_step.p, S.cl_init.p, S.cl_R.p, S.cl_W.p, S.cl_T.p, nullptr,
-                          nullptr, nullptr, nullptr, 0, 0);
-    const int nt = (npad + 15) / 16;
-    const size_t lds_pairs = (size_t)4 * (S.cl_maxsteps + 64) * sizeof(int);
-    if (r <= kClosurePairsMax && S.cl_maxsteps < 32768 && lds_pairs <= 60 * 1024 && !g.sw.bcr_s_tiles)  // (the switch: the tile kernel for every closure count)
-        hipLaunchKernelGGL((k_bcr_closure_S_pairs<B>), dim3((npad + 3) / 4, npad), dim3(256), lds_pairs, st, r, npad,
-                           S.cl_maxsteps, S.cl_off.p, S.cl_step.p, S.cl_R.p, S.cl_W.p, S.far_e.p, g.bcr_wsrc, g.bcr_wsquare,
-                           S.cl_S.p, S.cl_T.p, S.cl_alive.p);
-    else
-    hipLaunchKernelGGL((k_bcr_closure_S<B>), dim3(nt, nt), dim3(256), (size_t)32 * S.cl_maxsteps * sizeof(int), st, r, npad,
-                       S.cl_maxsteps, S.cl_ndense, S.cl_dense.p, S.cl_off.p, S.cl_step.p, S.cl_R.p,
-                       S.cl_W.p, S.far_e.p, g.bcr_wsrc, g.bcr_wsquare, S.cl_S.p, S.cl_T.p, S.cl_alive.p);
-    if (r <= kSolveLdsMax) {
-        bcr_launch_solve_lds(st, r, npad, S.cl_S.p, S.cl_T.p, S.lam.p);
-    } else {
-        dense_invert_spd(g, S.cl_S.p, npad);
-        hipLaunchKernelGGL(k_bcr_closure_lambda, dim3((r + 3) / 4), dim3(256), 0, st, r, npad, S.cl_S.p, S.cl_T.p,
-                           S.lam.p);
-    }
-    hipLaunchKernelGGL((k_bcr_closure_correct<B>), dim3(S.cl_nelim), dim3(1024), 0, st, P, S.co_off.p, S.co_rec.p,
-                       S.co_elim.p, S.cl_owner.p, S.cl_W.p, S.lam.p);
-    bcr_run<B, 3>(g, -1, 0, false, 2);
+    bcr_ways_back<B>(g, R, rq.out ? static_cast<double4 *>(rq.out) : g.X.p + g.ng, xc_top, xext);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3600,7 +3557,10 @@ static void bcr_shard_reduce_t(Graph &g, BcrTop &T, int rank) {
     if (S.nfix > 0)
         hipLaunchKernelGGL(k_bcr_fix_diag, dim3((S.nfix + 255) / 256), dim3(256), 0, g.stream, S.nfix, S.fix_row.p, S.fix_off.p,
                            S.fix_e.p, g.bcr_wsrc, g.bcr_wsquare, g.levels[0].diag.p, S.fix_saved.p, 0);
-    bcr_run<B, 3>(g, -1, 0, true, 1);
+    BcrRequest rq;
+    rq.phase = 1;
+    rq.open_top = true;
+    bcr_pass<B>(g, rq);
     if (S.nfix > 0)
         hipLaunchKernelGGL(k_bcr_fix_diag, dim3((S.nfix + 255) / 256), dim3(256), 0, g.stream, S.nfix, S.fix_row.p, S.fix_off.p,
                            S.fix_e.p, g.bcr_wsrc, g.bcr_wsquare, g.levels[0].diag.p, S.fix_saved.p, 1);
@@ -3642,7 +3602,10 @@ static void bcr_top_solve_t(Graph &g, BcrTop &T) {
 template <int B>
 static void bcr_shard_back_t(Graph &g, BcrTop &T, int rank) {
     const double *xs = T.x.p + (size_t)rank * B * 3;
-    bcr_run<B, 3>(g, -1, 0, true, 2, xs, rank > 0 ? xs - (size_t)B * 3 : nullptr);
+    BcrRequest rq;
+    rq.phase = 2;
+    rq.open_top = true;
+    bcr_pass<B>(g, rq, xs, rank > 0 ? xs - (size_t)B * 3 : nullptr);
 }
 
 // this rank's closures: their forward eliminations through its levels, its share of S and T and its dead pivots -> T.xbuf
@@ -3790,22 +3753,71 @@ void bcr_shard_closures_forward(Graph &g, BcrTop &T, int rank) { IRH_BCR_DISPATC
 void bcr_top_solve_closures(Graph &g, BcrTop &T) { IRH_BCR_DISPATCH(bcr_top_solve_closures_t, g, T) }
 void bcr_shard_closures_correct(Graph &g, BcrTop &T) { IRH_BCR_DISPATCH(bcr_shard_closures_correct_t, g, T) }
 
+template <int B>
+static void bcr_solve_t(Graph &g, const BcrRequest &rq) {
+    BcrState &S = *g.bcr;
+    if (S.nfar == 0 || rq.only >= 0) {
+        bcr_pass<B>(g, rq);
+        return;
+    }
+    // closures: the reduction (which keeps the inverses of the eliminated blocks), the closures' forward eliminations,
+    // the Woodbury system, the corrected right-hand sides, the ways back
+    hipStream_t st = g.stream;
+    const int r = S.nfar, npad = S.cl_npad, nl = (int)S.lev.size();
+    if (!S.dead_clean) IRH_CHECK(hipMemsetAsync(S.dead.p, 0, sizeof(int), st));
+    S.dead_clean = false;
+    BcrRequest part = rq;
+    part.phase = 1;
+    bcr_pass<B>(g, part);
+    BcrClPlan P;
+    for (int l = 0; l < nl; l++) {
+        P.W[l] = S.lev[l].W.p;
+        P.Wrw[l] = S.lev[l].W.p;
+        P.Dinv[l] = S.Dinv[(size_t)l].p;
+    }
+    P.topDinv = S.topDinv.p;
+    P.xtop = S.xtop.p;
+    bcr_launch_forward<B>(st, P, r, S.cl_nslots, S.cl_off.p, S.cl_step.p, S.cl_init.p, S.cl_R.p, S.cl_W.p, S.cl_T.p, nullptr,
+                          nullptr, nullptr, nullptr, 0, 0);
+    const int nt = (npad + 15) / 16;
+    const size_t lds_pairs = (size_t)4 * (S.cl_maxsteps + 64) * sizeof(int);
+    if (r <= kClosurePairsMax && S.cl_maxsteps < 32768 && lds_pairs <= 60 * 1024 && !g.sw.bcr_s_tiles)  // (the switch: the tile kernel for every closure count)
+        hipLaunchKernelGGL((k_bcr_closure_S_pairs<B>), dim3((npad + 3) / 4, npad), dim3(256), lds_pairs, st, r, npad,
+                           S.cl_maxsteps, S.cl_off.p, S.cl_step.p, S.cl_R.p, S.cl_W.p, S.far_e.p, g.bcr_wsrc, g.bcr_wsquare,
+                           S.cl_S.p, S.cl_T.p, S.cl_alive.p);
+    else
+    hipLaunchKernelGGL((k_bcr_closure_S<B>), dim3(nt, nt), dim3(256), (size_t)32 * S.cl_maxsteps * sizeof(int), st, r, npad,
+                       S.cl_maxsteps, S.cl_ndense, S.cl_dense.p, S.cl_off.p, S.cl_step.p, S.cl_R.p,
+                       S.cl_W.p, S.far_e.p, g.bcr_wsrc, g.bcr_wsquare, S.cl_S.p, S.cl_T.p, S.cl_alive.p);
+    if (r <= kSolveLdsMax) {
+        bcr_launch_solve_lds(st, r, npad, S.cl_S.p, S.cl_T.p, S.lam.p);
+    } else {
+        dense_invert_spd(g, S.cl_S.p, npad);
+        hipLaunchKernelGGL(k_bcr_closure_lambda, dim3((r + 3) / 4), dim3(256), 0, st, r, npad, S.cl_S.p, S.cl_T.p,
+                           S.lam.p);
+    }
+    hipLaunchKernelGGL((k_bcr_closure_correct<B>), dim3(S.cl_nelim), dim3(1024), 0, st, P, S.co_off.p, S.co_rec.p,
+                       S.co_elim.p, S.cl_owner.p, S.cl_W.p, S.lam.p);
+    part.phase = 2;
+    bcr_pass<B>(g, part);
+}
+
 // levels[0] values, diagonal and right-hand side (assemble_values) -> g.X. Asynchronous; only >= 0 launches one
 // kernel alone (bench: 0.. the reductions, 100.. the ways back).
-int bcr_solve(Graph &g, int only) {
-    if (!g.bcr_B) return IROTAVG_ERR_BAD_ARG;
+int bcr_solve(Graph &g, const BcrRequest &rq) {
+    if (!g.bcr_B || rq.phase != 0 || rq.open_top) return IROTAVG_ERR_BAD_ARG;  // (the passes of a shard: bcr_shard_*)
     bcr_alloc(g);
     switch (g.bcr_B) {
-    case 8: bcr_run_all<8>(g, only); break;
-    case 12: bcr_run_all<12>(g, only); break;
-    case 16: bcr_run_all<16>(g, only); break;
-    case 20: bcr_run_all<20>(g, only); break;
-    case 24: bcr_run_all<24>(g, only); break;
-    case 28: bcr_run_all<28>(g, only); break;
-    case 32: bcr_run_all<32>(g, only); break;
+    case 8: bcr_solve_t<8>(g, rq); break;
+    case 12: bcr_solve_t<12>(g, rq); break;
+    case 16: bcr_solve_t<16>(g, rq); break;
+    case 20: bcr_solve_t<20>(g, rq); break;
+    case 24: bcr_solve_t<24>(g, rq); break;
+    case 28: bcr_solve_t<28>(g, rq); break;
+    case 32: bcr_solve_t<32>(g, rq); break;
     default: return IROTAVG_ERR_BAD_ARG;
     }
-    if (only < 0) g.stats.direct_solves += 1;
+    if (rq.only < 0) g.stats.direct_solves += 1;
     return IROTAVG_OK;
 }
 
@@ -3920,23 +3932,19 @@ int bcr_stamps_up(Graph &g, double *out) {
     if (!g.bcr_B) return IROTAVG_ERR_BAD_ARG;
     bcr_alloc(g);
     BcrState &S = *g.bcr;
-    struct DbgScope {
-        BcrState &S;
-        ~DbgScope() { S.dbg_word = -1; }
-    } dbg_scope{S};
-    S.dbg_word = 128 + 256 * g.sw.bcr_stamp_chunk;
+    BcrRequest rq;
+    rq.dbg = 128 + 256 * g.sw.bcr_stamp_chunk;
     const size_t cnt = (size_t)std::max(S.lev[0].nch * 16, 32 * kUpLevels);
     if (!S.stamps.p) S.stamps.alloc(cnt);
     IRH_CHECK(hipMemsetAsync(S.stamps.p, 0, sizeof(long long) * cnt, g.stream));
-    const int rc = bcr_solve(g, -1);
-    S.dbg_word = -1;
+    const int rc = bcr_solve(g, rq);
     if (rc != IROTAVG_OK) return rc;
     long long h[32 * kUpLevels];
     IRH_CHECK(hipMemcpyAsync(h, S.stamps.p, sizeof(h), hipMemcpyDeviceToHost, g.stream));
     IRH_CHECK(hipStreamSynchronize(g.stream));
     bcr_up_release(g);
     for (int k = 0; k < 32 * kUpLevels; k++) out[k] = !h[k] ? -1.0 : (k & 31) >= 20 ? (double)h[k] : (double)(h[k] - h[16]);
-    return S.up_used ? IROTAVG_OK : IROTAVG_ERR_BAD_ARG;
+    return S.last.fused_up ? IROTAVG_OK : IROTAVG_ERR_BAD_ARG;
 }
 
 // development aid: the reduction of `level` once with stamps on; out[0..16) = shader clocks of chunk `chunk` relative to
@@ -3946,15 +3954,12 @@ int bcr_stamps(Graph &g, int level, int chunk, double *out) {
     bcr_alloc(g);
     BcrState &S = *g.bcr;
     if (level < 0 || level >= (int)S.lev.size() || chunk < 0 || chunk >= S.lev[level].nch) return IROTAVG_ERR_BAD_ARG;
-    struct DbgScope {
-        BcrState &S;
-        ~DbgScope() { S.dbg_word = -1; }
-    } dbg_scope{S};
-    S.dbg_word = 64;
+    BcrRequest rq;
+    rq.only = level;
+    rq.dbg = 64;
     if (!S.stamps.p) S.stamps.alloc((size_t)S.lev[0].nch * 16);
     IRH_CHECK(hipMemsetAsync(S.stamps.p, 0, sizeof(long long) * (size_t)S.lev[0].nch * 16, g.stream));
-    const int rc = bcr_solve(g, level);
-    S.dbg_word = -1;
+    const int rc = bcr_solve(g, rq);
     if (rc != IROTAVG_OK) return rc;
     long long h[16];
     IRH_CHECK(hipMemcpyAsync(h, S.stamps.p + (size_t)chunk * 16, sizeof(h), hipMemcpyDeviceToHost, g.stream));
@@ -4215,21 +4220,19 @@ void bcr_gate(Graph &g, double *flags_copy) {
 
 int bcr_closures(Graph &g) { return g.bcr_B ? (int)g.bcr_far_e.size() : 0; }
 
-// partial sums of the score a solve with Graph::bcr_apply leaves in part_score (one double per workgroup of the two ways
-// back), or 0 when such a solve cannot make the step itself: closures, a shard, one level, more slots than the pinned block
-// has doubles for
+// partial sums of the score a solve with BcrRequest::apply leaves in part_score, or 0 (bcr_route.hpp)
 int bcr_apply_slots(Graph &g) {
-    if (!g.bcr_B || !g.bcr_far_e.empty() || g.bcr_shard || g.ng != 0) return 0;
+    if (!g.bcr_B || !g.bcr_far_e.empty() || g.bcr_shard || g.ng != 0) return 0;  // (nothing to allocate for)
     bcr_alloc(g);
-    const BcrState &S = *g.bcr;
-    if (S.lev.size() < 2 || S.nfar != 0) return 0;
-    // (level 0's chunks and, when there is a level of chunks above them, level 1's: a mixed level 1 writes solution rows)
-    const int slots = S.lev[0].nch + (S.top16 && S.lev.size() == 2 ? 0 : S.lev[1].nch);
-    return slots <= 4 * kMaxParts ? slots : 0;
+    return bcr_apply_slots(bcr_shape(g));
+}
+const BcrRoute &bcr_last_route(Graph &g) {
+    static const BcrRoute none;
+    return g.bcr ? g.bcr->last : none;
 }
 
 const int *bcr_fail_word(Graph &g) {
-    if (!g.bcr || !g.bcr->up_used || g.bcr->up_cnt.n < (size_t)kUpLevels + 1) return nullptr;
+    if (!g.bcr || !g.bcr->last.fused_up || g.bcr->up_cnt.n < (size_t)kUpLevels + 1) return nullptr;
     return reinterpret_cast<const int *>(g.bcr->up_cnt.p + kUpLevels);
 }
 bool bcr_up_failed(Graph &g) {

@@ -3,6 +3,7 @@
 #include <functional>
 #include <memory>
 
+#include "bcr_route.hpp"
 #include "common.hpp"
 #include "hostwait.hpp"  // now_seconds; the sequence number and the wait of publish_parts / wait_published
 
@@ -136,29 +137,23 @@ struct Graph {
     // direct solve of a banded level-0 operator by block cyclic reduction (bcr.hip): block size (8 / 16 / 24 / 32;
     // 0 = the solves run through the PCG) and the half-bandwidth found at creation (-1: not looked at)
     int bcr_B = 0, band0 = -1;
-    // run_irls, plain direct path: the ways back of the solve also make the step (K6) and leave the score's partial sums
-    // in part_score, bcr_apply_slots() doubles; bcr_applied = the last solve did
-    bool bcr_apply = false, bcr_applied = false;
     int bcr_up_held = 0;  // 1/1024ths of the device reserved for k_bcr_reduce_up's workgroups (bcr_up_reserve)
     bool pool_headroom = false;  // allocations made for this handle ask the device pool for half as much again (resident.hip)
     bool bcr_no_fused_up = false;  // a wait inside k_bcr_reduce_up gave up once (bcr_up_failed): level by level from then on
-    // ls_solve on a plain banded handle: the level-0 reduction assembles its own slices first (K3 inside k_bcr_reduce,
-    // bcr_run) instead of a launch of k_assemble0w in front of it. bcr_asm_fused: asked of the solve that follows;
-    // bcr_asm_fused_last: what the most recent ls_solve did (irotavg_graph_direct_info)
-    bool bcr_asm_fused = false, bcr_asm_fused_last = false;
-    // the solve that follows may use the handle's unit-weight factor (bcr.hip, BcrUnit): 1 = run_irls's first solve of a
-    // call (weights all one); time_kernel: 2 = the right-hand-side-only solve, 3 = its upper launch alone
-    int bcr_unit_req = 0;
+    // (what a caller asks of ONE solve -- level 0 assembling its own slices, the unit-weight factor, the step inside the
+    // ways back, a redirected result, a debug word -- travels in a BcrRequest, bcr_route.hpp; what the most recent whole
+    // solve did is bcr_last_route()). What the most recent ls_solve did about K3 (irotavg_graph_direct_info):
+    bool bcr_asm_fused_last = false;
     std::unique_ptr<BcrState, BcrDeleter> bcr;
     std::vector<int> bcr_far_i, bcr_far_j, bcr_far_e;  // long-range edges (rows, edge id): Woodbury correction
     const double *bcr_wsrc = nullptr;                  // per-edge weights of the last assembly and whether the
     int bcr_wsquare = 0;                               // operator holds their squares (IRLS) -- assemble_values
     // the guard of the closure path (run_irls, precondition): a direct solve whose BAND part lost a pivot is repeated as
     // a CG solve of the full operator with the regularised direct solve (dead pivot -> the row's own diagonal entry) as
-    // its preconditioner: bcr_guard switches bcr_solve to that mode, bcr_out redirects its result (nullptr: X)
+    // its preconditioner: bcr_guard switches bcr_solve to that mode (handle state: dist.hip sets it on every shard; the
+    // solve's result goes where BcrRequest::out says)
     bool bcr_guard = false;
     bool bcr_last_guarded = false;  // the most recent linear solve of this handle was such a guarded one (bcr_residual)
-    double4 *bcr_out = nullptr;
     // a shard of a sharded sequence solved directly (dist.hip): bcr_ext0 = a rank lies before this one
     bool bcr_shard = false;
     int bcr_ext0 = 0;
@@ -218,7 +213,10 @@ void order_streams(Graph &g, hipStream_t from, hipStream_t to, bool in);
 
 // solver entry points (solver.hip)
 void launch_edge_residual(Graph &g, bool weights_to_one = false);
-int ls_solve(Graph &g, const std::function<void()> *tail = nullptr, bool *tail_ran = nullptr);  // assemble (IRLS weights) + PCG; result in g.X
+// assemble (IRLS weights) + PCG or the direct solve; result in g.X. direct_apply / direct_unit: BcrRequest::apply / unit of
+// the direct solve (run_irls)
+int ls_solve(Graph &g, const std::function<void()> *tail = nullptr, bool *tail_ran = nullptr, bool direct_apply = false,
+             int direct_unit = 0);
 void launch_update_weights(Graph &g, int cost, double sigma, bool gated = false);
 void launch_apply_step(Graph &g, bool gated);
 double finish_apply_step(Graph &g);
@@ -397,7 +395,9 @@ void candidate_angles(Graph &g, int64_t n, const double *q12, double *angle);
 // bcr.hip
 void bcr_plan(Graph &g, const int32_t *I);  // sets Graph::bcr_B / band0 (capi.cpp, ahead of the build)
 void bcr_plan_dev(Graph &g, const DevEdgeSrc &src);  // the same from an edge list on the device (needs g.stream)
-int bcr_solve(Graph &g, int only = -1);     // levels[0] values / diagonal / right-hand side -> g.X, asynchronous
+int bcr_solve(Graph &g, const BcrRequest &rq = {});  // levels[0] values / diagonal / right-hand side -> g.X, asynchronous
+BcrShape bcr_shape(const Graph &g);           // what the route reads of the handle (levels: once they are allocated)
+const BcrRoute &bcr_last_route(Graph &g);     // the route of the handle's most recent whole solve
 int bcr_levels(Graph &g);
 int bcr_info(Graph &g, int64_t *out, int cap);
 int bcr_residual(Graph &g, double *relres);  // ||b - A x|| / ||b|| per coordinate of the last direct solve (one pass over level 0)
@@ -406,7 +406,7 @@ int bcr_closures(Graph &g);  // loop closures the direct solver of this handle c
 // or better; above it the system counts as not solved (IROTAVG_ERR_SOLVER), on one GPU and on shards alike
 constexpr double kClosureRepairAccept = 1e-8;
 bool bcr_band_part_anchored(int64_t m, int f, int64_t nu, int B, const int32_t *I);  // the band part alone is positive definite (exact)
-int bcr_apply_slots(Graph &g);
+int bcr_apply_slots(Graph &g);  // bcr_apply_slots(BcrShape) of the handle, its levels allocated
 void bcr_gate(Graph &g, double *flags_copy = nullptr);  // flags_copy: two doubles' room for a copy of the four flag words (+ the verdict as bcr_gate_skip_word)
 const int *bcr_gate_skip_word(Graph &g);  // flags[FL_DONE] = 1 unless the last direct solve with closures saw a dead pivot (flags[3] = their number)
 void dense_invert_spd(Graph &g, double *A, int npad);  // in place, npad a multiple of 64 (dense.hip)
@@ -421,7 +421,7 @@ int bcr_block_products(int B, int wpe, const double *Dinv, const double *P, cons
 // the last direct solve went through the single-launch upper reduction and a workgroup of it gave up waiting (its solution
 // is all NaN): clears the word, switches the handle to level-by-level launches and says so (one small synchronous read)
 bool bcr_up_failed(Graph &g);
-void bcr_unit_commit(Graph &g, bool finite);  // the score of the solve that bcr_unit_req = 1 announced is in
+void bcr_unit_commit(Graph &g, bool finite);  // the score of the solve that BcrRequest::unit = 1 announced is in
 int bcr_unit_last(Graph &g);                  // what the most recent solve did: 0 nothing, 1 filled the store, 2 was served from it
 bool bcr_unit_valid(Graph &g);
 void bcr_unit_trim() noexcept;                // irotavg_trim_memory: every handle's store is released and invalid

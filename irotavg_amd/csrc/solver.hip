@@ -1813,9 +1813,9 @@ PrecInfo precondition(Graph &g, int first, double rtol2, bool check) {
         // as many steps as there are dead pivots
         hipLaunchKernelGGL(k_pcg_check_only, dim3(1), dim3(kRowBlock), 0, g.stream, g.part_rr.p, np_rr, first, rtol2,
                            g.scal.p, g.flags.p);
-        g.bcr_out = L0.y.p;
-        (void)bcr_solve(g);
-        g.bcr_out = nullptr;
+        BcrRequest rq;
+        rq.out = L0.y.p;
+        (void)bcr_solve(g, rq);
         pi.np_rz = grid_for_elems(L0.n);
         hipLaunchKernelGGL(k_rz_parts, dim3(pi.np_rz), dim3(kRowBlock), 0, g.stream, L0.n, L0.b.p, L0.y.p, g.part_rz.p,
                            g.flags.p);
@@ -2073,14 +2073,15 @@ int pcg_solve_classic(Graph &g, const std::function<void()> *tail, bool *tail_ra
 // much as ~25 PCG iterations. After the coarse values are refreshed, dense_is_stale() compares the
 // coarse diagonal with the one the inverse was computed from; the inverse is re-used (rescaled)
 // when the change is a nearly uniform factor. Depends on data only (deterministic).
-int ls_solve(Graph &g, const std::function<void()> *tail, bool *tail_ran) {
+int ls_solve(Graph &g, const std::function<void()> *tail, bool *tail_ran, bool direct_apply, int direct_unit) {
     if (tail_ran) *tail_ran = false;
-    // a plain banded handle whose chunks of eight blocks are whole slices: no launch of K3 -- the workgroups of the level-0
-    // reduction assemble their own slices first (bcr_run). Everything else assembles in a launch of its own: closures,
-    // shards, blocks of 12 / 20 / 28 rows, the classic assembly, the level-by-level repeat after a wait that gave up
-    const bool fused_asm = g.bcr_B && (8 * g.bcr_B) % 64 == 0 && g.asm_windowed && g.bcr_far_e.empty() && !g.bcr_shard &&
-                           g.ng == 0 && !g.bcr_no_fused_up && !g.sw.bcr_no_fused_asm;
-    if (fused_asm) {
+    // no launch of K3 where the workgroups of the level-0 reduction assemble their own slices first (bcr_can_assemble): the
+    // answer goes to the solve with the request, which refuses a route that disagrees with it
+    BcrRequest direct;
+    direct.apply = direct_apply;
+    direct.unit = direct_unit;
+    direct.assemble = bcr_can_assemble(bcr_shape(g));
+    if (direct.assemble) {
         g.bcr_wsrc = g.dw.p;
         g.bcr_wsquare = 1;
     } else {
@@ -2088,15 +2089,8 @@ int ls_solve(Graph &g, const std::function<void()> *tail, bool *tail_ran) {
     }
     if (g.bcr_B) {
         g.bcr_last_guarded = false;
-        g.bcr_asm_fused = fused_asm;
-        struct Done {
-            Graph &g;
-            ~Done() {
-                g.bcr_asm_fused_last = g.bcr_asm_fused;
-                g.bcr_asm_fused = false;
-            }
-        } done{g};
-        return bcr_solve(g);  // asynchronous; a non-finite result shows in the score of the step
+        g.bcr_asm_fused_last = direct.assemble;
+        return bcr_solve(g, direct);  // asynchronous; a non-finite result shows in the score of the step
     }
     int rc = pcg_solve(g, tail, tail_ran);
     auto failed = [&]() { return rc == IROTAVG_ERR_NOT_CONVERGED || rc == IROTAVG_ERR_SOLVER; };
@@ -2240,18 +2234,9 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
             // banded operator: assembly of level 0, direct solve, weight and rotation update -- ~14 launches and
             // ONE host round trip (the score) per iteration
             const double score_before = score;
-            g.bcr_apply = ap_slots > 0;
-            g.bcr_applied = false;
             with_res = !(it + 1 >= max_iters || (it > 0 && score <= 50.0 * change_th));
             // (the first system of a call is the unit-weight one, whatever the rotations: the direct solver may keep its factor)
-            g.bcr_unit_req = it == 0 && fuse_wr ? 1 : 0;
-            struct UnitReq {
-                Graph &g;
-                ~UnitReq() { g.bcr_unit_req = 0; }
-            } unit_req{g};
-            rc = ls_solve(g);
-            g.bcr_unit_req = 0;
-            g.bcr_apply = false;
+            rc = ls_solve(g, nullptr, nullptr, ap_slots > 0, it == 0 && fuse_wr ? 1 : 0);
             if (rc != IROTAVG_OK) break;
             if (bcr_closures(g) > 0) {
                 // The Woodbury correction of the closures needs the BAND part alone to be positive definite. A cost whose
@@ -2328,7 +2313,7 @@ int run_irls(Graph &g, int cost, double sigma, int max_iters, double change_th, 
                     launch_update_weights(g, cost, sigma);
                     score = apply_step(g);
                 }
-            } else if (fuse_wr && g.bcr_applied) {
+            } else if (fuse_wr && bcr_last_route(g).apply) {
                 const PubPart part = {g.part_score.p, g.h_part(), ap_slots};
                 publish_begin(g);
                 launch_weights_then_residual(g, cost, sigma, &part, with_res);  // (its first workgroup publishes)
@@ -2527,24 +2512,26 @@ int time_kernel(Graph &g, int which, int reps, double *ms) {
             hipLaunchKernelGGL(k_apply_step, dim3(grid_for_elems(g.nu)), dim3(kRowBlock), 0, g.stream,
                                g.nu, g.f, g.ng, g.X.p, g.Q.p, g.part_score.p, 0, (const int *)nullptr);
             break;
-        default:
+        default: {
             // 20 + l: reduction of level l of the banded direct solver, 40 + l: its way back, 19: a whole solve
+            BcrRequest rq;
             if (which == 19) (void)bcr_solve(g);
             else if (which == 17 || which == 18) {
                 // the right-hand-side-only solve over the kept unit-weight factor: all four launches / its upper launch alone
-                g.bcr_unit_req = which == 17 ? 2 : 3;
-                g.bcr_asm_fused = which == 17;
+                rq.unit = which == 17 ? 2 : 3;
+                rq.assemble = which == 17;
                 g.bcr_wsrc = g.dw.p;
                 g.bcr_wsquare = 1;
-                (void)bcr_solve(g);
-                g.bcr_unit_req = 0;
-                g.bcr_asm_fused = false;
+                (void)bcr_solve(g, rq);
                 unit_served = unit_served && bcr_unit_last(g) == 2;
                 bcr_unit_commit(g, false);
             }
-            else if (which >= 20 && which < 40) (void)bcr_solve(g, which - 20);
-            else if (which >= 40 && which < 60) (void)bcr_solve(g, 100 + which - 40);
+            else if (which >= 20 && which < 60) {
+                rq.only = which < 40 ? which - 20 : 100 + which - 40;
+                (void)bcr_solve(g, rq);
+            }
             break;
+        }
         }
     };
     if (which == 17 || which == 18) {

@@ -1,5 +1,5 @@
 """Cases and references for ONE linear solve of the banded direct solver WITH LOOP CLOSURES (irotavg_amd/csrc/bcr.hip,
-bcr_run_all: the Sherman-Morrison-Woodbury correction around the block cyclic reduction), shared by the CPU test of the
+bcr_solve_t: the Sherman-Morrison-Woodbury correction around the block cyclic reduction), shared by the CPU test of the
 references themselves (test_closure_cases_cpu.py) and the GPU test (test_gpu_closure_solve.py). The closure-free half of the
 solver is band_cases.py's; this module reuses its graphs, its restatement of the reduction, its measure and its bar. A plain
 module: building a case and its references needs no device.

@@ -25,7 +25,7 @@ def test_level_shapes_the_cases_are_named_for():
         elif c["route"] == "top16":
             assert len(lev) == 2 and 9 <= lev[1][0] <= 16 and c["top16"]
         elif c["route"] == "up":
-            assert len(lev) in (3, 4) and c["B"] <= 24 and lev[1][1] <= 256 and c["top16"]     # bcr_run: fused_up
+            assert len(lev) in (3, 4) and c["B"] <= 24 and lev[1][1] <= 256 and c["top16"]     # bcr_wants_up
         elif c["route"] == "sep":
             assert len(lev) in (3, 4) and c["B"] >= 28 and not c["top16"]
         elif c["route"] == "mixed":

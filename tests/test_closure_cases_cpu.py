@@ -1,5 +1,5 @@
 """The references of tests/closure_cases.py checked against each other on the CPU -- what test_gpu_closure_solve.py then holds
-the closure half of the banded direct solver (bcr.hip: bcr_run_all) to: the classification of the extra edges and the level
+the closure half of the banded direct solver (bcr.hip: bcr_solve_t) to: the classification of the extra edges and the level
 shapes the cases are named for, the operator's parts against the whole operator, the long-double Woodbury reference
 against the dense long-double Cholesky, the float64 Woodbury formula against LAPACK and the long-double solve on every
 case, and what the bar of 16 can see: every mutant of the formula is above it on a named case."""

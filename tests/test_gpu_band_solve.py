@@ -16,10 +16,10 @@ Per case: Graph(I, QQ, n, f, band_direct=1), set_rotations(Q0), edge_residual(),
   whole slices (blocks of 8 / 16 / 24 / 32) and IROTAVG_BCR_NO_FUSED_ASM is not set. A mixed case on a device whose
   compute-unit count gives no mixed level FAILS with that message;
 * stats(): direct_solves == 1, pcg_solves == 0, direct_up_fallbacks == 0, direct_guarded == 0. IROTAVG_BCR_UP_CAP=0 reports
-  the same: bcr_run asks bcr_up_reserve for a share of the device, gets none and launches the levels one by one -- a refused
+  the same: bcr_pass asks bcr_up_reserve for a share of the device, gets none and launches the levels one by one -- a refused
   reservation is no fall-back (direct_up_fallbacks counts only a wait inside the single launch that gave up, bcr_up_failed);
 * direct_dead_pivots == 0 on every case, the dead-pivot cases included: bcr_invert adds to the counter it is handed, and
-  bcr_run hands one over only on a handle with closures (`S.nfar > 0 ? S.dead.p : nullptr`; the single-launch upper levels
+  bcr_reduce_level hands one over only on a handle with closures (`far ? S.dead.p : nullptr`; the single-launch upper levels
   and the sixteen-block top pass none at all), and the statistic is written by run_irls alone, after a gate refused a step.
   On a closure-free handle a dead pivot is silent; what the case plants shows as X[row] == 0 exactly, asserted here, and as
   the restatement's own count (test_band_cases_cpu.py);

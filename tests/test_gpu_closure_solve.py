@@ -1,4 +1,4 @@
-"""ONE linear solve of the banded direct solver WITH LOOP CLOSURES (irotavg_amd/csrc/bcr.hip, bcr_run_all: the two split passes
+"""ONE linear solve of the banded direct solver WITH LOOP CLOSURES (irotavg_amd/csrc/bcr.hip, bcr_solve_t: the two split passes
 of the reduction around k_bcr_closure_forward / _forward_wave, k_bcr_closure_S / _S_pairs, k_bcr_closure_solve_lds or
 dense_invert_spd + k_bcr_closure_lambda, k_bcr_closure_correct, on the step programs of bcr_closure_plan) against the
 references of tests/closure_cases.py (checked on the CPU by test_closure_cases_cpu.py). test_gpu_band_solve.py is the same

@@ -1,5 +1,6 @@
-"""The host's half of the completion protocol (irotavg_amd/csrc/hostwait.hpp) and the host arithmetic of the window
-kernels (winbatch.hpp) without a device: the stand-alone programs under tools/ are built with AddressSanitizer and
+"""The host's half of the completion protocol (irotavg_amd/csrc/hostwait.hpp), the host arithmetic of the window
+kernels (winbatch.hpp) and the route decision of the banded direct solver (bcr_route.hpp) without a device: the
+stand-alone programs under tools/ are built with AddressSanitizer and
 UndefinedBehaviorSanitizer and run as child processes. Nothing is preloaded and nothing is loaded into Python."""
 import os
 import subprocess
@@ -22,7 +23,8 @@ def sanitizer_runtime(tmp_path_factory):
         pytest.skip("g++ lacks the ASan / UBSan runtime: " + r.stderr.strip().splitlines()[-1])
 
 
-@pytest.mark.parametrize("name,says", [("hostwait_check", "hostwait check ok"), ("winbatch_host_check", "winbatch host check ok")])
+@pytest.mark.parametrize("name,says", [("hostwait_check", "hostwait check ok"), ("winbatch_host_check", "winbatch host check ok"),
+                                       ("bcr_route_host_check", "bcr route host check ok")])
 def test_host_check_is_clean_under_asan_and_ubsan(sanitizer_runtime, tmp_path, name, says):
     exe = str(tmp_path / name)
     r = subprocess.run(["g++", *FLAGS, os.path.join(ROOT, "tools", name + ".cpp"), "-o", exe], capture_output=True, text=True)
