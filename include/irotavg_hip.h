@@ -370,8 +370,8 @@ int irotavg_edge_diagnostics(int64_t m, int64_t n_total, int f, const int32_t *I
  * IROTAVG_HOST_BUILD=0) and keeps its own copies: the caller's buffers are only read and are free again on return.
  * opt->device (or the current device) is the handle's device. An edge index outside [0, n_total) is found by the
  * build's first kernel: IROTAVG_ERR_BAD_ARG, *g stays NULL. No HIP device: IROTAVG_ERR_NO_DEVICE. init_mst has no
- * device form at handle size (window-size problems: irotavg_window_init_mst_batch_dev below): bring initial rotations
- * with irotavg_graph_set_rotations_dev. */
+ * device form at handle size (window-size problems: irotavg_window_init_mst_batch_dev below); irotavg_init_tree_dev
+ * below initialises on device arrays along another tree. Bring initial rotations with irotavg_graph_set_rotations_dev. */
 int irotavg_graph_create_dev(irotavg_graph **g, int64_t m, int64_t n_total, int f, const int32_t *I_dev,
                              const double *QQ_dev, int64_t qq_rs, int64_t qq_cs, const irotavg_options *opt,
                              void *stream);
@@ -519,6 +519,43 @@ int irotavg_cycle_check_dev(int64_t m, int64_t n_total, const int32_t *I_dev, co
 /* Testing and measuring aid, NOT a stable interface (it may change or go without notice): the lanes that share one edge
  * in the triangle kernel, 8, 16, 32 or 64; 0 gives the default back. Process-wide. The results do not depend on it. Returns the width in force before the call, IROTAVG_ERR_BAD_ARG for any other value. */
 int irotavg_cycle_check_group(int lanes);
+
+/* An order-free spanning-tree initialiser, a second one next to irotavg_init_mst (docs/init_tree.md): the tree is the
+ * minimum spanning forest under the keys (rank[k], k), ordered lexicographically -- distinct, so the forest is unique and
+ * depends on no launch geometry; k alone decides between parallel and reversed duplicates. T(0) = Q[0];
+ * T(b) = QQ_k (x) T(a) along a tree edge k = (a, b) walked from a, T(a) = QQ_k* (x) T(b) walked from b (QQ_k*: w negated).
+ * Every free view v >= f gets Q[v] = +-T(v) up to rounding; the sign and the association of the products are not
+ * specified. Computed on the device by Boruvka rounds, the rotations as labels of a union-find composed by pointer
+ * jumping: the number of launches grows with log(n_total), not with the depth of the tree.
+ *   I           m pairs of ids in [0, n_total); self loops are never used
+ *   QQ, ldqq    m x 4 column-major [x y z w], ldqq >= m; taken as given, not normalised
+ *   rank        m int32 or NULL (all zero); rank[k] < 0: edge k is never used
+ *   Q, ldq      n_total x 4 column-major, ldq >= n_total: row 0 is read, the rows from f on are written and never read (they
+ *               may hold NaN), rows 1 .. f-1 are neither read nor written (irotavg_init_mst re-anchors at a fixed view it
+ *               passes; this call does not)
+ *   in_tree     m int32 or NULL: 1 for a tree edge, 0 otherwise
+ *   info        4 int64 on the HOST or NULL: Boruvka rounds run; components left (1: spanning); tree edges with rank > 0;
+ *               the largest rank in the tree
+ * IROTAVG_ERR_NOT_SPANNING unless the forest is one tree over all n_total views, fixed ones included; info is written then
+ * too (the diagnosis), nothing else. IROTAVG_ERR_BAD_ARG before any device work: NULL I, QQ or Q, m <= 0 or above
+ * 0x7fffffff, n_total <= 0 or above 0x7fffffff, f < 1 or f > n_total, ldqq < m, ldq < n_total. No HIP device:
+ * IROTAVG_ERR_NO_DEVICE. An id outside [0, n_total) is found on the device before anything is indexed with it:
+ * IROTAVG_ERR_BAD_ARG, every output byte untouched. Q and in_tree are written on success alone. Memory is O(n_total)
+ * from the device pool. IROTAVG_ERR_SOLVER: a round or pass bound of the implementation was passed (an internal error that
+ * no input should reach). Deterministic: two calls give the same bytes. */
+int irotavg_init_tree(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, const int32_t *rank,
+                      double *Q, int64_t ldq, int32_t *in_tree, int64_t info[4]);
+/* The same on arrays that live on the device: I_dev m pairs (8-byte aligned), QQ_dev and Q_dev strided m x 4 and
+ * n_total x 4 matrices under the stride rule above (8-byte aligned), rank_dev and in_tree_dev 4-byte aligned, the lowest
+ * and highest element of every array device memory of the current device (else IROTAVG_ERR_BAD_ARG, before any kernel).
+ * The kernels go on `stream` itself: inputs may still be in flight there, the outputs are ready for whatever is enqueued
+ * on it next. The call blocks until the status and info are back. Q is bitwise the host call's. */
+int irotavg_init_tree_dev(int64_t m, int64_t n_total, int f, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                          int64_t qq_cs, const int32_t *rank_dev, double *Q_dev, int64_t q_rs, int64_t q_cs,
+                          int32_t *in_tree_dev, int64_t *info /* HOST */, void *stream);
+/* Testing and measuring aid, NOT a stable interface: of the calling thread's most recent irotavg_init_tree[_dev], out[0] =
+ * the kernels and fills it put on the stream, out[1] = the most pointer-jumping passes of one round that moved a pointer. */
+void irotavg_init_tree_counters(int64_t out[2]);
 
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash

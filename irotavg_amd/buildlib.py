@@ -7,8 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 CLI = os.path.join(HERE, "bin", "l1_irls")
 LIB = os.path.join(HERE, "libirotavg_hip.so")
-SOURCES = ["build.cpp", "gbuild.hip", "solver.hip", "cgcg.hip", "dense.hip", "bcr.hip", "l1pd.hip", "capi.cpp", "viewgraph.cpp", "dist.hip", "window.hip", "resident.hip", "marginals.hip", "edgediag.hip", "wincov.hip", "winmst.hip", "cycles.hip", "devapi.hip"]
-HEADERS = ["common.hpp", "graph.hpp", "kernels.hpp", "asm0w.hpp", "bcr_route.hpp", "switches.hpp", "marginals.hpp", "winbatch.hpp", "winio.hpp", "winmst.hpp", "cycles.hpp", "hostwait.hpp", "batchdev.hpp", "../../include/irotavg_hip.h"]
+SOURCES = ["build.cpp", "gbuild.hip", "solver.hip", "cgcg.hip", "dense.hip", "bcr.hip", "l1pd.hip", "capi.cpp", "viewgraph.cpp", "dist.hip", "window.hip", "resident.hip", "marginals.hip", "edgediag.hip", "wincov.hip", "winmst.hip", "cycles.hip", "treeinit.hip", "devapi.hip"]
+HEADERS = ["common.hpp", "graph.hpp", "kernels.hpp", "asm0w.hpp", "bcr_route.hpp", "switches.hpp", "marginals.hpp", "winbatch.hpp", "winio.hpp", "winmst.hpp", "cycles.hpp", "treeinit.hpp", "hostwait.hpp", "batchdev.hpp", "../../include/irotavg_hip.h"]
 
 
 def hipcc():

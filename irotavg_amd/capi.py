@@ -52,6 +52,7 @@ SYMBOLS = [
     "irotavg_window_gate", "irotavg_window_gate_batch_dev",
     "irotavg_window_init_mst_batch_dev",
     "irotavg_cycle_check", "irotavg_cycle_check_dev", "irotavg_cycle_check_group",
+    "irotavg_init_tree", "irotavg_init_tree_dev", "irotavg_init_tree_counters",
 ]
 
 
@@ -187,6 +188,11 @@ def lib():
     L.irotavg_cycle_check_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, vp, vp, vp, _i64p,
                                           vp]
     L.irotavg_cycle_check_group.argtypes = [C.c_int]
+    L.irotavg_init_tree.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _ip, _dp, C.c_int64, _ip, _i64p]
+    L.irotavg_init_tree_dev.argtypes = [C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64,
+                                        C.c_int64, vp, _i64p, vp]
+    L.irotavg_init_tree_counters.argtypes = [_i64p]
+    L.irotavg_init_tree_counters.restype = None
     L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
     L.irotavg_viewgraph_num_connections.restype = C.c_int64
@@ -702,6 +708,47 @@ def cycle_check_group(lanes):
     if old < 0:
         raise IrotavgError(old, "irotavg_cycle_check_group")
     return old
+
+
+INFO_FIELDS = ("rounds", "components", "ranked_edges", "max_rank")
+
+
+def init_tree(I, QQ, n_total, Q, f=1, rank=None, in_tree=True, info=True, allow_rc=()):
+    """irotavg_init_tree (docs/init_tree.md): the order-free spanning-tree initialiser. Q (n_total, 4): row 0 is read, the
+    rows from f on are written in place on success (Q must be a float64 array; it is updated through a column-major copy).
+    rank: m int32 or None. Returns dict(rc, Q, in_tree (int32, m, preset to -1; None if not asked for), info (dict of
+    INFO_FIELDS; None unless rc is OK or ERR_NOT_SPANNING)). Anything but OK raises unless listed in allow_rc."""
+    I = edges(I)
+    QQ = fmat(QQ)
+    m = len(I)
+    if QQ.shape != (m, 4):
+        raise ValueError("QQ must be (%d, 4)" % m)
+    Qf = fmat(Q)
+    if Qf.shape != (int(n_total), 4):
+        raise ValueError("Q must be (%d, 4)" % int(n_total))
+    rk = None
+    if rank is not None:
+        rk = np.ascontiguousarray(rank, dtype=np.int32)
+        if rk.shape != (m,):
+            raise ValueError("rank must be (%d,)" % m)
+    tree = np.full(m, -1, dtype=np.int32) if in_tree else None
+    s = (C.c_int64 * 4)(-1, -1, -1, -1)
+    rc = lib().irotavg_init_tree(m, int(n_total), int(f), _i(I), _d(QQ), QQ.shape[0], None if rk is None else _i(rk),
+                                 _d(Qf), Qf.shape[0], None if tree is None else _i(tree), s if info else None)
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_init_tree")
+    if rc == OK:
+        Q[...] = Qf
+    return dict(rc=rc, Q=Q, in_tree=tree,
+                info=dict(zip(INFO_FIELDS, (int(v) for v in s))) if info and rc in (OK, ERR_NOT_SPANNING) else None)
+
+
+def init_tree_counters():
+    """irotavg_init_tree_counters: (launches, most moving pointer-jumping passes of one round) of this thread's most recent
+    init_tree. A measuring aid."""
+    out = (C.c_int64 * 2)(0, 0)
+    lib().irotavg_init_tree_counters(out)
+    return int(out[0]), int(out[1])
 
 
 def plan_host(world, rank, I, n_total, f):

@@ -541,4 +541,46 @@ int irotavg_cycle_check_dev(int64_t m, int64_t n_total, const int32_t *I_dev, co
 
 int irotavg_cycle_check_group(int lanes) { return cycle_check_group(lanes); }
 
+// The order-free spanning-tree initialiser (docs/init_tree.md; the kernels: treeinit.hip). Handle-free; the device form runs
+// on the caller's stream itself, as the cycle check does.
+static bool tree_sizes_ok(int64_t m, int64_t n_total, int f) {
+    return m > 0 && m <= 0x7fffffffLL && n_total > 0 && n_total <= 0x7fffffffLL && f >= 1 && f <= n_total;
+}
+static bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+int irotavg_init_tree(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, const int32_t *rank,
+                      double *Q, int64_t ldq, int32_t *in_tree, int64_t info[4]) {
+    if (!I || !QQ || !Q || !tree_sizes_ok(m, n_total, f) || ldqq < m || ldq < n_total) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int { return init_tree_host(m, n_total, f, I, QQ, ldqq, rank, Q, ldq, in_tree, info); });
+}
+
+int irotavg_init_tree_dev(int64_t m, int64_t n_total, int f, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                          int64_t qq_cs, const int32_t *rank_dev, double *Q_dev, int64_t q_rs, int64_t q_cs,
+                          int32_t *in_tree_dev, int64_t *info, void *stream) {
+    if (!I_dev || !QQ_dev || !Q_dev || !tree_sizes_ok(m, n_total, f) || !strides_ok(m, 4, qq_rs, qq_cs) ||
+        !strides_ok(n_total, 4, q_rs, q_cs))
+        return IROTAVG_ERR_BAD_ARG;
+    if (!aligned8(I_dev) || !aligned8(QQ_dev) || !aligned8(Q_dev) || !aligned4(rank_dev) || !aligned4(in_tree_dev))
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!dev_index_ok(I_dev, m, device) || !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device) ||
+            !dev_matrix_ok(Q_dev, n_total, 4, q_rs, q_cs, device))
+            return IROTAVG_ERR_BAD_ARG;
+        const int32_t *const per_edge[2] = {rank_dev, in_tree_dev};
+        for (const int32_t *p : per_edge)
+            if (p && !dev_span_ok(p, p + m - 1, device)) return IROTAVG_ERR_BAD_ARG;
+        const TreeArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, rank_dev, Q_dev, (long long)q_rs, (long long)q_cs,
+                           in_tree_dev};
+        return init_tree_dev(m, n_total, f, A, info, static_cast<hipStream_t>(stream));
+    });
+}
+
+void irotavg_init_tree_counters(int64_t out[2]) {
+    if (out) init_tree_counters(out);
+}
+
 }  // extern "C"

@@ -342,6 +342,23 @@ int cycle_check_dev(int64_t m, int64_t n_total, const CycleArrays &A, double thr
                     hipStream_t stream);
 int cycle_check_host(int64_t m, int64_t n_total, const CycleArrays &A, double threshold, int64_t *summary);
 int cycle_check_group(int lanes);  // irotavg_cycle_check_group
+// treeinit.hip: the order-free spanning-tree initialiser (irotavg_init_tree[_dev]; docs/init_tree.md). The arguments have
+// been checked. The device form runs on `stream`, reads row 0 of Q and writes the rows from f on; the host form uploads,
+// runs the same kernels and copies those rows back. Both block until the status and info are back; rank, in_tree and info
+// may each be nullptr. Outputs are written on success alone, info also with IROTAVG_ERR_NOT_SPANNING.
+struct TreeArrays {
+    const int32_t *I;  // m pairs
+    const double *QQ;  // strided m x 4
+    long long qq_rs, qq_cs;
+    const int32_t *rank;  // m, or nullptr: all zero
+    double *Q;            // strided n_total x 4
+    long long q_rs, q_cs;
+    int32_t *in_tree;  // m, or nullptr
+};
+int init_tree_dev(int64_t m, int64_t n_total, int f, const TreeArrays &A, int64_t *info /* host */, hipStream_t stream);
+int init_tree_host(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, const int32_t *rank, double *Q,
+                   int64_t ldq, int32_t *in_tree, int64_t *info);
+void init_tree_counters(int64_t out[2]);  // irotavg_init_tree_counters
 // wincov.hip: the uncertainty queries of a window-size problem in one kernel launch (docs/viewgraph_uncertainty.md)
 struct WinCov;
 WinCov *wincov_new();

@@ -170,6 +170,18 @@ class TorchGraph(capi.Graph):
         _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
         return cycle_check(edge_index, QQ, self.n_total, threshold, **kw)
 
+    def init_tree(self, edge_index, QQ, rank=None, **kw):
+        """init_tree (below) of the tensors passed with the handle's n_total and f, then set_rotations: the handle starts
+        from the tree's rotations without a host round trip. The anchor Q[0] and the other fixed rows are the identity.
+        Returns init_tree's dict; its Q is the (n_total, 4) tensor handed to the handle."""
+        _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
+        Q = torch.zeros((self.n_total, 4), dtype=torch.float64, device=self.device)
+        Q[:, 3] = 1.0
+        out = init_tree(edge_index, QQ, self.n_total, Q, self.f, rank, **kw)
+        if out["rc"] == capi.OK:
+            self.set_rotations(Q)
+        return out
+
     # the host-array forms of the parent stay reachable under their own names
     host_set_rotations = capi.Graph.set_rotations
     host_set_weights = capi.Graph.set_weights
@@ -425,3 +437,63 @@ def cycle_check(edge_index, QQ, n_total, threshold=5 * 3.141592653589793 / 180, 
     _allowed(rc, "irotavg_cycle_check_dev", allow_rc)
     return dict(rc=rc, tri_count=outs[0], tri_ok=outs[1], tri_min=outs[2],
                 summary=dict(zip(capi.SUMMARY_FIELDS, (int(v) for v in s))) if summary and rc == capi.OK else None)
+
+
+# ---- the order-free spanning-tree initialiser (irotavg_init_tree_dev, docs/init_tree.md) ----------------------------------
+def rank_from_cycle_check(tri_count, tri_ok):
+    """The rank init_tree takes, from the counts of cycle_check, in plain torch on the device: 0 for a supported edge
+    (tri_ok >= 1), 1 for an untested one (tri_count == 0), 2 for a contradicted one (triangles, none of them consistent).
+    Returns an int32 tensor of m entries."""
+    _check(tri_count, "tri_count", (torch.int32,), (None,), placed=False)
+    _check(tri_ok, "tri_ok", (torch.int32,), (int(tri_count.shape[0]),), placed=False)
+    if tri_ok.device != tri_count.device:
+        raise ValueError("tri_ok is on %s, tri_count on %s" % (tri_ok.device, tri_count.device))
+    rank = torch.full_like(tri_count, 2)
+    rank[tri_count == 0] = 1
+    rank[tri_ok >= 1] = 0
+    return rank
+
+
+def init_tree(edge_index, QQ, n_total, Q, f=1, rank=None, in_tree=False, allow_rc=()):
+    """Initial rotations along the minimum spanning tree under the keys (rank[k], k), on torch's current stream: the tree
+    does not depend on the order of the edge list beyond the index k that breaks ties, and the number of launches grows
+    with log(n_total). A second initialiser next to capi / ral init_mst, whose sweep it does not reproduce.
+
+    edge_index: (m, 2) int32 or int64 (narrowed on the device: a value outside int32 range becomes an id the device check
+    refuses), QQ: (m, 4) and Q: (n_total, 4) float64 with any strides. Row 0 of Q is read, the rows from f on are written
+    in place (they are never read and may hold NaN), rows 1 .. f-1 are neither read nor written. rank: None (all zero) or a
+    contiguous int32 tensor of m entries, rank[k] < 0: edge k is never used (rank_from_cycle_check gives one). in_tree:
+    True (a new int32 tensor), False / None, or a contiguous int32 tensor of m entries to fill. Returns dict(rc, Q,
+    in_tree, info); info is a host dict of capi.INFO_FIELDS, also with ERR_NOT_SPANNING (then Q and in_tree are as they
+    were). An id outside [0, n_total) gives ERR_BAD_ARG with every output byte as it was; anything but OK raises unless
+    listed in allow_rc. The call blocks until the status is back."""
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), placed=False)
+    m = int(edge_index.shape[0])
+    _check(QQ, "QQ", (torch.float64,), (m, 4), placed=False)
+    n_total, f = int(n_total), int(f)
+    _check(Q, "Q", (torch.float64,), (n_total, 4), placed=False)
+    if rank is not None:
+        _check(rank, "rank", (torch.int32,), (m,), placed=False)
+    if not (in_tree is True or in_tree is False or in_tree is None):
+        _check(in_tree, "in_tree", (torch.int32,), (m,), placed=False)
+    if m < 1:
+        raise ValueError("edge_index must have at least one row")
+    if not 0 < n_total <= INT32_MAX:
+        raise ValueError("n_total must lie in [1, 2^31 - 1], got %d" % n_total)
+    if not 1 <= f <= n_total:
+        raise ValueError("f must lie in [1, n_total], got %d" % f)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (m, 4), device)
+    _check(Q, "Q", (torch.float64,), (n_total, 4), device)
+    rk = None if rank is None else _vector(rank, "rank", m, device, torch.int32)
+    tree = _output(in_tree, "in_tree", m, device, torch.int32)
+    s = (C.c_int64 * 4)(-1, -1, -1, -1)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        rc = capi.lib().irotavg_init_tree_dev(m, n_total, f, _ptr(ei), _ptr(QQ), *matrix_strides(QQ),
+                                              None if rk is None else _ptr(rk), _ptr(Q), *matrix_strides(Q),
+                                              None if tree is None else _ptr(tree), s, _stream(device))
+    _allowed(rc, "irotavg_init_tree_dev", allow_rc)
+    return dict(rc=rc, Q=Q, in_tree=tree,
+                info=dict(zip(capi.INFO_FIELDS, (int(v) for v in s))) if rc in (capi.OK, capi.ERR_NOT_SPANNING) else None)
