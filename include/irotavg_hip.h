@@ -520,6 +520,42 @@ int irotavg_cycle_check_dev(int64_t m, int64_t n_total, const int32_t *I_dev, co
  * in the triangle kernel, 8, 16, 32 or 64; 0 gives the default back. Process-wide. The results do not depend on it. Returns the width in force before the call, IROTAVG_ERR_BAD_ARG for any other value. */
 int irotavg_cycle_check_group(int lanes);
 
+/* The four-cycle test, for the edges that no triangle tests (docs/cycle_check.md, "Four-cycles"): a loop closure joins two
+ * distant parts of a view sequence and closes no triangle, but closures come in clusters, and the quadrilateral
+ * a -> b -> b' -> a' -> a of two closures and two sequence edges tests both. A quadrilateral of edge k = (a, b) is an
+ * ordered triple (k1, k2, k3): k1 joins b and c, k2 joins c and d, k3 joins d and a; a, b, c, d pairwise distinct, no self
+ * loop among the four; parallel edges are distinct, every triple counts; a triangle is not a quadrilateral. Its error is
+ * the angle of q(k3, d->a) (x) (q(k2, c->d) (x) (q(k1, b->c) (x) q(k, a->b))), in this association, wrapped and taken in
+ * absolute value as the triangle's. Inputs as irotavg_cycle_check, and
+ *   ne, edges   the edges to test: ne int32 edge ids in [0, m), in any order, duplicates allowed (computed twice); or
+ *               NULL with ne == m: all m edges in order. The usual subset: the edges with tri_count == 0
+ *   quad_count  ne int32 or NULL: entry t counts the quadrilaterals of edge edges[t] (stored saturated at 2^31 - 1)
+ *   quad_ok     ne int32 or NULL: those with error <= threshold
+ *   quad_min    ne doubles or NULL: the smallest error, +inf without a quadrilateral
+ *   summary     4 int64 on the HOST or NULL: sum of quad_count; tested edges with quad_ok >= 1; tested edges with
+ *               quad_count >= 1 and quad_ok == 0; tested edges with quad_count == 0 (the last three add up to ne)
+ * A quadrilateral whose error is not finite counts, is never ok and leaves quad_min alone. A self loop gets 0, 0, +inf.
+ * Errors and write rules are those of irotavg_cycle_check; in addition ne < 0, ne above 0x7fffffff, edges NULL with
+ * ne != m or edges not 4-byte aligned is IROTAVG_ERR_BAD_ARG before any device work, and an entry of edges outside [0, m)
+ * is found on the device before anything is indexed with it: IROTAVG_ERR_BAD_ARG, every output byte untouched. With
+ * every output NULL the call is the id check, of edge ids and view ids. Each tested edge walks the shorter of its two
+ * rows and, for every neighbour there, that neighbour's row: about deg^2 look-ups per edge; nothing more is done for
+ * hubs. Memory is O(m) whatever n_total is. Deterministic: two calls give the same bytes. */
+int irotavg_cycle_check4(int64_t m, int64_t n_total, const int32_t *I, const double *QQ, int64_t ldqq, double threshold,
+                         int64_t ne, const int32_t *edges, int32_t *quad_count, int32_t *quad_ok, double *quad_min,
+                         int64_t summary[4]);
+/* The same on arrays that live on the device, under the rules of irotavg_cycle_check_dev: edges_dev and the count arrays
+ * 4-byte aligned, quad_min_dev 8-byte aligned, the lowest and highest element of every array device memory of the current
+ * device. The kernels go on `stream` itself; the call blocks until the error word and the summary are back. Bitwise the
+ * host call. */
+int irotavg_cycle_check4_dev(int64_t m, int64_t n_total, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                             int64_t qq_cs, double threshold, int64_t ne, const int32_t *edges_dev, int32_t *quad_count_dev,
+                             int32_t *quad_ok_dev, double *quad_min_dev, int64_t summary[4] /* HOST */, void *stream);
+/* Testing and measuring aid, NOT a stable interface, as irotavg_cycle_check_group: the lanes of one sub-group of the
+ * quadrilateral kernel, 8, 16, 32 or 64; 0 gives the default back. Process-wide. The results do not depend on it. Returns
+ * the width in force before the call, IROTAVG_ERR_BAD_ARG for any other value. */
+int irotavg_cycle_check4_group(int lanes);
+
 /* An order-free spanning-tree initialiser, a second one next to irotavg_init_mst (docs/init_tree.md): the tree is the
  * minimum spanning forest under the keys (rank[k], k), ordered lexicographically -- distinct, so the forest is unique and
  * depends on no launch geometry; k alone decides between parallel and reversed duplicates. T(0) = Q[0];

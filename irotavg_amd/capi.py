@@ -52,6 +52,7 @@ SYMBOLS = [
     "irotavg_window_gate", "irotavg_window_gate_batch_dev",
     "irotavg_window_init_mst_batch_dev",
     "irotavg_cycle_check", "irotavg_cycle_check_dev", "irotavg_cycle_check_group",
+    "irotavg_cycle_check4", "irotavg_cycle_check4_dev", "irotavg_cycle_check4_group",
     "irotavg_init_tree", "irotavg_init_tree_dev", "irotavg_init_tree_counters",
 ]
 
@@ -188,6 +189,11 @@ def lib():
     L.irotavg_cycle_check_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, vp, vp, vp, _i64p,
                                           vp]
     L.irotavg_cycle_check_group.argtypes = [C.c_int]
+    L.irotavg_cycle_check4.argtypes = [C.c_int64, C.c_int64, _ip, _dp, C.c_int64, C.c_double, C.c_int64, _ip, _ip, _ip, _dp,
+                                       _i64p]
+    L.irotavg_cycle_check4_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_int64, vp, vp,
+                                           vp, vp, _i64p, vp]
+    L.irotavg_cycle_check4_group.argtypes = [C.c_int]
     L.irotavg_init_tree.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _ip, _dp, C.c_int64, _ip, _i64p]
     L.irotavg_init_tree_dev.argtypes = [C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64,
                                         C.c_int64, vp, _i64p, vp]
@@ -282,6 +288,9 @@ def edges(I):
     if I.ndim != 2 or I.shape[1] != 2:
         raise ValueError("I must be (m, 2)")
     return I
+
+
+_edge_pairs = edges  # the name for functions that have an argument called edges (cycle_check4)
 
 
 def default_options(**kw):
@@ -707,6 +716,46 @@ def cycle_check_group(lanes):
     old = lib().irotavg_cycle_check_group(int(lanes))
     if old < 0:
         raise IrotavgError(old, "irotavg_cycle_check_group")
+    return old
+
+
+SUMMARY4_FIELDS = ("quadrilaterals", "supported", "contradicted", "untested")
+
+
+def cycle_check4(I, QQ, n_total, threshold=5 * np.pi / 180, edges=None, count=True, ok=True, min_err=True, summary=True,
+                 allow_rc=()):
+    """irotavg_cycle_check4 (docs/cycle_check.md, "Four-cycles"): the four-cycle test of the edges listed (edges: ne int32
+    edge ids, or None: all m in order), before any solve. Returns dict(rc, quad_count, quad_ok (int32, ne each), quad_min
+    (float64, ne), summary (dict of SUMMARY4_FIELDS)); an output that was not asked for is None. Counts are preset to -1
+    and quad_min to NaN, and written only on success."""
+    I = _edge_pairs(I)
+    QQ = fmat(QQ)
+    m = len(I)
+    if QQ.shape != (m, 4):
+        raise ValueError("QQ must be (%d, 4)" % m)
+    sub = None if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
+    if sub is not None and sub.ndim != 1:
+        raise ValueError("edges must be one-dimensional")
+    ne = m if sub is None else len(sub)
+    cnt = np.full(ne, -1, dtype=np.int32) if count else None
+    okc = np.full(ne, -1, dtype=np.int32) if ok else None
+    mn = np.full(ne, np.nan) if min_err else None
+    s = (C.c_int64 * 4)(-1, -1, -1, -1)
+    rc = lib().irotavg_cycle_check4(m, int(n_total), _i(I), _d(QQ), QQ.shape[0], float(threshold), ne,
+                                    None if sub is None else _i(sub), None if cnt is None else _i(cnt),
+                                    None if okc is None else _i(okc), None if mn is None else _d(mn), s if summary else None)
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_cycle_check4")
+    return dict(rc=rc, quad_count=cnt, quad_ok=okc, quad_min=mn,
+                summary=dict(zip(SUMMARY4_FIELDS, (int(v) for v in s))) if summary and rc == OK else None)
+
+
+def cycle_check4_group(lanes):
+    """irotavg_cycle_check4_group: the lanes of one sub-group of the quadrilateral kernel (8, 16, 32, 64; 0: the default);
+    returns the width in force before. A measuring aid: no result depends on it."""
+    old = lib().irotavg_cycle_check4_group(int(lanes))
+    if old < 0:
+        raise IrotavgError(old, "irotavg_cycle_check4_group")
     return old
 
 

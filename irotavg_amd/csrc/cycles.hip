@@ -11,7 +11,8 @@
 // No atomics, no flag between workgroups, no loop that is not bounded by a row length or 32 rounds of a search. The sums
 // are integers and the one floating-point reduction is a minimum: no result depends on an order. Memory: 2m keys and
 // values twice (sort in, sort out), the sort's own storage, an AoS image of QQ unless the caller's rows are 16-byte rows
-// already -- nothing grows with n_total.
+// already -- nothing grows with n_total. Steps 1, 2, the AoS image and step 4 are shared with the four-cycle test
+// (cycles4.hip) through cyc_prep_alloc / cyc_prep_run / cyc_finish.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -23,6 +24,7 @@
 #include "kernels.hpp"   // tile_range
 #include "winbatch.hpp"  // rows16
 #include "cycles.hpp"
+#include "cycload.hpp"
 
 namespace irh {
 namespace {
@@ -59,14 +61,6 @@ __global__ __launch_bounds__(kT) void k_cyc_image(long long m, const double *__r
     img[2 * k] = make_double2(r[0], r[cs]);
     img[2 * k + 1] = make_double2(r[2 * cs], r[3 * cs]);
 }
-
-struct CycDevLoad {  // QQ_k as two 16-byte loads
-    const double2 *q;
-    __host__ __device__ CycQ operator()(uint32_t k) const {
-        const double2 lo = q[2 * (size_t)k], hi = q[2 * (size_t)k + 1];
-        return CycQ{lo.x, lo.y, hi.x, hi.y};
-    }
-};
 
 template <int G>
 __global__ __launch_bounds__(kT) void k_cyc_triangles(int m, long long n2, const uint64_t *__restrict__ keys,
@@ -160,64 +154,82 @@ int cycle_check_group(int lanes) {
     return g_group.exchange(lanes);
 }
 
-int cycle_check_dev(int64_t m, int64_t n_total, const CycleArrays &A, double threshold, int64_t *summary, hipStream_t stream) {
+// ---- the part both cycle tests share (graph.hpp: CycPrep): every temporary first, then emit, sort and the AoS image ----------
+void cyc_prep_alloc(CycPrep &P, int64_t m, int64_t n_total, const double *QQ, long long qq_rs, long long qq_cs, bool sort,
+                    hipStream_t stream) {
     const long long n2 = 2 * (long long)m;
-    const bool triangles = A.tri_count || A.tri_ok || A.tri_min || summary;
-    const bool own_rows = rows16(reinterpret_cast<uintptr_t>(A.QQ), A.qq_rs, A.qq_cs);
-    const int G = g_group.load();
-    // the workgroups of the triangle kernel: kCycPasses passes each while the graph is small, then longer chunks
-    long long nwg = std::max<long long>(1, (m + (long long)(kT / G) * kCycPasses - 1) / ((long long)(kT / G) * kCycPasses));
-    if (nwg > 8) nwg = std::min<long long>(kCycMaxGrid, (nwg + 7) / 8 * 8);
-    // every temporary first (the pool): nothing after the first launch can fail for want of memory
-    DevBuf<uint64_t> kin, kout;
-    DevBuf<uint32_t> vin, vout;
-    DevBuf<char> tmp;
-    DevBuf<double2> img;
-    DevBuf<long long> parts, head;
-    const unsigned bits = (unsigned)cyc_key_bits(n_total);
-    size_t bytes = 0;
-    kin.alloc((size_t)n2);
-    vin.alloc((size_t)n2);
-    head.alloc(5);
-    if (triangles) {  // (the id check alone ends behind the first kernel)
-        IRH_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                            (uint32_t *)nullptr, (size_t)n2, 0u, bits, stream));
-        kout.alloc((size_t)n2);
-        vout.alloc((size_t)n2);
-        tmp.alloc(std::max<size_t>(bytes, 1));
-        if (!own_rows) img.alloc(2 * (size_t)m);
-        parts.alloc(4 * (size_t)nwg);
+    P.sort = sort;
+    P.own_rows = rows16(reinterpret_cast<uintptr_t>(QQ), qq_rs, qq_cs);
+    P.bits = (unsigned)cyc_key_bits(n_total);
+    P.bytes = 0;
+    P.kin.alloc((size_t)n2);
+    P.vin.alloc((size_t)n2);
+    P.head.alloc(5);
+    if (sort) {  // (the id check alone ends behind the first kernel)
+        IRH_CHECK(rocprim::radix_sort_pairs(nullptr, P.bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                            (uint32_t *)nullptr, (size_t)n2, 0u, P.bits, stream));
+        P.kout.alloc((size_t)n2);
+        P.vout.alloc((size_t)n2);
+        P.tmp.alloc(std::max<size_t>(P.bytes, 1));
+        if (!P.own_rows) P.img.alloc(2 * (size_t)m);
     }
-    const int2 *I2 = reinterpret_cast<const int2 *>(A.I);
-    IRH_CHECK(hipMemsetAsync(head.p, 0, 5 * sizeof(long long), stream));
-    hipLaunchKernelGGL(k_cyc_emit, dim3(grid_of(m)), dim3(kT), 0, stream, (long long)m, (long long)n_total, I2, kin.p, vin.p,
-                       head.p);
+}
+
+void cyc_prep_run(CycPrep &P, int64_t m, int64_t n_total, const int32_t *I, const double *QQ, long long qq_rs, long long qq_cs,
+                  hipStream_t stream) {
+    const long long n2 = 2 * (long long)m;
+    IRH_CHECK(hipMemsetAsync(P.head.p, 0, 5 * sizeof(long long), stream));
+    hipLaunchKernelGGL(k_cyc_emit, dim3(grid_of(m)), dim3(kT), 0, stream, (long long)m, (long long)n_total,
+                       reinterpret_cast<const int2 *>(I), P.kin.p, P.vin.p, P.head.p);
     IRH_CHECK(hipGetLastError());
-    if (triangles) {
-        IRH_CHECK(rocprim::radix_sort_pairs(tmp.p, bytes, kin.p, kout.p, vin.p, vout.p, (size_t)n2, 0u, bits, stream));
-        const double2 *qq = reinterpret_cast<const double2 *>(A.QQ);
-        if (!own_rows) {
-            hipLaunchKernelGGL(k_cyc_image, dim3(grid_of(m)), dim3(kT), 0, stream, (long long)m, A.QQ, A.qq_rs, A.qq_cs, img.p);
-            IRH_CHECK(hipGetLastError());
-            qq = img.p;
-        }
-        switch (G) {
-        case 8: launch_triangles<8>((int)nwg, stream, (int)m, n2, kout.p, vout.p, I2, qq, threshold, head.p, A, parts.p); break;
-        case 32: launch_triangles<32>((int)nwg, stream, (int)m, n2, kout.p, vout.p, I2, qq, threshold, head.p, A, parts.p); break;
-        case 64: launch_triangles<64>((int)nwg, stream, (int)m, n2, kout.p, vout.p, I2, qq, threshold, head.p, A, parts.p); break;
-        default: launch_triangles<16>((int)nwg, stream, (int)m, n2, kout.p, vout.p, I2, qq, threshold, head.p, A, parts.p);
-        }
+    if (!P.sort) return;
+    IRH_CHECK(rocprim::radix_sort_pairs(P.tmp.p, P.bytes, P.kin.p, P.kout.p, P.vin.p, P.vout.p, (size_t)n2, 0u, P.bits, stream));
+    P.qq = reinterpret_cast<const double2 *>(QQ);
+    if (!P.own_rows) {
+        hipLaunchKernelGGL(k_cyc_image, dim3(grid_of(m)), dim3(kT), 0, stream, (long long)m, QQ, qq_rs, qq_cs, P.img.p);
         IRH_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_cyc_summary, dim3(1), dim3(kT), 0, stream, (int)nwg, parts.p, head.p);
+        P.qq = P.img.p;
+    }
+}
+
+int cyc_finish(CycPrep &P, int nparts, const long long *parts, int64_t *summary, hipStream_t stream) {
+    if (nparts > 0) {
+        hipLaunchKernelGGL(k_cyc_summary, dim3(1), dim3(kT), 0, stream, nparts, parts, P.head.p);
         IRH_CHECK(hipGetLastError());
     }
     long long h[5] = {0, 0, 0, 0, 0};
-    IRH_CHECK(hipMemcpyAsync(h, head.p, sizeof(h), hipMemcpyDeviceToHost, stream));
+    IRH_CHECK(hipMemcpyAsync(h, P.head.p, sizeof(h), hipMemcpyDeviceToHost, stream));
     IRH_CHECK(hipStreamSynchronize(stream));  // (the temporaries go back to the pool idle)
     if (h[0] != 0) return IROTAVG_ERR_BAD_ARG;
     if (summary)
         for (int j = 0; j < 4; j++) summary[j] = h[1 + j];
     return IROTAVG_OK;
+}
+
+int cycle_check_dev(int64_t m, int64_t n_total, const CycleArrays &A, double threshold, int64_t *summary, hipStream_t stream) {
+    const long long n2 = 2 * (long long)m;
+    const bool triangles = A.tri_count || A.tri_ok || A.tri_min || summary;
+    const int G = g_group.load();
+    // the workgroups of the triangle kernel: kCycPasses passes each while the graph is small, then longer chunks
+    long long nwg = std::max<long long>(1, (m + (long long)(kT / G) * kCycPasses - 1) / ((long long)(kT / G) * kCycPasses));
+    if (nwg > 8) nwg = std::min<long long>(kCycMaxGrid, (nwg + 7) / 8 * 8);
+    // every temporary first (the pool): nothing after the first launch can fail for want of memory
+    CycPrep P;
+    DevBuf<long long> parts;
+    cyc_prep_alloc(P, m, n_total, A.QQ, A.qq_rs, A.qq_cs, triangles, stream);
+    if (triangles) parts.alloc(4 * (size_t)nwg);
+    cyc_prep_run(P, m, n_total, A.I, A.QQ, A.qq_rs, A.qq_cs, stream);
+    if (triangles) {
+        const int2 *I2 = reinterpret_cast<const int2 *>(A.I);
+        switch (G) {
+        case 8: launch_triangles<8>((int)nwg, stream, (int)m, n2, P.kout.p, P.vout.p, I2, P.qq, threshold, P.head.p, A, parts.p); break;
+        case 32: launch_triangles<32>((int)nwg, stream, (int)m, n2, P.kout.p, P.vout.p, I2, P.qq, threshold, P.head.p, A, parts.p); break;
+        case 64: launch_triangles<64>((int)nwg, stream, (int)m, n2, P.kout.p, P.vout.p, I2, P.qq, threshold, P.head.p, A, parts.p); break;
+        default: launch_triangles<16>((int)nwg, stream, (int)m, n2, P.kout.p, P.vout.p, I2, P.qq, threshold, P.head.p, A, parts.p);
+        }
+        IRH_CHECK(hipGetLastError());
+    }
+    return cyc_finish(P, triangles ? (int)nwg : 0, parts.p, summary, stream);
 }
 
 int cycle_check_host(int64_t m, int64_t n_total, const CycleArrays &A, double threshold, int64_t *summary) {

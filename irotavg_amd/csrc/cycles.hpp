@@ -72,12 +72,12 @@ IRH_CYC_HD CycQ cyc_directed(CycQ q, bool against) {
     if (against) q.w = -q.w;
     return q;
 }
-// q0 = q(k, a -> b), q1 = q(k1, b -> c), q2 = q(k2, c -> a); the angle wrapped as edge_log wraps it
-IRH_CYC_HD double cyc_triangle_error(const CycQ q0, const CycQ q1, const CycQ q2) {
+// the angle of a composed rotation d, wrapped as edge_log wraps it, in absolute value: the tail of every cycle error
+// (the triangle's below, the quadrilateral's in cycles4.hpp)
+IRH_CYC_HD double cyc_angle_error(const CycQ d) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-    const CycQ d = cyc_qmul(q2, cyc_qmul(q1, q0));
     const double s = sqrt(d.x * d.x + d.y * d.y + d.z * d.z);
     double th = 2.0 * atan2(s, d.w);
     if (th < -CYC_PI)
@@ -85,6 +85,10 @@ IRH_CYC_HD double cyc_triangle_error(const CycQ q0, const CycQ q1, const CycQ q2
     else if (th >= CYC_PI)
         th -= 2.0 * CYC_PI;
     return fabs(th);
+}
+// q0 = q(k, a -> b), q1 = q(k1, b -> c), q2 = q(k2, c -> a)
+IRH_CYC_HD double cyc_triangle_error(const CycQ q0, const CycQ q1, const CycQ q2) {
+    return cyc_angle_error(cyc_qmul(q2, cyc_qmul(q1, q0)));
 }
 
 struct CycAcc {
@@ -179,11 +183,8 @@ inline int cyc_begin(int64_t m, int64_t n_total, const int32_t *I, CycResult &R)
     return CYC_OK;
 }
 
-// The kernels' way on one thread: emit, sort, and per edge the two rows, the shorter one dealt to `group` lanes that each
-// keep their own sums, merged at the end. I: m pairs, qq: m rows [x y z w].
-inline int cycles_sorted(int64_t m, int64_t n_total, const int32_t *I, const double *qq, double threshold, int group,
-                         CycResult &R) {
-    if (cyc_begin(m, n_total, I, R) != CYC_OK) return CYC_BAD_ID;
+// emit and sort on one thread: the 2m half-edges of valid ids, ordered as the device's radix sort orders them
+inline void cyc_sorted_halves(int64_t m, int64_t n_total, const int32_t *I, std::vector<uint64_t> &keys, std::vector<uint32_t> &vals) {
     std::vector<std::pair<uint64_t, uint32_t>> half((size_t)(2 * m));
     for (int64_t k = 0; k < m; k++) {
         uint64_t key[2];
@@ -196,9 +197,19 @@ inline int cycles_sorted(int64_t m, int64_t n_total, const int32_t *I, const dou
     std::stable_sort(half.begin(), half.end(), [mask](const std::pair<uint64_t, uint32_t> &p, const std::pair<uint64_t, uint32_t> &q) {
         return (p.first & mask) < (q.first & mask);  // (what a radix sort of that many bits sees)
     });
-    std::vector<uint64_t> keys(half.size());
-    std::vector<uint32_t> vals(half.size());
+    keys.resize(half.size());
+    vals.resize(half.size());
     for (size_t t = 0; t < half.size(); t++) keys[t] = half[t].first, vals[t] = half[t].second;
+}
+
+// The kernels' way on one thread: emit, sort, and per edge the two rows, the shorter one dealt to `group` lanes that each
+// keep their own sums, merged at the end. I: m pairs, qq: m rows [x y z w].
+inline int cycles_sorted(int64_t m, int64_t n_total, const int32_t *I, const double *qq, double threshold, int group,
+                         CycResult &R) {
+    if (cyc_begin(m, n_total, I, R) != CYC_OK) return CYC_BAD_ID;
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> vals;
+    cyc_sorted_halves(m, n_total, I, keys, vals);
     const long long n2 = (long long)keys.size();
     const CycAosLoad load{qq};
     for (int64_t k = 0; k < m; k++) {

@@ -541,12 +541,53 @@ int irotavg_cycle_check_dev(int64_t m, int64_t n_total, const int32_t *I_dev, co
 
 int irotavg_cycle_check_group(int lanes) { return cycle_check_group(lanes); }
 
+// The four-cycle test of the edges listed (docs/cycle_check.md, "Four-cycles"; the kernels: cycles4.hip): the triangle
+// test's checks, and those of the subset.
+static bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+static bool subset_ok(int64_t m, int64_t ne, const int32_t *edges) {
+    return ne >= 0 && ne <= 0x7fffffffLL && (edges || ne == m) && aligned4(edges);
+}
+
+int irotavg_cycle_check4(int64_t m, int64_t n_total, const int32_t *I, const double *QQ, int64_t ldqq, double threshold,
+                         int64_t ne, const int32_t *edges, int32_t *quad_count, int32_t *quad_ok, double *quad_min,
+                         int64_t summary[4]) {
+    if (!I || !QQ || !cycle_sizes_ok(m, n_total, threshold) || ldqq < m || !subset_ok(m, ne, edges)) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        const Cycle4Arrays A{I, QQ, 1, (long long)ldqq, edges, quad_count, quad_ok, quad_min};
+        return cycle_check4_host(m, n_total, A, threshold, ne, summary);
+    });
+}
+
+int irotavg_cycle_check4_dev(int64_t m, int64_t n_total, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                             int64_t qq_cs, double threshold, int64_t ne, const int32_t *edges_dev, int32_t *quad_count_dev,
+                             int32_t *quad_ok_dev, double *quad_min_dev, int64_t summary[4], void *stream) {
+    if (!I_dev || !QQ_dev || !cycle_sizes_ok(m, n_total, threshold) || !strides_ok(m, 4, qq_rs, qq_cs) ||
+        !subset_ok(m, ne, edges_dev))
+        return IROTAVG_ERR_BAD_ARG;
+    if (!aligned8(I_dev) || !aligned8(QQ_dev) || !aligned8(quad_min_dev) || !aligned4(quad_count_dev) || !aligned4(quad_ok_dev))
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!dev_index_ok(I_dev, m, device) || !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device)) return IROTAVG_ERR_BAD_ARG;
+        const int32_t *const per_entry[3] = {edges_dev, quad_count_dev, quad_ok_dev};
+        for (const int32_t *p : per_entry)
+            if (p && ne > 0 && !dev_span_ok(p, p + ne - 1, device)) return IROTAVG_ERR_BAD_ARG;
+        if (quad_min_dev && ne > 0 && !dev_vector_ok(quad_min_dev, ne, device)) return IROTAVG_ERR_BAD_ARG;
+        const Cycle4Arrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, edges_dev, quad_count_dev, quad_ok_dev, quad_min_dev};
+        return cycle_check4_dev(m, n_total, A, threshold, ne, summary, static_cast<hipStream_t>(stream));
+    });
+}
+
+int irotavg_cycle_check4_group(int lanes) { return cycle_check4_group(lanes); }
+
 // The order-free spanning-tree initialiser (docs/init_tree.md; the kernels: treeinit.hip). Handle-free; the device form runs
 // on the caller's stream itself, as the cycle check does.
 static bool tree_sizes_ok(int64_t m, int64_t n_total, int f) {
     return m > 0 && m <= 0x7fffffffLL && n_total > 0 && n_total <= 0x7fffffffLL && f >= 1 && f <= n_total;
 }
-static bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 int irotavg_init_tree(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, const int32_t *rank,
                       double *Q, int64_t ldq, int32_t *in_tree, int64_t info[4]) {

@@ -342,6 +342,40 @@ int cycle_check_dev(int64_t m, int64_t n_total, const CycleArrays &A, double thr
                     hipStream_t stream);
 int cycle_check_host(int64_t m, int64_t n_total, const CycleArrays &A, double threshold, int64_t *summary);
 int cycle_check_group(int lanes);  // irotavg_cycle_check_group
+// cycles.hip: what the triangle test and the four-cycle test (cycles4.hip) share. cyc_prep_alloc takes every temporary from
+// the pool; cyc_prep_run clears head (the error word and the four sums), range-checks and emits the half-edges and, with
+// `sort`, sorts them into kout / vout and leaves QQ as 16-byte rows behind qq; cyc_finish adds the workgroups' sums
+// (nparts > 0: k_cyc_summary), reads head back, waits, and returns IROTAVG_ERR_BAD_ARG when the error word is set.
+struct CycPrep {
+    DevBuf<uint64_t> kin, kout;
+    DevBuf<uint32_t> vin, vout;
+    DevBuf<char> tmp;
+    DevBuf<double2> img;
+    DevBuf<long long> head;
+    size_t bytes = 0;
+    unsigned bits = 0;
+    bool sort = false, own_rows = false;
+    const double2 *qq = nullptr;
+};
+void cyc_prep_alloc(CycPrep &P, int64_t m, int64_t n_total, const double *QQ, long long qq_rs, long long qq_cs, bool sort,
+                    hipStream_t stream);
+void cyc_prep_run(CycPrep &P, int64_t m, int64_t n_total, const int32_t *I, const double *QQ, long long qq_rs, long long qq_cs,
+                  hipStream_t stream);
+int cyc_finish(CycPrep &P, int nparts, const long long *parts, int64_t *summary /* host */, hipStream_t stream);
+// cycles4.hip: the four-cycle test of the edges listed (irotavg_cycle_check4[_dev]; docs/cycle_check.md, "Four-cycles").
+// The arguments have been checked; forms, blocking and nullptr outputs as cycle_check_dev / cycle_check_host.
+struct Cycle4Arrays {
+    const int32_t *I;  // m pairs
+    const double *QQ;  // strided m x 4 (device form) / column-major with qq_cs = ldqq, qq_rs = 1 (host form)
+    long long qq_rs, qq_cs;
+    const int32_t *edges;  // ne edge ids, or nullptr: all m edges in order
+    int32_t *quad_count, *quad_ok;  // ne each
+    double *quad_min;
+};
+int cycle_check4_dev(int64_t m, int64_t n_total, const Cycle4Arrays &A, double threshold, int64_t ne, int64_t *summary /* host */,
+                     hipStream_t stream);
+int cycle_check4_host(int64_t m, int64_t n_total, const Cycle4Arrays &A, double threshold, int64_t ne, int64_t *summary);
+int cycle_check4_group(int lanes);  // irotavg_cycle_check4_group
 // treeinit.hip: the order-free spanning-tree initialiser (irotavg_init_tree[_dev]; docs/init_tree.md). The arguments have
 // been checked. The device form runs on `stream`, reads row 0 of Q and writes the rows from f on; the host form uploads,
 // runs the same kernels and copies those rows back. Both block until the status and info are back; rank, in_tree and info

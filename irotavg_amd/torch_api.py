@@ -170,6 +170,11 @@ class TorchGraph(capi.Graph):
         _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
         return cycle_check(edge_index, QQ, self.n_total, threshold, **kw)
 
+    def cycle_check4(self, edge_index, QQ, threshold=5 * 3.141592653589793 / 180, edges=None, **kw):
+        """cycle_check4 (below) of the tensors passed, with the handle's n_total, as cycle_check above."""
+        _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
+        return cycle_check4(edge_index, QQ, self.n_total, threshold, edges, **kw)
+
     def init_tree(self, edge_index, QQ, rank=None, **kw):
         """init_tree (below) of the tensors passed with the handle's n_total and f, then set_rotations: the handle starts
         from the tree's rotations without a host round trip. The anchor Q[0] and the other fixed rows are the identity.
@@ -437,6 +442,58 @@ def cycle_check(edge_index, QQ, n_total, threshold=5 * 3.141592653589793 / 180, 
     _allowed(rc, "irotavg_cycle_check_dev", allow_rc)
     return dict(rc=rc, tri_count=outs[0], tri_ok=outs[1], tri_min=outs[2],
                 summary=dict(zip(capi.SUMMARY_FIELDS, (int(v) for v in s))) if summary and rc == capi.OK else None)
+
+
+# ---- the four-cycle test of the edges no triangle tests (irotavg_cycle_check4_dev, docs/cycle_check.md) ----------------------
+def cycle_check4(edge_index, QQ, n_total, threshold=5 * 3.141592653589793 / 180, edges=None, count=True, ok=True,
+                 min_err=True, summary=True, allow_rc=()):
+    """The four-cycle test on torch's current stream: for every edge listed the quadrilaterals it closes with three other
+    edges, how many of them are consistent within `threshold` radians, and the smallest inconsistency. It reaches the loop
+    closures that close no triangle; the usual subset is `torch.nonzero(tri_count == 0).flatten()` of cycle_check.
+
+    edge_index, QQ, n_total, threshold: as cycle_check. edges: None (all m edges in order) or a 1-D int32 or int64 tensor
+    of ne edge ids in any order, duplicates allowed (narrowed on the device: a value outside int32 range becomes an id the
+    device check refuses). count / ok / min_err: True (a new tensor), False / None (not computed), or a contiguous tensor
+    of ne entries to fill (int32 for the counts, float64 for min_err); entry t belongs to edges[t]. Returns dict(rc,
+    quad_count, quad_ok, quad_min, summary); summary is a host dict of capi.SUMMARY4_FIELDS, or None. A view id outside
+    [0, n_total) or an edge id outside [0, m) gives ERR_BAD_ARG with every output byte as it was; anything but OK raises
+    unless listed in allow_rc. The call blocks until the summary is back."""
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), placed=False)
+    m = int(edge_index.shape[0])
+    _check(QQ, "QQ", (torch.float64,), (m, 4), placed=False)
+    if edges is not None:
+        _check(edges, "edges", (torch.int32, torch.int64), (None,), placed=False)
+    ne = m if edges is None else int(edges.shape[0])
+    wants = (("count", count, torch.int32), ("ok", ok, torch.int32), ("min_err", min_err, torch.float64))
+    for name, want, dt in wants:
+        if not (want is True or want is False or want is None):
+            _check(want, name, (dt,), (ne,), placed=False)
+    n_total, threshold = int(n_total), float(threshold)
+    if m < 1:
+        raise ValueError("edge_index must have at least one row")
+    if ne < 1:
+        raise ValueError("edges must have at least one entry")
+    if not 0 < n_total <= INT32_MAX:
+        raise ValueError("n_total must lie in [1, 2^31 - 1], got %d" % n_total)
+    if not threshold >= 0.0:
+        raise ValueError("threshold must be a non-negative angle, got %r" % threshold)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (m, 4), device)
+    if edges is not None:
+        _check(edges, "edges", (torch.int32, torch.int64), (None,), device)
+    outs = [_output(want, name, ne, device, dt) for name, want, dt in wants]
+    s = (C.c_int64 * 4)(-1, -1, -1, -1)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        sub = None if edges is None else _narrow(edges)
+        rc = capi.lib().irotavg_cycle_check4_dev(m, n_total, _ptr(ei), _ptr(QQ), *matrix_strides(QQ), threshold, ne,
+                                                 None if sub is None else _ptr(sub),
+                                                 *[None if t is None else _ptr(t) for t in outs], s if summary else None,
+                                                 _stream(device))
+    _allowed(rc, "irotavg_cycle_check4_dev", allow_rc)
+    return dict(rc=rc, quad_count=outs[0], quad_ok=outs[1], quad_min=outs[2],
+                summary=dict(zip(capi.SUMMARY4_FIELDS, (int(v) for v in s))) if summary and rc == capi.OK else None)
 
 
 # ---- the order-free spanning-tree initialiser (irotavg_init_tree_dev, docs/init_tree.md) ----------------------------------

@@ -9,6 +9,9 @@ on the same graph as context. `--groups` adds the device-array call at every gro
 
     python tools/time_cycle_check.py                      # the three documented cases
     python tools/time_cycle_check.py --cases band --groups
+    python tools/time_cycle_check.py --quads --groups     # the four-cycle test (irotavg_cycle_check4_dev), same protocol
+
+Run each case under a time limit of its own (`timeout`): one case per invocation, `--cases NAME` or `--quads NAME`.
 """
 import argparse
 import ctypes as C
@@ -30,8 +33,99 @@ def stats(ms):
     return dict(median_ms=round(ms[len(ms) // 2], 4), min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4), reps=len(ms))
 
 
+def paired_loops(S, share, seed):
+    """S (band-only) with `share` of its edge count added as loop closures in pairs (a, b), (a + 1, b + 1): the cluster
+    a place-recognition match comes in, whose quadrilateral with two sequence edges tests both. Noise-free closures."""
+    from irotavg_amd import synth
+    rng = np.random.default_rng([seed, 4])
+    n, pairs = S["n"], int(round(share * len(S["I"]) / 2))
+    a = rng.integers(0, n - 1, size=pairs)
+    b = (a + rng.integers(n // 4, 3 * n // 4, size=pairs)) % (n - 1)
+    I = np.concatenate([S["I"], np.stack([a, b], 1), np.stack([a + 1, b + 1], 1)]).astype(np.int32)
+    extra = I[len(S["I"]):]
+    return I, np.concatenate([S["QQ"], synth.qmul(S["Qgt"][extra[:, 1]], synth.qconj(S["Qgt"][extra[:, 0]]))])
+
+
+def quads(args):
+    """--quads: the four-cycle test (a) of the untested subset of a 100k / 2M band graph with 2 % paired loop edges, next
+    to the triangle test of the whole graph, (b) of all edges of the band graph, (c) at every sub-group width."""
+    import torch
+    from irotavg_amd import capi, synth
+    L = capi.lib()
+    if L.irotavg_device_count() <= 0:
+        raise SystemExit("no HIP device: the product has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = dict(tool="time_cycle_check --quads", device=torch.cuda.get_device_name(dev), threshold=args.threshold,
+               default_group=capi.cycle_check4_group(0), cases=[])
+    n, m_ask = args.quads_size
+    S = synth.make_graph(n, m_ask, 0.0, seed=args.seed)
+    for name in args.quads.split(","):
+        I, QQ = paired_loops(S, 0.02, args.seed) if name == "paired" else (np.ascontiguousarray(S["I"], dtype=np.int32), S["QQ"])
+        m = len(I)
+        ei, qq = torch.tensor(I, device=dev), torch.tensor(np.ascontiguousarray(QQ), dtype=torch.float64, device=dev)
+        tri = [torch.zeros(m, dtype=torch.int32, device=dev), torch.zeros(m, dtype=torch.int32, device=dev),
+               torch.zeros(m, dtype=torch.float64, device=dev)]
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ts, qs = (C.c_int64 * 4)(), (C.c_int64 * 4)()
+
+        def tri_call():
+            t = time.perf_counter()
+            rc = L.irotavg_cycle_check_dev(m, n, C.c_void_p(ei.data_ptr()), C.c_void_p(qq.data_ptr()), 4, 1, args.threshold,
+                                           *[C.c_void_p(x.data_ptr()) for x in tri], ts, stream)
+            dt = time.perf_counter() - t   # (the call blocks until the summary is back)
+            capi.check(rc, "irotavg_cycle_check_dev")
+            return 1e3 * dt
+
+        tri_call()
+        sub = torch.nonzero(tri[0] == 0).flatten().to(torch.int32) if name == "paired" else None
+        ne = m if sub is None else int(sub.shape[0])
+        quad = [torch.zeros(ne, dtype=torch.int32, device=dev), torch.zeros(ne, dtype=torch.int32, device=dev),
+                torch.zeros(ne, dtype=torch.float64, device=dev)]
+
+        def quad_call():
+            t = time.perf_counter()
+            rc = L.irotavg_cycle_check4_dev(m, n, C.c_void_p(ei.data_ptr()), C.c_void_p(qq.data_ptr()), 4, 1, args.threshold, ne,
+                                            None if sub is None else C.c_void_p(sub.data_ptr()),
+                                            *[C.c_void_p(x.data_ptr()) for x in quad], qs, stream)
+            dt = time.perf_counter() - t
+            capi.check(rc, "irotavg_cycle_check4_dev")
+            return 1e3 * dt
+
+        for _ in range(args.warmup):
+            quad_call()
+            tri_call()
+        tq, tt = [], []
+        for _ in range(args.reps):
+            tq.append(quad_call())
+            tt.append(tri_call())
+        h = capi.cycle_check4(I, QQ, n, args.threshold, None if sub is None else sub.cpu().numpy())
+        equal = bool(all(h[k].tobytes() == x.cpu().numpy().tobytes() for k, x in zip(("quad_count", "quad_ok", "quad_min"), quad))
+                     and list(h["summary"].values()) == list(qs))
+        row = dict(case=name, views=n, edges=m, tested=ne, quads=stats(tq), triangles_whole_graph=stats(tt), bitwise_equal=equal,
+                   summary=dict(zip(capi.SUMMARY4_FIELDS, (int(v) for v in qs))))
+        row["quadrilaterals_per_s"] = round(row["summary"]["quadrilaterals"] / (1e-3 * row["quads"]["median_ms"]), 1)
+        row["share_supported"] = round(row["summary"]["supported"] / ne, 4)
+        row["quads_over_triangles_median"] = round(row["quads"]["median_ms"] / row["triangles_whole_graph"]["median_ms"], 4)
+        if args.groups:
+            row["groups"] = {}
+            for g in (8, 16, 32, 64):
+                old = capi.cycle_check4_group(g)
+                try:
+                    for _ in range(args.warmup):
+                        quad_call()
+                    row["groups"][str(g)] = stats([quad_call() for _ in range(args.reps)])
+                finally:
+                    capi.cycle_check4_group(old)
+        out["cases"].append(row)
+        del ei, qq, tri, quad, sub
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--quads", nargs="?", const="paired,band", default=None,
+                    help="time the four-cycle test instead: comma-separated names of paired, band (default both)")
+    ap.add_argument("--quads-size", type=int, nargs=2, default=(100000, 2000000), metavar=("VIEWS", "EDGES"))
     ap.add_argument("--cases", default="band,loops,large", help="comma-separated names of %s" % sorted(CASES))
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
@@ -42,6 +136,8 @@ def main():
     args = ap.parse_args()
     if args.reps < 7:
         ap.error("--reps must be at least 7")
+    if args.quads:
+        return quads(args)
     import torch
     from irotavg_amd import capi, ral, synth
     L = capi.lib()
