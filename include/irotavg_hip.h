@@ -556,6 +556,31 @@ int irotavg_cycle_check4_dev(int64_t m, int64_t n_total, const int32_t *I_dev, c
  * the width in force before the call, IROTAVG_ERR_BAD_ARG for any other value. */
 int irotavg_cycle_check4_group(int lanes);
 
+/* A corruption estimate for every edge by cycle-edge message passing over the triangles of irotavg_cycle_check
+ * (docs/cycle_check.md, "Corruption estimates"): no poses, no fixed views, no solver, any topology. A triangle is USED when
+ * its error d is finite; U(k) are the used triangles of edge k in the order of the sorted half-edges. s0[k] is the mean of
+ * d over U(k). Iteration t = 0 .. iters-1 (Jacobi): for a triangle (k1, k2) of k, e = s[k1] + s[k2], mu the smallest e over
+ * U(k) (NaN ignored), w = exp(-beta[t] (e - mu)), s'[k] = sum w d / sum w over U(k), a term with a NaN weight left out. An
+ * edge without a used triangle, or with every term left out, gets NaN. Inputs as irotavg_cycle_check (no threshold), and
+ *   iters, beta   0 <= iters <= 64; beta: iters doubles on the HOST, each finite and >= 0, in 1/rad (NULL with iters == 0)
+ *   max_records   a cap on the used triangles of all edges together (16 bytes each are kept), 0: none
+ *   s             m doubles or NULL: the estimate in radians after the last iteration, NaN: no used triangle
+ *   tri_used      m int32 or NULL: |U(k)| (a count above 2^31 - 1 is stored as 2^31 - 1)
+ *   summary       2 int64 on the HOST or NULL: the used triangles of all edges (exact); edges without one
+ * Errors and write rules are those of irotavg_cycle_check; in addition iters outside [0, 64], beta NULL with iters > 0, a
+ * beta[t] that is NaN, infinite or negative, or max_records < 0 is IROTAVG_ERR_BAD_ARG before any device work. More used
+ * triangles than max_records > 0: IROTAVG_ERR_NOMEM, s and tri_used untouched, summary WRITTEN (the number that was needed).
+ * A table that cannot be allocated: IROTAVG_ERR_NOMEM. With every output NULL the call is the id check. Memory is O(m) plus
+ * 16 bytes per used triangle. Deterministic: two calls give the same bytes. */
+int irotavg_cycle_cemp(int64_t m, int64_t n_total, const int32_t *I, const double *QQ, int64_t ldqq, int iters,
+                       const double *beta, int64_t max_records, double *s, int32_t *tri_used, int64_t summary[2]);
+/* The same on arrays that live on the device, under the rules of irotavg_cycle_check_dev: s_dev 8-byte and tri_used_dev
+ * 4-byte aligned, the lowest and highest element of every array device memory of the current device; beta stays on the
+ * host. The kernels go on `stream` itself; the call blocks until the outputs are written. */
+int irotavg_cycle_cemp_dev(int64_t m, int64_t n_total, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                           int64_t qq_cs, int iters, const double *beta, int64_t max_records, double *s_dev,
+                           int32_t *tri_used_dev, int64_t summary[2] /* HOST */, void *stream);
+
 /* An order-free spanning-tree initialiser, a second one next to irotavg_init_mst (docs/init_tree.md): the tree is the
  * minimum spanning forest under the keys (rank[k], k), ordered lexicographically -- distinct, so the forest is unique and
  * depends on no launch geometry; k alone decides between parallel and reversed duplicates. T(0) = Q[0];

@@ -54,6 +54,7 @@ SYMBOLS = [
     "irotavg_cycle_check", "irotavg_cycle_check_dev", "irotavg_cycle_check_group",
     "irotavg_cycle_check4", "irotavg_cycle_check4_dev", "irotavg_cycle_check4_group",
     "irotavg_init_tree", "irotavg_init_tree_dev", "irotavg_init_tree_counters",
+    "irotavg_cycle_cemp", "irotavg_cycle_cemp_dev",
 ]
 
 
@@ -194,6 +195,9 @@ def lib():
     L.irotavg_cycle_check4_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, C.c_int64, vp, vp,
                                            vp, vp, _i64p, vp]
     L.irotavg_cycle_check4_group.argtypes = [C.c_int]
+    L.irotavg_cycle_cemp.argtypes = [C.c_int64, C.c_int64, _ip, _dp, C.c_int64, C.c_int, _dp, C.c_int64, _dp, _ip, _i64p]
+    L.irotavg_cycle_cemp_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int, _dp, C.c_int64, vp, vp,
+                                         _i64p, vp]
     L.irotavg_init_tree.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _ip, _dp, C.c_int64, _ip, _i64p]
     L.irotavg_init_tree_dev.argtypes = [C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64,
                                         C.c_int64, vp, _i64p, vp]
@@ -757,6 +761,42 @@ def cycle_check4_group(lanes):
     if old < 0:
         raise IrotavgError(old, "irotavg_cycle_check4_group")
     return old
+
+
+CEMP_SUMMARY_FIELDS = ("records", "untested")
+
+
+def cemp_schedule(beta):
+    """beta of cycle_cemp as a float64 array of at most 64 finite, non-negative entries (ValueError otherwise)."""
+    b = np.ascontiguousarray(beta, dtype=np.float64)
+    if b.ndim != 1 or len(b) > 64:
+        raise ValueError("beta must be one-dimensional with at most 64 entries")
+    if not (np.isfinite(b) & (b >= 0)).all():
+        raise ValueError("every beta must be finite and non-negative")
+    return b
+
+
+def cycle_cemp(I, QQ, n_total, beta, max_records=0, s=True, used=True, summary=True, allow_rc=()):
+    """irotavg_cycle_cemp (docs/cycle_check.md, "Corruption estimates"): len(beta) iterations of cycle-edge message passing
+    over the triangles of every edge. Returns dict(rc, s (float64, m, radians; NaN: no used triangle), tri_used (int32, m),
+    summary (dict of CEMP_SUMMARY_FIELDS; also with ERR_NOMEM from max_records)); an output that was not asked for is None.
+    s is preset to -1 and tri_used to -1, and written only on success."""
+    I = edges(I)
+    QQ = fmat(QQ)
+    m = len(I)
+    if QQ.shape != (m, 4):
+        raise ValueError("QQ must be (%d, 4)" % m)
+    b = cemp_schedule(beta)
+    sv = np.full(m, -1.0) if s else None
+    cnt = np.full(m, -1, dtype=np.int32) if used else None
+    h = (C.c_int64 * 2)(-1, -1)
+    rc = lib().irotavg_cycle_cemp(m, int(n_total), _i(I), _d(QQ), QQ.shape[0], len(b), _d(b) if len(b) else None,
+                                  int(max_records), None if sv is None else _d(sv), None if cnt is None else _i(cnt),
+                                  h if summary else None)
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_cycle_cemp")
+    return dict(rc=rc, s=sv, tri_used=cnt,
+                summary=dict(zip(CEMP_SUMMARY_FIELDS, (int(v) for v in h))) if summary and h[0] >= 0 else None)
 
 
 INFO_FIELDS = ("rounds", "components", "ranked_edges", "max_rank")

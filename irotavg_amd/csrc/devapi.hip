@@ -583,6 +583,44 @@ int irotavg_cycle_check4_dev(int64_t m, int64_t n_total, const int32_t *I_dev, c
 
 int irotavg_cycle_check4_group(int lanes) { return cycle_check4_group(lanes); }
 
+// A corruption estimate for every edge (docs/cycle_check.md, "Corruption estimates"; the kernels: cemp.hip): the triangle
+// test's checks without a threshold, and those of the schedule and the cap.
+static bool cemp_args_ok(int iters, const double *beta, int64_t max_records) {
+    if (iters < 0 || iters > 64 || (iters > 0 && !beta) || max_records < 0) return false;
+    for (int t = 0; t < iters; t++)
+        if (!(beta[t] >= 0.0) || beta[t] > std::numeric_limits<double>::max()) return false;  // (NaN: false)
+    return true;
+}
+
+int irotavg_cycle_cemp(int64_t m, int64_t n_total, const int32_t *I, const double *QQ, int64_t ldqq, int iters,
+                       const double *beta, int64_t max_records, double *s, int32_t *tri_used, int64_t summary[2]) {
+    if (!I || !QQ || !cycle_sizes_ok(m, n_total, 0.0) || ldqq < m || !cemp_args_ok(iters, beta, max_records)) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        const CempArrays A{I, QQ, 1, (long long)ldqq, s, tri_used};
+        return cycle_cemp_host(m, n_total, A, iters, beta, max_records, summary);
+    });
+}
+
+int irotavg_cycle_cemp_dev(int64_t m, int64_t n_total, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs, int64_t qq_cs,
+                           int iters, const double *beta, int64_t max_records, double *s_dev, int32_t *tri_used_dev,
+                           int64_t summary[2], void *stream) {
+    if (!I_dev || !QQ_dev || !cycle_sizes_ok(m, n_total, 0.0) || !strides_ok(m, 4, qq_rs, qq_cs) ||
+        !cemp_args_ok(iters, beta, max_records))
+        return IROTAVG_ERR_BAD_ARG;
+    if (!aligned8(I_dev) || !aligned8(QQ_dev) || !aligned8(s_dev) || !aligned4(tri_used_dev)) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!dev_index_ok(I_dev, m, device) || !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device)) return IROTAVG_ERR_BAD_ARG;
+        if (s_dev && !dev_vector_ok(s_dev, m, device)) return IROTAVG_ERR_BAD_ARG;
+        if (tri_used_dev && !dev_span_ok(tri_used_dev, tri_used_dev + m - 1, device)) return IROTAVG_ERR_BAD_ARG;
+        const CempArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, s_dev, tri_used_dev};
+        return cycle_cemp_dev(m, n_total, A, iters, beta, max_records, summary, static_cast<hipStream_t>(stream));
+    });
+}
+
 // The order-free spanning-tree initialiser (docs/init_tree.md; the kernels: treeinit.hip). Handle-free; the device form runs
 // on the caller's stream itself, as the cycle check does.
 static bool tree_sizes_ok(int64_t m, int64_t n_total, int f) {

@@ -376,6 +376,21 @@ int cycle_check4_dev(int64_t m, int64_t n_total, const Cycle4Arrays &A, double t
                      hipStream_t stream);
 int cycle_check4_host(int64_t m, int64_t n_total, const Cycle4Arrays &A, double threshold, int64_t ne, int64_t *summary);
 int cycle_check4_group(int lanes);  // irotavg_cycle_check4_group
+// cemp.hip: a corruption estimate for every edge by message passing over its triangles (irotavg_cycle_cemp[_dev];
+// docs/cycle_check.md, "Corruption estimates"). The arguments have been checked (beta: `iters` host doubles); forms and
+// nullptr outputs as cycle_check_dev / cycle_check_host. Both block until the outputs are written. summary (2 entries) is
+// written with IROTAVG_ERR_NOMEM from max_records too, s and tri_used on success alone.
+struct CempArrays {
+    const int32_t *I;  // m pairs
+    const double *QQ;  // strided m x 4 (device form) / column-major with qq_cs = ldqq, qq_rs = 1 (host form)
+    long long qq_rs, qq_cs;
+    double *s;
+    int32_t *tri_used;
+};
+int cycle_cemp_dev(int64_t m, int64_t n_total, const CempArrays &A, int iters, const double *beta, int64_t max_records,
+                   int64_t *summary /* host */, hipStream_t stream);
+int cycle_cemp_host(int64_t m, int64_t n_total, const CempArrays &A, int iters, const double *beta, int64_t max_records,
+                    int64_t *summary);
 // treeinit.hip: the order-free spanning-tree initialiser (irotavg_init_tree[_dev]; docs/init_tree.md). The arguments have
 // been checked. The device form runs on `stream`, reads row 0 of Q and writes the rows from f on; the host form uploads,
 // runs the same kernels and copies those rows back. Both block until the status and info are back; rank, in_tree and info

@@ -175,6 +175,11 @@ class TorchGraph(capi.Graph):
         _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
         return cycle_check4(edge_index, QQ, self.n_total, threshold, edges, **kw)
 
+    def cycle_cemp(self, edge_index, QQ, beta=None, **kw):
+        """cycle_cemp (below) of the tensors passed, with the handle's n_total, as cycle_check above."""
+        _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
+        return cycle_cemp(edge_index, QQ, self.n_total, beta, **kw)
+
     def init_tree(self, edge_index, QQ, rank=None, **kw):
         """init_tree (below) of the tensors passed with the handle's n_total and f, then set_rotations: the handle starts
         from the tree's rotations without a host round trip. The anchor Q[0] and the other fixed rows are the identity.
@@ -494,6 +499,72 @@ def cycle_check4(edge_index, QQ, n_total, threshold=5 * 3.141592653589793 / 180,
     _allowed(rc, "irotavg_cycle_check4_dev", allow_rc)
     return dict(rc=rc, quad_count=outs[0], quad_ok=outs[1], quad_min=outs[2],
                 summary=dict(zip(capi.SUMMARY4_FIELDS, (int(v) for v in s))) if summary and rc == capi.OK else None)
+
+
+# ---- a corruption estimate for every edge (irotavg_cycle_cemp_dev, docs/cycle_check.md, "Corruption estimates") ------------
+def cemp_beta(iters=6, beta0=8.0, rate=2.0):
+    """The default schedule of cycle_cemp: beta0 * rate^t / pi for t = 0 .. iters-1, in 1/rad, as a list of floats."""
+    iters = int(iters)
+    if not 0 <= iters <= 64:
+        raise ValueError("iters must lie in [0, 64], got %d" % iters)
+    return [float(beta0) * float(rate) ** t / 3.141592653589793 for t in range(iters)]
+
+
+def cycle_cemp(edge_index, QQ, n_total, beta=None, max_records=0, s=True, used=True, summary=True, allow_rc=()):
+    """Cycle-edge message passing on torch's current stream: for every edge an estimate, in radians, of how far its
+    measurement is from the truth, from the triangles of cycle_check alone. Each triangle is weighted by how clean its two
+    other edges look (exp(-beta[t] * (sum of their estimates))), an edge's estimate is the weighted mean of its triangle
+    errors, and beta grows from iteration to iteration. No poses, no weights, no fixed views, any topology.
+
+    edge_index, QQ, n_total: as cycle_check. beta: a sequence of at most 64 finite, non-negative floats, one per iteration
+    (None: cemp_beta(); empty: the plain mean of the triangle errors). max_records: a cap on the triangles kept (16 bytes
+    each), 0 for none. s / used: True (a new tensor), False / None (not computed), or a contiguous tensor of m entries to
+    fill (float64 / int32). Returns dict(rc, s, tri_used, summary); s is NaN for an edge without a used triangle; summary is
+    a host dict of capi.CEMP_SUMMARY_FIELDS, or None. More triangles than max_records gives ERR_NOMEM with s and tri_used as
+    they were and summary["records"] the number needed; an id outside [0, n_total) gives ERR_BAD_ARG with every output byte
+    as it was; anything but OK raises unless listed in allow_rc. The call blocks until the outputs are written."""
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), placed=False)
+    m = int(edge_index.shape[0])
+    _check(QQ, "QQ", (torch.float64,), (m, 4), placed=False)
+    wants = (("s", s, torch.float64), ("used", used, torch.int32))
+    for name, want, dt in wants:
+        if not (want is True or want is False or want is None):
+            _check(want, name, (dt,), (m,), placed=False)
+    n_total, max_records = int(n_total), int(max_records)
+    if m < 1:
+        raise ValueError("edge_index must have at least one row")
+    if not 0 < n_total <= INT32_MAX:
+        raise ValueError("n_total must lie in [1, 2^31 - 1], got %d" % n_total)
+    b = capi.cemp_schedule(cemp_beta() if beta is None else beta)
+    if max_records < 0:
+        raise ValueError("max_records must not be negative, got %d" % max_records)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (m, 4), device)
+    outs = [_output(want, name, m, device, dt) for name, want, dt in wants]
+    h = (C.c_int64 * 2)(-1, -1)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        rc = capi.lib().irotavg_cycle_cemp_dev(m, n_total, _ptr(ei), _ptr(QQ), *matrix_strides(QQ), len(b),
+                                               capi._d(b) if len(b) else None, max_records,
+                                               *[None if t is None else _ptr(t) for t in outs], h if summary else None,
+                                               _stream(device))
+    _allowed(rc, "irotavg_cycle_cemp_dev", allow_rc)
+    return dict(rc=rc, s=outs[0], tri_used=outs[1],
+                summary=dict(zip(capi.CEMP_SUMMARY_FIELDS, (int(v) for v in h))) if summary and h[0] >= 0 else None)
+
+
+def rank_from_cemp(s, threshold):
+    """The rank init_tree takes, from the estimates of cycle_cemp, in plain torch on the device: 0 for s <= threshold, 1
+    for NaN (no used triangle), 2 otherwise. Returns an int32 tensor of m entries."""
+    _check(s, "s", (torch.float64,), (None,), placed=False)
+    threshold = float(threshold)
+    if not threshold >= 0.0:
+        raise ValueError("threshold must be a non-negative angle, got %r" % threshold)
+    rank = torch.full(s.shape, 2, dtype=torch.int32, device=s.device)
+    rank[torch.isnan(s)] = 1
+    rank[s <= threshold] = 0
+    return rank
 
 
 # ---- the order-free spanning-tree initialiser (irotavg_init_tree_dev, docs/init_tree.md) ----------------------------------

@@ -10,6 +10,7 @@ on the same graph as context. `--groups` adds the device-array call at every gro
     python tools/time_cycle_check.py                      # the three documented cases
     python tools/time_cycle_check.py --cases band --groups
     python tools/time_cycle_check.py --quads --groups     # the four-cycle test (irotavg_cycle_check4_dev), same protocol
+    python tools/time_cycle_check.py --cemp               # the corruption estimates (irotavg_cycle_cemp_dev), band and loops
 
 Run each case under a time limit of its own (`timeout`): one case per invocation, `--cases NAME` or `--quads NAME`.
 """
@@ -121,8 +122,67 @@ def quads(args):
     print(json.dumps(out))
 
 
+def cemp(args):
+    """--cemp: the corruption estimates (irotavg_cycle_cemp_dev) at six iterations of the default schedule and at none,
+    alternating with the triangle test on the same graph; the time of one iteration is the difference over six."""
+    import torch
+    from irotavg_amd import capi, synth, torch_api
+    L = capi.lib()
+    if L.irotavg_device_count() <= 0:
+        raise SystemExit("no HIP device: the product has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = dict(tool="time_cycle_check --cemp", device=torch.cuda.get_device_name(dev), cases=[])
+    beta = np.array(torch_api.cemp_beta(6))
+    for name in args.cemp.split(","):
+        n, m_ask, p_loop = CASES[name]
+        S = synth.make_graph(n, m_ask, p_loop, seed=args.seed)
+        m = len(S["I"])
+        ei = torch.tensor(np.ascontiguousarray(S["I"], dtype=np.int32), device=dev)
+        qq = torch.tensor(np.ascontiguousarray(S["QQ"]), dtype=torch.float64, device=dev)
+        s, used = torch.zeros(m, dtype=torch.float64, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
+        tri = [torch.zeros(m, dtype=torch.int32, device=dev), torch.zeros(m, dtype=torch.int32, device=dev),
+               torch.zeros(m, dtype=torch.float64, device=dev)]
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        hs, ts = (C.c_int64 * 2)(), (C.c_int64 * 4)()
+        torch.cuda.synchronize()
+
+        def cemp_call(iters):
+            t = time.perf_counter()
+            rc = L.irotavg_cycle_cemp_dev(m, n, C.c_void_p(ei.data_ptr()), C.c_void_p(qq.data_ptr()), 4, 1, iters, capi._d(beta), 0,
+                                          C.c_void_p(s.data_ptr()), C.c_void_p(used.data_ptr()), hs, stream)
+            dt = time.perf_counter() - t   # (the call blocks until the outputs are written)
+            capi.check(rc, "irotavg_cycle_cemp_dev")
+            return 1e3 * dt
+
+        def tri_call():
+            t = time.perf_counter()
+            rc = L.irotavg_cycle_check_dev(m, n, C.c_void_p(ei.data_ptr()), C.c_void_p(qq.data_ptr()), 4, 1, args.threshold,
+                                           *[C.c_void_p(x.data_ptr()) for x in tri], ts, stream)
+            dt = time.perf_counter() - t
+            capi.check(rc, "irotavg_cycle_check_dev")
+            return 1e3 * dt
+
+        t6, t0, tt = [], [], []
+        for rep in range(args.warmup + args.reps):
+            a, b, c = cemp_call(6), cemp_call(0), tri_call()
+            if rep >= args.warmup:
+                t6.append(a), t0.append(b), tt.append(c)
+        row = dict(case=name, views=n, edges=m, p_loop=p_loop, cemp_iters6=stats(t6), cemp_iters0=stats(t0),
+                   per_iteration=stats([(a - b) / 6 for a, b in zip(t6, t0)]), cycle_check=stats(tt),
+                   summary=dict(zip(capi.CEMP_SUMMARY_FIELDS, (int(v) for v in hs))))
+        row["table_bytes"] = 16 * row["summary"]["records"]
+        row["iters6_over_cycle_check_median"] = round(row["cemp_iters6"]["median_ms"] / row["cycle_check"]["median_ms"], 4)
+        row["iteration_over_cycle_check_median"] = round(row["per_iteration"]["median_ms"] / row["cycle_check"]["median_ms"], 4)
+        row["table_gb_per_s_of_an_iteration"] = round(row["table_bytes"] / (1e6 * row["per_iteration"]["median_ms"]), 1)
+        out["cases"].append(row)
+        del ei, qq, s, used, tri
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cemp", nargs="?", const="band,loops", default=None,
+                    help="time the corruption estimates instead: comma-separated names of band, loops (default both)")
     ap.add_argument("--quads", nargs="?", const="paired,band", default=None,
                     help="time the four-cycle test instead: comma-separated names of paired, band (default both)")
     ap.add_argument("--quads-size", type=int, nargs=2, default=(100000, 2000000), metavar=("VIEWS", "EDGES"))
@@ -138,6 +198,8 @@ def main():
         ap.error("--reps must be at least 7")
     if args.quads:
         return quads(args)
+    if args.cemp:
+        return cemp(args)
     import torch
     from irotavg_amd import capi, ral, synth
     L = capi.lib()
