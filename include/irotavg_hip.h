@@ -618,6 +618,44 @@ int irotavg_init_tree_dev(int64_t m, int64_t n_total, int f, const int32_t *I_de
  * the kernels and fills it put on the stream, out[1] = the most pointer-jumping passes of one round that moved a pointer. */
 void irotavg_init_tree_counters(int64_t out[2]);
 
+/* Weiszfeld sweeps (docs/local_sweeps.md): solver-free refinement of rotations; every free view is moved to the geodesic
+ * median (IROTAVG_L1) or mean (IROTAVG_L2) of what its neighbours predict for it, all views at once (Jacobi). No fixed
+ * structure, no band, no solver, no tolerance; any topology.
+ *   m, n_total, I, QQ, ldqq   as irotavg_cycle_check: Q_b = QQ_k (x) Q_a, quaternions [x y z w] taken as given; q(k, u->v)
+ *               is QQ_k along the stored direction and QQ_k with only w negated against it
+ *   f           1 <= f <= n_total: the views [0, f) are fixed, read as neighbours and never written
+ *   Q, ldq      n_total x 4 column-major, ldq >= n_total: input and output
+ *   w           m doubles or NULL (all ones): edge weights
+ *   cost        IROTAVG_L1 or IROTAVG_L2
+ *   sweeps      0 .. 1024;  inner  1 .. 16;  floor  finite and > 0, in radians
+ * Sweep t forms every Q^{t+1} from Q^t. For a free view v the TERMS are the entries i of its row of the sorted half-edges,
+ * in row order (neighbours ascending, parallel edges adjacent in the sort's order, no self loops); entry i is the
+ * half-edge v -> u_i of edge k_i and predicts P_i = q(k_i, u_i->v) (x) Q^t[u_i]. From y_0 = Q^t[v], for j = 0 .. inner-1:
+ * r_i = the log of y_j* (x) P_i wrapped into [-pi, pi), zero below the library's EPS (edge_log); rho_i = |r_i|;
+ * c_i = w[k_i] / max(rho_i, floor) for L1, w[k_i] for L2; a term is left out of both sums when a component of r_i is not
+ * finite or w[k_i] is not finite or <= 0; x_j = sum c_i r_i / sum c_i, zero when no term is left;
+ * y_{j+1} = y_j (x) exp(x_j), the library's right-multiplied step, a step that is not finite leaving y alone. Then
+ * Q^{t+1}[v] = y_inner, not renormalised. With inner > 1 the predictions stay fixed while y moves (Hartley's
+ * single-rotation median nested in the sweep). A free view with an empty row keeps its rotation.
+ *   step        sweeps doubles on the HOST or NULL: step[t] = the largest |x_0| of sweep t over the free views, NaN
+ *               ignored: the stationarity of the iteration, the caller's stopping rule
+ *   info        2 int64 on the HOST or NULL: the half-edges in rows of free views; the free views with an empty row
+ * Errors and write rules are those of irotavg_cycle_check: IROTAVG_ERR_BAD_ARG before any device work for NULL I, QQ or Q,
+ * a size, f, cost, sweeps, inner or floor out of range, ldqq < m, ldq < n_total; IROTAVG_ERR_NO_DEVICE without a device; an
+ * id outside [0, n_total) is found on the device before anything is indexed with it: IROTAVG_ERR_BAD_ARG, every byte of Q
+ * untouched. Outputs are written on success alone. With sweeps == 0 and info NULL the call is the id check; f == n_total
+ * succeeds and writes nothing to Q. The sums of a view are added in one fixed order and there are no atomics: two calls
+ * give the same bytes. */
+int irotavg_weiszfeld(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, double *Q, int64_t ldq,
+                      const double *w, int cost, int sweeps, int inner, double floor, double *step, int64_t info[2]);
+/* The same on arrays that live on the device, under the rules of irotavg_init_tree_dev: QQ_dev and Q_dev strided m x 4 and
+ * n_total x 4 matrices under the stride rule, everything 8-byte aligned, the lowest and highest element of every array
+ * device memory of the current device. The kernels go on `stream` itself; the call blocks until the error word, step and
+ * info are back. Q is bitwise the host call's. */
+int irotavg_weiszfeld_dev(int64_t m, int64_t n_total, int f, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                          int64_t qq_cs, double *Q_dev, int64_t q_rs, int64_t q_cs, const double *w_dev, int cost, int sweeps,
+                          int inner, double floor, double *step /* HOST */, int64_t *info /* HOST */, void *stream);
+
 /* Testing aid: fingerprint of the handle's static structure -- every index array the build produces (edge
  * streams, boundary slots, per level the SELL-64 pattern and the value-refresh maps) as one 64-bit FNV-1a hash
  * each, followed by the scalars that choose kernels (level shapes, far-entry count, fused-assembly / two-launch

@@ -55,6 +55,7 @@ SYMBOLS = [
     "irotavg_cycle_check4", "irotavg_cycle_check4_dev", "irotavg_cycle_check4_group",
     "irotavg_init_tree", "irotavg_init_tree_dev", "irotavg_init_tree_counters",
     "irotavg_cycle_cemp", "irotavg_cycle_cemp_dev",
+    "irotavg_weiszfeld", "irotavg_weiszfeld_dev",
 ]
 
 
@@ -203,6 +204,10 @@ def lib():
                                         C.c_int64, vp, _i64p, vp]
     L.irotavg_init_tree_counters.argtypes = [_i64p]
     L.irotavg_init_tree_counters.restype = None
+    L.irotavg_weiszfeld.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_int, C.c_int,
+                                    C.c_int, C.c_double, _dp, _i64p]
+    L.irotavg_weiszfeld_dev.argtypes = [C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64,
+                                        vp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i64p, vp]
     L.irotavg_viewgraph_rotation_variance.argtypes = [vp, C.c_int, _dp, C.c_int64, _ip, _dp, C.POINTER(UncertaintyInfo)]
     L.irotavg_viewgraph_num_connections.argtypes = [vp, C.c_int]
     L.irotavg_viewgraph_num_connections.restype = C.c_int64
@@ -838,6 +843,56 @@ def init_tree_counters():
     out = (C.c_int64 * 2)(0, 0)
     lib().irotavg_init_tree_counters(out)
     return int(out[0]), int(out[1])
+
+
+SWEEP_INFO_FIELDS = ("half_edges", "empty_rows")
+SWEEP_COSTS = {"l2": 0, "l1": 1}  # IROTAVG_L2, IROTAVG_L1
+
+
+def sweep_args(cost, sweeps, inner, floor):
+    """cost, sweeps, inner, floor of weiszfeld as (int, int, int, float), or ValueError: "l1" / "l2" (or IROTAVG_L1 / L2),
+    sweeps in [0, 1024], inner in [1, 16], floor finite and > 0."""
+    if cost not in SWEEP_COSTS and cost not in SWEEP_COSTS.values():
+        raise ValueError("cost must be 'l1' or 'l2', got %r" % (cost,))
+    sweeps, inner, floor = int(sweeps), int(inner), float(floor)
+    if not 0 <= sweeps <= 1024:
+        raise ValueError("sweeps must lie in [0, 1024], got %d" % sweeps)
+    if not 1 <= inner <= 16:
+        raise ValueError("inner must lie in [1, 16], got %d" % inner)
+    if not 0.0 < floor < float("inf"):
+        raise ValueError("floor must be a finite positive angle, got %r" % floor)
+    return int(SWEEP_COSTS.get(cost, cost)), sweeps, inner, floor
+
+
+def weiszfeld(I, QQ, n_total, Q, f=1, w=None, cost="l1", sweeps=10, inner=1, floor=1e-6, step=True, info=True, allow_rc=()):
+    """irotavg_weiszfeld (docs/local_sweeps.md): `sweeps` Jacobi sweeps that move every free view to the geodesic median
+    ("l1") or mean ("l2") of what its neighbours predict for it. Q (n_total, 4) float64: the rows from f on are updated in
+    place on success (through a column-major copy). w: m weights or None. Returns dict(rc, Q, step (float64, sweeps; None
+    if not asked for), info (dict of SWEEP_INFO_FIELDS or None)). Anything but OK raises unless listed in allow_rc."""
+    I = edges(I)
+    QQ = fmat(QQ)
+    m = len(I)
+    if QQ.shape != (m, 4):
+        raise ValueError("QQ must be (%d, 4)" % m)
+    Qf = fmat(Q)
+    if Qf.shape != (int(n_total), 4):
+        raise ValueError("Q must be (%d, 4)" % int(n_total))
+    wv = None
+    if w is not None:
+        wv = np.ascontiguousarray(w, dtype=np.float64)
+        if wv.shape != (m,):
+            raise ValueError("w must be (%d,)" % m)
+    cost, sweeps, inner, floor = sweep_args(cost, sweeps, inner, floor)
+    st = np.full(sweeps, -1.0) if step else None
+    h = (C.c_int64 * 2)(-1, -1)
+    rc = lib().irotavg_weiszfeld(m, int(n_total), int(f), _i(I), _d(QQ), QQ.shape[0], _d(Qf), Qf.shape[0],
+                                 None if wv is None else _d(wv), cost, sweeps, inner, floor, None if st is None else _d(st),
+                                 h if info else None)
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_weiszfeld")
+    if rc == OK:
+        Q[...] = Qf
+    return dict(rc=rc, Q=Q, step=st, info=dict(zip(SWEEP_INFO_FIELDS, (int(v) for v in h))) if info and rc == OK else None)
 
 
 def plan_host(world, rank, I, n_total, f):

@@ -662,4 +662,38 @@ void irotavg_init_tree_counters(int64_t out[2]) {
     if (out) init_tree_counters(out);
 }
 
+// Weiszfeld sweeps (docs/local_sweeps.md; the kernels: sweep.hip). Handle-free; the device form runs on the caller's stream
+// itself, as the cycle check does: its size checks, and those of the sweep.
+static bool sweep_args_ok(int64_t m, int64_t n_total, int f, int cost, int sweeps, int inner, double floor) {
+    return cycle_sizes_ok(m, n_total, 0.0) && f >= 1 && f <= n_total && (cost == IROTAVG_L1 || cost == IROTAVG_L2) && sweeps >= 0 &&
+           sweeps <= 1024 && inner >= 1 && inner <= 16 && floor > 0.0 && floor <= std::numeric_limits<double>::max();  // (NaN: false)
+}
+
+int irotavg_weiszfeld(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, double *Q, int64_t ldq,
+                      const double *w, int cost, int sweeps, int inner, double floor, double *step, int64_t info[2]) {
+    if (!I || !QQ || !Q || !sweep_args_ok(m, n_total, f, cost, sweeps, inner, floor) || ldqq < m || ldq < n_total)
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int { return weiszfeld_host(m, n_total, f, I, QQ, ldqq, Q, ldq, w, cost, sweeps, inner, floor, step, info); });
+}
+
+int irotavg_weiszfeld_dev(int64_t m, int64_t n_total, int f, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs, int64_t qq_cs,
+                          double *Q_dev, int64_t q_rs, int64_t q_cs, const double *w_dev, int cost, int sweeps, int inner,
+                          double floor, double *step, int64_t *info, void *stream) {
+    if (!I_dev || !QQ_dev || !Q_dev || !sweep_args_ok(m, n_total, f, cost, sweeps, inner, floor) || !strides_ok(m, 4, qq_rs, qq_cs) ||
+        !strides_ok(n_total, 4, q_rs, q_cs))
+        return IROTAVG_ERR_BAD_ARG;
+    if (!aligned8(I_dev) || !aligned8(QQ_dev) || !aligned8(Q_dev) || !aligned8(w_dev)) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!dev_index_ok(I_dev, m, device) || !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device) ||
+            !dev_matrix_ok(Q_dev, n_total, 4, q_rs, q_cs, device) || (w_dev && !dev_vector_ok(w_dev, m, device)))
+            return IROTAVG_ERR_BAD_ARG;
+        const SweepArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs, w_dev};
+        return weiszfeld_dev(m, n_total, f, A, cost, sweeps, inner, floor, step, info, static_cast<hipStream_t>(stream));
+    });
+}
+
 }  // extern "C"

@@ -391,6 +391,22 @@ int cycle_cemp_dev(int64_t m, int64_t n_total, const CempArrays &A, int iters, c
                    int64_t *summary /* host */, hipStream_t stream);
 int cycle_cemp_host(int64_t m, int64_t n_total, const CempArrays &A, int iters, const double *beta, int64_t max_records,
                     int64_t *summary);
+// sweep.hip: Weiszfeld sweeps over the sorted half-edges (irotavg_weiszfeld[_dev]; docs/local_sweeps.md). The arguments have
+// been checked. The device form runs on `stream`, reads every row of Q and writes the rows from f on; the host form
+// uploads, runs the same kernels and copies those rows back. Both block until the error word, step and info are back;
+// w, step and info may each be nullptr. Outputs are written on success alone.
+struct SweepArrays {
+    const int32_t *I;  // m pairs
+    const double *QQ;  // strided m x 4
+    long long qq_rs, qq_cs;
+    double *Q;  // strided n_total x 4, in and out
+    long long q_rs, q_cs;
+    const double *w;  // m, or nullptr: all ones
+};
+int weiszfeld_dev(int64_t m, int64_t n_total, int f, const SweepArrays &A, int cost, int sweeps, int inner, double floor,
+                  double *step /* host */, int64_t *info /* host */, hipStream_t stream);
+int weiszfeld_host(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, double *Q, int64_t ldq,
+                   const double *w, int cost, int sweeps, int inner, double floor, double *step, int64_t *info);
 // treeinit.hip: the order-free spanning-tree initialiser (irotavg_init_tree[_dev]; docs/init_tree.md). The arguments have
 // been checked. The device form runs on `stream`, reads row 0 of Q and writes the rows from f on; the host form uploads,
 // runs the same kernels and copies those rows back. Both block until the status and info are back; rank, in_tree and info

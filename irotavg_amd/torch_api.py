@@ -192,6 +192,12 @@ class TorchGraph(capi.Graph):
             self.set_rotations(Q)
         return out
 
+    def weiszfeld(self, edge_index, QQ, Q, **kw):
+        """weiszfeld (below) of the tensors passed, with the handle's n_total and f. Q is updated in place; the handle's
+        own rotations are not touched (set_rotations(Q) hands them over)."""
+        _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
+        return weiszfeld(edge_index, QQ, self.n_total, Q, self.f, **kw)
+
     # the host-array forms of the parent stay reachable under their own names
     host_set_rotations = capi.Graph.set_rotations
     host_set_weights = capi.Graph.set_weights
@@ -567,6 +573,16 @@ def rank_from_cemp(s, threshold):
     return rank
 
 
+def weights_from_cemp(s, beta):
+    """Edge weights from the estimates of cycle_cemp, in plain torch on the device: exp(-beta * s), and 1 where s is NaN
+    (an edge no triangle tests). What weiszfeld takes as w and set_weights as weights."""
+    _check(s, "s", (torch.float64,), (None,), placed=False)
+    beta = float(beta)
+    if not 0.0 <= beta < float("inf"):
+        raise ValueError("beta must be finite and non-negative, got %r" % beta)
+    return torch.where(torch.isnan(s), torch.ones_like(s), torch.exp(-beta * s))
+
+
 # ---- the order-free spanning-tree initialiser (irotavg_init_tree_dev, docs/init_tree.md) ----------------------------------
 def rank_from_cycle_check(tri_count, tri_ok):
     """The rank init_tree takes, from the counts of cycle_check, in plain torch on the device: 0 for a supported edge
@@ -625,3 +641,50 @@ def init_tree(edge_index, QQ, n_total, Q, f=1, rank=None, in_tree=False, allow_r
     _allowed(rc, "irotavg_init_tree_dev", allow_rc)
     return dict(rc=rc, Q=Q, in_tree=tree,
                 info=dict(zip(capi.INFO_FIELDS, (int(v) for v in s))) if rc in (capi.OK, capi.ERR_NOT_SPANNING) else None)
+
+
+# ---- Weiszfeld sweeps: solver-free L1 / L2 refinement (irotavg_weiszfeld_dev, docs/local_sweeps.md) ----------------------
+def weiszfeld(edge_index, QQ, n_total, Q, f=1, w=None, cost="l1", sweeps=10, inner=1, floor=1e-6, step=True, allow_rc=()):
+    """`sweeps` Jacobi sweeps on torch's current stream: every free view is moved to the geodesic median (cost "l1") or
+    mean ("l2") of what its neighbours predict for it, all views at once. No solver, no fixed structure, any topology; it
+    cannot fail numerically. The usual start is init_tree's Q; l1ra / irls start from the result, or the caller keeps it.
+
+    edge_index, QQ, n_total: as cycle_check. Q: (n_total, 4) float64 with any strides, read and, from row f on, updated in
+    place. w: None (all ones) or a contiguous float64 tensor of m edge weights (weights_from_cemp gives one); an edge whose
+    weight is not finite or <= 0 is left out. inner: Weiszfeld iterations per view and sweep against fixed predictions
+    (1 .. 16). floor: the smallest residual length, in radians, an L1 coefficient divides by. step: True for the largest
+    step of every sweep, in radians (a host list of `sweeps` floats: the caller's stopping rule), False / None for none.
+    Returns dict(rc, Q, step, info); info is a host dict of capi.SWEEP_INFO_FIELDS. An id outside [0, n_total) gives
+    ERR_BAD_ARG with every byte of Q as it was; anything but OK raises unless listed in allow_rc. The call blocks until the
+    status is back."""
+    import numpy as np
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), placed=False)
+    m = int(edge_index.shape[0])
+    _check(QQ, "QQ", (torch.float64,), (m, 4), placed=False)
+    n_total, f = int(n_total), int(f)
+    _check(Q, "Q", (torch.float64,), (n_total, 4), placed=False)
+    if w is not None:
+        _check(w, "w", (torch.float64,), (m,), placed=False)
+    if m < 1:
+        raise ValueError("edge_index must have at least one row")
+    if not 0 < n_total <= INT32_MAX:
+        raise ValueError("n_total must lie in [1, 2^31 - 1], got %d" % n_total)
+    if not 1 <= f <= n_total:
+        raise ValueError("f must lie in [1, n_total], got %d" % f)
+    cost, sweeps, inner, floor = capi.sweep_args(cost, sweeps, inner, floor)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (m, 4), device)
+    _check(Q, "Q", (torch.float64,), (n_total, 4), device)
+    wv = None if w is None else _vector(w, "w", m, device)
+    st = np.full(sweeps, -1.0) if step else None
+    h = (C.c_int64 * 2)(-1, -1)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        rc = capi.lib().irotavg_weiszfeld_dev(m, n_total, f, _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(Q), *matrix_strides(Q),
+                                              None if wv is None else _ptr(wv), cost, sweeps, inner, floor,
+                                              None if st is None else capi._d(st), h, _stream(device))
+    _allowed(rc, "irotavg_weiszfeld_dev", allow_rc)
+    ok = rc == capi.OK
+    return dict(rc=rc, Q=Q, step=st.tolist() if ok and st is not None else None,
+                info=dict(zip(capi.SWEEP_INFO_FIELDS, (int(v) for v in h))) if ok else None)
