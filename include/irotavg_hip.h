@@ -581,6 +581,38 @@ int irotavg_cycle_cemp_dev(int64_t m, int64_t n_total, const int32_t *I_dev, con
                            int64_t qq_cs, int iters, const double *beta, int64_t max_records, double *s_dev,
                            int32_t *tri_used_dev, int64_t summary[2] /* HOST */, void *stream);
 
+/* A corruption estimate for the edges LISTED by message passing over the quadrilaterals of irotavg_cycle_check4
+ * (docs/cycle_check.md, "Corruption estimates over four-cycles"): for the loop closures that close no triangle and that
+ * irotavg_cycle_cemp leaves NaN. Meant for that untested subset: 32 bytes are kept per used quadrilateral, and all edges
+ * of a dense band graph close billions of them; max_records is the guard. A quadrilateral (k1, k2, k3) of a listed edge
+ * is USED when its error d is finite; U4(k) are the used quadrilaterals of k. The state S holds s_in for every edge that
+ * is not listed and the current estimate for a listed one; it starts as the plain mean of d over U4(k). Iteration
+ * t = 0 .. iters-1 (Jacobi, all listed edges together): e = S[k1] + S[k2] + S[k3], mu the smallest e over U4(k) (NaN
+ * ignored), w = exp(-beta[t] (e - mu)), S'[k] = sum w d / sum w, a term with a NaN weight left out. A listed edge without
+ * a used quadrilateral, or with every term left out, gets NaN; so does a self loop. Inputs as irotavg_cycle_check4 (no
+ * threshold), and
+ *   s_in          m doubles: the s of irotavg_cycle_cemp, NaN where no triangle was used. Required unless edges is NULL,
+ *                 where it is never read; the entries of listed edges are never read
+ *   iters, beta, max_records   as irotavg_cycle_cemp (the cap counts the used quadrilaterals of the listed positions)
+ *   s4            ne doubles or NULL: entry t is the estimate of edges[t]; duplicates give equal bytes
+ *   quad_used     ne int32 or NULL: |U4| (a count above 2^31 - 1 is stored as 2^31 - 1)
+ *   summary       2 int64 on the HOST or NULL: the used quadrilaterals of all listed positions (exact); positions without one
+ * Errors and write rules are those of irotavg_cycle_check4 and, for iters, beta and max_records, of irotavg_cycle_cemp;
+ * s_in NULL with edges non-NULL is IROTAVG_ERR_BAD_ARG before any device work. Over the cap: IROTAVG_ERR_NOMEM, s4 and
+ * quad_used untouched, summary WRITTEN. Memory is O(m) plus 32 bytes per used quadrilateral of the listed positions.
+ * No atomics; deterministic: two calls give the same bytes. */
+int irotavg_cycle_cemp4(int64_t m, int64_t n_total, const int32_t *I, const double *QQ, int64_t ldqq, const double *s_in,
+                        int64_t ne, const int32_t *edges, int iters, const double *beta, int64_t max_records, double *s4,
+                        int32_t *quad_used, int64_t summary[2]);
+/* The same on arrays that live on the device, under the rules of irotavg_cycle_check4_dev: s_in_dev and s4_dev 8-byte,
+ * edges_dev and quad_used_dev 4-byte aligned, the lowest and highest element of every array device memory of the current
+ * device; beta stays on the host. The kernels go on `stream` itself; the call blocks until the outputs are written.
+ * Bitwise the host call. */
+int irotavg_cycle_cemp4_dev(int64_t m, int64_t n_total, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                            int64_t qq_cs, const double *s_in_dev, int64_t ne, const int32_t *edges_dev, int iters,
+                            const double *beta, int64_t max_records, double *s4_dev, int32_t *quad_used_dev,
+                            int64_t summary[2] /* HOST */, void *stream);
+
 /* An order-free spanning-tree initialiser, a second one next to irotavg_init_mst (docs/init_tree.md): the tree is the
  * minimum spanning forest under the keys (rank[k], k), ordered lexicographically -- distinct, so the forest is unique and
  * depends on no launch geometry; k alone decides between parallel and reversed duplicates. T(0) = Q[0];

@@ -54,7 +54,7 @@ SYMBOLS = [
     "irotavg_cycle_check", "irotavg_cycle_check_dev", "irotavg_cycle_check_group",
     "irotavg_cycle_check4", "irotavg_cycle_check4_dev", "irotavg_cycle_check4_group",
     "irotavg_init_tree", "irotavg_init_tree_dev", "irotavg_init_tree_counters",
-    "irotavg_cycle_cemp", "irotavg_cycle_cemp_dev",
+    "irotavg_cycle_cemp", "irotavg_cycle_cemp_dev", "irotavg_cycle_cemp4", "irotavg_cycle_cemp4_dev",
     "irotavg_weiszfeld", "irotavg_weiszfeld_dev",
 ]
 
@@ -199,6 +199,10 @@ def lib():
     L.irotavg_cycle_cemp.argtypes = [C.c_int64, C.c_int64, _ip, _dp, C.c_int64, C.c_int, _dp, C.c_int64, _dp, _ip, _i64p]
     L.irotavg_cycle_cemp_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_int, _dp, C.c_int64, vp, vp,
                                          _i64p, vp]
+    L.irotavg_cycle_cemp4.argtypes = [C.c_int64, C.c_int64, _ip, _dp, C.c_int64, _dp, C.c_int64, _ip, C.c_int, _dp, C.c_int64,
+                                      _dp, _ip, _i64p]
+    L.irotavg_cycle_cemp4_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, C.c_int, _dp,
+                                          C.c_int64, vp, vp, _i64p, vp]
     L.irotavg_init_tree.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _ip, _dp, C.c_int64, _ip, _i64p]
     L.irotavg_init_tree_dev.argtypes = [C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64,
                                         C.c_int64, vp, _i64p, vp]
@@ -801,6 +805,37 @@ def cycle_cemp(I, QQ, n_total, beta, max_records=0, s=True, used=True, summary=T
     if rc != OK and rc not in allow_rc:
         raise IrotavgError(rc, "irotavg_cycle_cemp")
     return dict(rc=rc, s=sv, tri_used=cnt,
+                summary=dict(zip(CEMP_SUMMARY_FIELDS, (int(v) for v in h))) if summary and h[0] >= 0 else None)
+
+
+def cycle_cemp4(I, QQ, n_total, s_in, edges=None, beta=(), max_records=0, s4=True, used=True, summary=True, allow_rc=()):
+    """irotavg_cycle_cemp4 (docs/cycle_check.md, "Corruption estimates over four-cycles"): len(beta) iterations of message
+    passing over the quadrilaterals of the edges listed (edges: ne int32 edge ids, or None: all m in order; s_in: m float64,
+    the s of cycle_cemp, or None with edges None). Returns dict(rc, s (float64, ne, radians; NaN: no used quadrilateral),
+    quad_used (int32, ne), summary (dict of CEMP_SUMMARY_FIELDS; also with ERR_NOMEM from max_records)); an output that was
+    not asked for is None. s and quad_used are preset to -1, and written only on success."""
+    I = _edge_pairs(I)
+    QQ = fmat(QQ)
+    m = len(I)
+    if QQ.shape != (m, 4):
+        raise ValueError("QQ must be (%d, 4)" % m)
+    sin = None if s_in is None else np.ascontiguousarray(s_in, dtype=np.float64)
+    if sin is not None and sin.shape != (m,):
+        raise ValueError("s_in must have %d entries" % m)
+    sub = None if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
+    if sub is not None and sub.ndim != 1:
+        raise ValueError("edges must be one-dimensional")
+    ne = m if sub is None else len(sub)
+    b = cemp_schedule(beta)
+    sv = np.full(ne, -1.0) if s4 else None
+    cnt = np.full(ne, -1, dtype=np.int32) if used else None
+    h = (C.c_int64 * 2)(-1, -1)
+    rc = lib().irotavg_cycle_cemp4(m, int(n_total), _i(I), _d(QQ), QQ.shape[0], None if sin is None else _d(sin), ne,
+                                   None if sub is None else _i(sub), len(b), _d(b) if len(b) else None, int(max_records),
+                                   None if sv is None else _d(sv), None if cnt is None else _i(cnt), h if summary else None)
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_cycle_cemp4")
+    return dict(rc=rc, s=sv, quad_used=cnt,
                 summary=dict(zip(CEMP_SUMMARY_FIELDS, (int(v) for v in h))) if summary and h[0] >= 0 else None)
 
 

@@ -85,6 +85,7 @@ __global__ __launch_bounds__(kT) void k_cyc_quads(int ne, const int32_t *__restr
         if (!skip && lane < 4) r = cyc_lower_bound(keys, 0, n2, cyc_key((uint32_t)((lane & 2) ? e.y : e.x) + (uint32_t)(lane & 1), 0u));
         const long long a0 = __shfl(r, 0, CYC4_WAVE), a1 = __shfl(r, 1, CYC4_WAVE), b0 = __shfl(r, 2, CYC4_WAVE), b1 = __shfl(r, 3, CYC4_WAVE);
         CycAcc acc = cyc_acc_zero();
+        Cyc4Sums sums{acc, threshold};
         if (!skip) {
             const bool x_is_b = b1 - b0 <= a1 - a0;  // the shorter row is walked, the longer one staged and searched
             const long long x0 = x_is_b ? b0 : a0, x1 = x_is_b ? b1 : a1, y0 = x_is_b ? a0 : b0, y1 = x_is_b ? a1 : b1;
@@ -98,12 +99,12 @@ __global__ __launch_bounds__(kT) void k_cyc_quads(int ne, const int32_t *__restr
                 wave_fence();
                 const CycRowStaged y{mine, ylen};
                 cyc4_lane(keys, vals, rows, x0, x1, lane / S, kSubs, lane % S, S, (uint32_t)e.x, (uint32_t)e.y, x_is_b, y, q0,
-                          threshold, load, acc);
+                          load, sums);
                 wave_fence();  // (the next edge's stores come behind every lane's reads)
             } else {  // a row too long for the slab: the sorted keys themselves are searched
                 const CycRowGlobal y{keys, vals, y0, ylen};
                 cyc4_lane(keys, vals, rows, x0, x1, lane / S, kSubs, lane % S, S, (uint32_t)e.x, (uint32_t)e.y, x_is_b, y, q0,
-                          threshold, load, acc);
+                          load, sums);
             }
         }
 #pragma unroll
@@ -140,6 +141,16 @@ void launch_quads(int grid, hipStream_t s, int ne, int m, const CycPrep &P, cons
 
 }  // namespace
 
+void cyc4_edge_ids(long long ne, long long m, const int32_t *edges, long long *err, hipStream_t stream) {
+    hipLaunchKernelGGL(k_cyc_edge_ids, dim3(grid_of(ne)), dim3(kT), 0, stream, ne, m, edges, err);
+    IRH_CHECK(hipGetLastError());
+}
+
+void cyc4_rows(long long n2, const uint64_t *keys, const long long *err, CycSpan *rows, hipStream_t stream) {
+    hipLaunchKernelGGL(k_cyc_rows, dim3(grid_of(n2)), dim3(kT), 0, stream, n2, keys, err, rows);
+    IRH_CHECK(hipGetLastError());
+}
+
 int cycle_check4_group(int lanes) {
     if (lanes == 0) lanes = kQuadDefaultGroup;
     if (lanes != 8 && lanes != 16 && lanes != 32 && lanes != 64) return IROTAVG_ERR_BAD_ARG;
@@ -166,12 +177,10 @@ int cycle_check4_dev(int64_t m, int64_t n_total, const Cycle4Arrays &A, double t
     }
     cyc_prep_run(P, m, n_total, A.I, A.QQ, A.qq_rs, A.qq_cs, stream);
     if (A.edges && ne > 0) {
-        hipLaunchKernelGGL(k_cyc_edge_ids, dim3(grid_of(ne)), dim3(kT), 0, stream, (long long)ne, (long long)m, A.edges, P.head.p);
-        IRH_CHECK(hipGetLastError());
+        cyc4_edge_ids(ne, m, A.edges, P.head.p, stream);
     }
     if (quads) {
-        hipLaunchKernelGGL(k_cyc_rows, dim3(grid_of(n2)), dim3(kT), 0, stream, n2, P.kout.p, P.head.p, rows.p);
-        IRH_CHECK(hipGetLastError());
+        cyc4_rows(n2, P.kout.p, P.head.p, rows.p, stream);
         switch (S) {
         case 8: launch_quads<8>((int)nwg, stream, (int)ne, (int)m, P, rows.p, threshold, A, parts.p); break;
         case 32: launch_quads<32>((int)nwg, stream, (int)ne, (int)m, P, rows.p, threshold, A, parts.p); break;

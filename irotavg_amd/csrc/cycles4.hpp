@@ -72,42 +72,61 @@ IRH_CYC_HD int cyc4_find(const Row &y, uint32_t w) {
     return lo;
 }
 
-// Entry j of the row of an x-entry: its neighbour w (d when x == b, c when x == a) is looked up in y, and every entry of
-// the run of equals there closes a quadrilateral. qx: the partial product q1 (x) q0 when x == b, q3 when x == a.
-template <class Row, class Load>
+// What the four-cycle test does with a quadrilateral: the sums of one lane. The walk below hands every quadrilateral it
+// closes to a sink as (d, k1, k2, k3); the message passing (cemp4.hpp) counts and stores them instead.
+struct Cyc4Sums {
+    CycAcc &acc;
+    double threshold;
+    IRH_CYC_HD void operator()(double d, uint32_t, uint32_t, uint32_t) { cyc_acc_add(acc, d, threshold); }
+};
+
+// Entry i of the walked row x: false when it is edge k itself or one parallel to it. Otherwise kx is its edge and qx the
+// partial product: x == b: b -> c as k1 needs it, multiplied onto q0 once for the whole row of c; x == a: a -> d, and k3
+// needs d -> a.
+template <class Load>
+IRH_CYC_HD bool cyc4_walked(const uint64_t *keys, const uint32_t *vals, long long i, uint32_t a, uint32_t b, bool x_is_b,
+                            const CycQ q0, const Load &load, uint32_t &kx, CycQ &qx) {
+    const uint32_t c = cyc_key_to(keys[i]);
+    if (c == a || c == b) return false;
+    const uint32_t vi = vals[i];
+    kx = cyc_val_edge(vi);
+    const CycQ qi = load(kx);
+    qx = x_is_b ? cyc_qmul(cyc_directed(qi, cyc_val_against(vi)), q0) : cyc_directed(qi, !cyc_val_against(vi));
+    return true;
+}
+
+// Entry j of the row of an x-entry (edge kx): its neighbour w (d when x == b, c when x == a) is looked up in y, and every
+// entry of the run of equals there closes a quadrilateral, handed to sink(d, k1, k2, k3) in run order. qx: cyc4_walked's.
+template <class Row, class Load, class Sink>
 IRH_CYC_HD void cyc4_entry(const uint64_t *keys, const uint32_t *vals, long long j, uint32_t a, uint32_t b, bool x_is_b,
-                           const Row &y, const CycQ q0, const CycQ qx, double threshold, const Load &load, CycAcc &acc) {
+                           const Row &y, const CycQ q0, uint32_t kx, const CycQ qx, const Load &load, Sink &sink) {
     const uint32_t w = cyc_key_to(keys[j]);
     if (w == a || w == b) return;
     int t = cyc4_find(y, w);
     if (t >= y.len || y.to(t) != w) return;
-    const uint32_t vj = vals[j];
+    const uint32_t vj = vals[j], kj = cyc_val_edge(vj);
     // x == b: the entry runs c -> d as k2 needs it; x == a: it runs d -> c
-    const CycQ q2 = cyc_directed(load(cyc_val_edge(vj)), x_is_b ? cyc_val_against(vj) : !cyc_val_against(vj));
+    const CycQ q2 = cyc_directed(load(kj), x_is_b ? cyc_val_against(vj) : !cyc_val_against(vj));
     for (; t < y.len && y.to(t) == w; t++) {
-        const uint32_t vy = y.val(t);
+        const uint32_t vy = y.val(t), ky = cyc_val_edge(vy);
         // x == b: the hit runs a -> d and k3 needs d -> a; x == a: it runs b -> c as k1 needs it
-        const CycQ qy = cyc_directed(load(cyc_val_edge(vy)), x_is_b ? !cyc_val_against(vy) : cyc_val_against(vy));
-        cyc_acc_add(acc, x_is_b ? cyc_quad_error_from(qx, q2, qy) : cyc_quad_error(q0, qy, q2, qx), threshold);
+        const CycQ qy = cyc_directed(load(ky), x_is_b ? !cyc_val_against(vy) : cyc_val_against(vy));
+        sink(x_is_b ? cyc_quad_error_from(qx, q2, qy) : cyc_quad_error(q0, qy, q2, qx), x_is_b ? kx : ky, kj, x_is_b ? ky : kx);
     }
 }
 
 // What lane `sl` of sub-group `sub` does for edge (a, b): of the walked row [x0, x1) the entries sub, sub + nsub, ...,
 // and of each entry's row (rows: cyc_target_row of every sorted half-edge) the entries sl, sl + S, ...
-template <class Row, class Load>
+template <class Row, class Load, class Sink>
 IRH_CYC_HD void cyc4_lane(const uint64_t *keys, const uint32_t *vals, const CycSpan *rows, long long x0, long long x1, int sub,
                           int nsub, int sl, int S, uint32_t a, uint32_t b, bool x_is_b, const Row &y, const CycQ q0,
-                          double threshold, const Load &load, CycAcc &acc) {
+                          const Load &load, Sink &sink) {
     for (long long i = x0 + sub; i < x1; i += nsub) {
-        const uint32_t c = cyc_key_to(keys[i]);
-        if (c == a || c == b) continue;  // edge k itself or one parallel to it
-        const uint32_t vi = vals[i];
-        const CycQ qi = load(cyc_val_edge(vi));
-        // x == b: b -> c as k1 needs it, multiplied onto q0 once for the whole row of c; x == a: a -> d, k3 needs d -> a
-        const CycQ qx = x_is_b ? cyc_qmul(cyc_directed(qi, cyc_val_against(vi)), q0) : cyc_directed(qi, !cyc_val_against(vi));
+        uint32_t kx;
+        CycQ qx;
+        if (!cyc4_walked(keys, vals, i, a, b, x_is_b, q0, load, kx, qx)) continue;
         const CycSpan r = rows[i];
-        for (long long j = (long long)r.beg + sl; j < r.end; j += S)
-            cyc4_entry(keys, vals, j, a, b, x_is_b, y, q0, qx, threshold, load, acc);
+        for (long long j = (long long)r.beg + sl; j < r.end; j += S) cyc4_entry(keys, vals, j, a, b, x_is_b, y, q0, kx, qx, load, sink);
     }
 }
 
@@ -161,12 +180,13 @@ inline int quads_sorted(int64_t m, int64_t n_total, const int32_t *I, const doub
             for (int sub = 0; sub < nsub; sub++)
                 for (int sl = 0; sl < group; sl++) {
                     CycAcc acc = cyc_acc_zero();
+                    Cyc4Sums sums{acc, threshold};
                     if (staged)
                         cyc4_lane(keys.data(), vals.data(), rows.data(), x0, x1, sub, nsub, sl, group, (uint32_t)a, (uint32_t)b,
-                                  x_is_b, ys, q0, threshold, load, acc);
+                                  x_is_b, ys, q0, load, sums);
                     else
                         cyc4_lane(keys.data(), vals.data(), rows.data(), x0, x1, sub, nsub, sl, group, (uint32_t)a, (uint32_t)b,
-                                  x_is_b, yg, q0, threshold, load, acc);
+                                  x_is_b, yg, q0, load, sums);
                     cyc_acc_merge(total, acc.count, acc.ok, acc.mn);
                 }
         }

@@ -621,6 +621,46 @@ int irotavg_cycle_cemp_dev(int64_t m, int64_t n_total, const int32_t *I_dev, con
     });
 }
 
+// A corruption estimate for the edges listed (docs/cycle_check.md, "Corruption estimates over four-cycles"; the kernels:
+// cemp4.hip): the four-cycle test's checks without a threshold, those of the schedule and the cap, and s_in with a list.
+int irotavg_cycle_cemp4(int64_t m, int64_t n_total, const int32_t *I, const double *QQ, int64_t ldqq, const double *s_in,
+                        int64_t ne, const int32_t *edges, int iters, const double *beta, int64_t max_records, double *s4,
+                        int32_t *quad_used, int64_t summary[2]) {
+    if (!I || !QQ || !cycle_sizes_ok(m, n_total, 0.0) || ldqq < m || !subset_ok(m, ne, edges) || (edges && !s_in) ||
+        !cemp_args_ok(iters, beta, max_records))
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        const Cemp4Arrays A{I, QQ, 1, (long long)ldqq, s_in, edges, s4, quad_used};
+        return cycle_cemp4_host(m, n_total, A, ne, iters, beta, max_records, summary);
+    });
+}
+
+int irotavg_cycle_cemp4_dev(int64_t m, int64_t n_total, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                            int64_t qq_cs, const double *s_in_dev, int64_t ne, const int32_t *edges_dev, int iters,
+                            const double *beta, int64_t max_records, double *s4_dev, int32_t *quad_used_dev, int64_t summary[2],
+                            void *stream) {
+    if (!I_dev || !QQ_dev || !cycle_sizes_ok(m, n_total, 0.0) || !strides_ok(m, 4, qq_rs, qq_cs) || !subset_ok(m, ne, edges_dev) ||
+        (edges_dev && !s_in_dev) || !cemp_args_ok(iters, beta, max_records))
+        return IROTAVG_ERR_BAD_ARG;
+    if (!aligned8(I_dev) || !aligned8(QQ_dev) || !aligned8(s_in_dev) || !aligned8(s4_dev) || !aligned4(quad_used_dev))
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!dev_index_ok(I_dev, m, device) || !dev_matrix_ok(QQ_dev, m, 4, qq_rs, qq_cs, device)) return IROTAVG_ERR_BAD_ARG;
+        if (edges_dev && !dev_vector_ok(s_in_dev, m, device)) return IROTAVG_ERR_BAD_ARG;
+        const int32_t *const per_entry[2] = {edges_dev, quad_used_dev};
+        for (const int32_t *p : per_entry)
+            if (p && ne > 0 && !dev_span_ok(p, p + ne - 1, device)) return IROTAVG_ERR_BAD_ARG;
+        if (s4_dev && ne > 0 && !dev_vector_ok(s4_dev, ne, device)) return IROTAVG_ERR_BAD_ARG;
+        // (without a list s_in is never read: the kernels are not handed it)
+        const Cemp4Arrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, edges_dev ? s_in_dev : nullptr, edges_dev, s4_dev, quad_used_dev};
+        return cycle_cemp4_dev(m, n_total, A, ne, iters, beta, max_records, summary, static_cast<hipStream_t>(stream));
+    });
+}
+
 // The order-free spanning-tree initialiser (docs/init_tree.md; the kernels: treeinit.hip). Handle-free; the device form runs
 // on the caller's stream itself, as the cycle check does.
 static bool tree_sizes_ok(int64_t m, int64_t n_total, int f) {

@@ -376,6 +376,11 @@ int cycle_check4_dev(int64_t m, int64_t n_total, const Cycle4Arrays &A, double t
                      hipStream_t stream);
 int cycle_check4_host(int64_t m, int64_t n_total, const Cycle4Arrays &A, double threshold, int64_t ne, int64_t *summary);
 int cycle_check4_group(int lanes);  // irotavg_cycle_check4_group
+// what the message passing over four-cycles (cemp4.hip) shares with it: the launches of k_cyc_edge_ids (an edge id outside
+// [0, m) sets the error word) and of k_cyc_rows (cyc_target_row of every sorted half-edge; nothing with the word set)
+struct CycSpan;
+void cyc4_edge_ids(long long ne, long long m, const int32_t *edges, long long *err, hipStream_t stream);
+void cyc4_rows(long long n2, const uint64_t *keys, const long long *err, CycSpan *rows, hipStream_t stream);
 // cemp.hip: a corruption estimate for every edge by message passing over its triangles (irotavg_cycle_cemp[_dev];
 // docs/cycle_check.md, "Corruption estimates"). The arguments have been checked (beta: `iters` host doubles); forms and
 // nullptr outputs as cycle_check_dev / cycle_check_host. Both block until the outputs are written. summary (2 entries) is
@@ -391,6 +396,22 @@ int cycle_cemp_dev(int64_t m, int64_t n_total, const CempArrays &A, int iters, c
                    int64_t *summary /* host */, hipStream_t stream);
 int cycle_cemp_host(int64_t m, int64_t n_total, const CempArrays &A, int iters, const double *beta, int64_t max_records,
                     int64_t *summary);
+// cemp4.hip: a corruption estimate for the edges listed by message passing over their quadrilaterals
+// (irotavg_cycle_cemp4[_dev]; docs/cycle_check.md, "Corruption estimates over four-cycles"). The arguments have been
+// checked; forms, blocking, summary and nullptr outputs as cycle_cemp_dev / cycle_cemp_host.
+struct Cemp4Arrays {
+    const int32_t *I;  // m pairs
+    const double *QQ;  // strided m x 4 (device form) / column-major with qq_cs = ldqq, qq_rs = 1 (host form)
+    long long qq_rs, qq_cs;
+    const double *s_in;    // m estimates of cycle_cemp; nullptr allowed with edges == nullptr
+    const int32_t *edges;  // ne edge ids, or nullptr: all m edges in order
+    double *s4;            // ne
+    int32_t *quad_used;    // ne
+};
+int cycle_cemp4_dev(int64_t m, int64_t n_total, const Cemp4Arrays &A, int64_t ne, int iters, const double *beta,
+                    int64_t max_records, int64_t *summary /* host */, hipStream_t stream);
+int cycle_cemp4_host(int64_t m, int64_t n_total, const Cemp4Arrays &A, int64_t ne, int iters, const double *beta,
+                     int64_t max_records, int64_t *summary);
 // sweep.hip: Weiszfeld sweeps over the sorted half-edges (irotavg_weiszfeld[_dev]; docs/local_sweeps.md). The arguments have
 // been checked. The device form runs on `stream`, reads every row of Q and writes the rows from f on; the host form
 // uploads, runs the same kernels and copies those rows back. Both block until the error word, step and info are back;

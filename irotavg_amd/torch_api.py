@@ -180,6 +180,11 @@ class TorchGraph(capi.Graph):
         _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
         return cycle_cemp(edge_index, QQ, self.n_total, beta, **kw)
 
+    def cycle_cemp4(self, edge_index, QQ, s, edges=None, beta=None, **kw):
+        """cycle_cemp4 (below) of the tensors passed, with the handle's n_total, as cycle_check above."""
+        self._open()
+        return cycle_cemp4(edge_index, QQ, self.n_total, s, edges, beta, **kw)
+
     def init_tree(self, edge_index, QQ, rank=None, **kw):
         """init_tree (below) of the tensors passed with the handle's n_total and f, then set_rotations: the handle starts
         from the tree's rotations without a host round trip. The anchor Q[0] and the other fixed rows are the identity.
@@ -557,6 +562,62 @@ def cycle_cemp(edge_index, QQ, n_total, beta=None, max_records=0, s=True, used=T
                                                _stream(device))
     _allowed(rc, "irotavg_cycle_cemp_dev", allow_rc)
     return dict(rc=rc, s=outs[0], tri_used=outs[1],
+                summary=dict(zip(capi.CEMP_SUMMARY_FIELDS, (int(v) for v in h))) if summary and h[0] >= 0 else None)
+
+
+def cycle_cemp4(edge_index, QQ, n_total, s, edges=None, beta=None, max_records=0, s4=True, used=True, summary=True,
+                allow_rc=()):
+    """Message passing over four-cycles on torch's current stream: an estimate, in radians, for the edges listed, from the
+    quadrilaterals of cycle_check4. It is meant for the loop closures that close no triangle and that cycle_cemp leaves
+    NaN. Each quadrilateral is weighted by how clean its three other edges look; the estimates of the listed edges are
+    iterated together, those of all other edges stay as s gives them.
+
+    edge_index, QQ, n_total: as cycle_check. s: (m,) float64, the s of cycle_cemp (the entries of listed edges are not
+    read). edges: None (torch.nonzero(torch.isnan(s)), the edges cycle_cemp left NaN) or a 1-D int32 or int64 tensor of
+    edge ids in any order, duplicates allowed. beta, max_records: as cycle_cemp (32 bytes are kept per quadrilateral).
+    s4 / used: True (a new tensor), False / None (not computed), or a contiguous tensor of ne entries to fill (float64 /
+    int32); entry t belongs to edges[t]. Returns dict(rc, edges, s, quad_used, summary): `s[q["edges"]] = q["s"]` merges
+    the result into a copy of s. Errors and summary as cycle_cemp. The call blocks until the outputs are written."""
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), placed=False)
+    m = int(edge_index.shape[0])
+    _check(QQ, "QQ", (torch.float64,), (m, 4), placed=False)
+    _check(s, "s", (torch.float64,), (m,), placed=False)
+    if edges is not None:
+        _check(edges, "edges", (torch.int32, torch.int64), (None,), placed=False)
+    n_total, max_records = int(n_total), int(max_records)
+    if m < 1:
+        raise ValueError("edge_index must have at least one row")
+    if not 0 < n_total <= INT32_MAX:
+        raise ValueError("n_total must lie in [1, 2^31 - 1], got %d" % n_total)
+    b = capi.cemp_schedule(cemp_beta() if beta is None else beta)
+    if max_records < 0:
+        raise ValueError("max_records must not be negative, got %d" % max_records)
+    if not s.is_contiguous():
+        raise ValueError("s must be contiguous")
+    if edges is None:
+        edges = torch.nonzero(torch.isnan(s)).flatten()
+    ne = int(edges.shape[0])
+    if ne < 1:
+        raise ValueError("edges must have at least one entry")
+    wants = (("s4", s4, torch.float64), ("used", used, torch.int32))
+    for name, want, dt in wants:
+        if not (want is True or want is False or want is None):
+            _check(want, name, (dt,), (ne,), placed=False)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
+    device = edge_index.device
+    _check(QQ, "QQ", (torch.float64,), (m, 4), device)
+    _check(s, "s", (torch.float64,), (m,), device)
+    _check(edges, "edges", (torch.int32, torch.int64), (None,), device)
+    outs = [_output(want, name, ne, device, dt) for name, want, dt in wants]
+    h = (C.c_int64 * 2)(-1, -1)
+    with torch.cuda.device(device):
+        ei, sub = _narrow(edge_index), _narrow(edges)
+        rc = capi.lib().irotavg_cycle_cemp4_dev(m, n_total, _ptr(ei), _ptr(QQ), *matrix_strides(QQ), _ptr(s), ne, _ptr(sub),
+                                                len(b), capi._d(b) if len(b) else None, max_records,
+                                                *[None if t is None else _ptr(t) for t in outs], h if summary else None,
+                                                _stream(device))
+    _allowed(rc, "irotavg_cycle_cemp4_dev", allow_rc)
+    return dict(rc=rc, edges=edges, s=outs[0], quad_used=outs[1],
                 summary=dict(zip(capi.CEMP_SUMMARY_FIELDS, (int(v) for v in h))) if summary and h[0] >= 0 else None)
 
 

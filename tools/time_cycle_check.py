@@ -179,8 +179,66 @@ def cemp(args):
     print(json.dumps(out))
 
 
+def cemp4(args):
+    """--cemp4 paired: the corruption estimates over four-cycles (irotavg_cycle_cemp4_dev) of the edges that triangle CEMP
+    leaves NaN on the paired graph of --quads, at six iterations and at none, alternating with the four-cycle test of the
+    same subset; the time of one iteration is the difference over six."""
+    import torch
+    from irotavg_amd import capi, synth, torch_api
+    L = capi.lib()
+    if L.irotavg_device_count() <= 0:
+        raise SystemExit("no HIP device: the product has no CPU fallback")
+    if args.cemp4 != "paired":
+        raise SystemExit("--cemp4 knows the case paired alone")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n, m_ask = args.quads_size
+    I, QQ = paired_loops(synth.make_graph(n, m_ask, 0.0, seed=args.seed), 0.02, args.seed)
+    m, beta = len(I), np.array(torch_api.cemp_beta(6))
+    ei, qq = torch.tensor(I, device=dev), torch.tensor(np.ascontiguousarray(QQ), dtype=torch.float64, device=dev)
+    s = torch_api.cycle_cemp(ei, qq, n, used=False, summary=False)["s"]
+    sub = torch.nonzero(torch.isnan(s)).flatten().to(torch.int32)
+    ne = int(sub.shape[0])
+    s4, used = torch.zeros(ne, dtype=torch.float64, device=dev), torch.zeros(ne, dtype=torch.int32, device=dev)
+    quad = [torch.zeros(ne, dtype=torch.int32, device=dev), torch.zeros(ne, dtype=torch.int32, device=dev),
+            torch.zeros(ne, dtype=torch.float64, device=dev)]
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    hs, qs, p = (C.c_int64 * 2)(), (C.c_int64 * 4)(), lambda t: C.c_void_p(t.data_ptr())
+    torch.cuda.synchronize()
+
+    def cemp4_call(iters):
+        t = time.perf_counter()
+        rc = L.irotavg_cycle_cemp4_dev(m, n, p(ei), p(qq), 4, 1, p(s), ne, p(sub), iters, capi._d(beta), 0, p(s4), p(used), hs, stream)
+        dt = time.perf_counter() - t   # (the call blocks until the outputs are written)
+        capi.check(rc, "irotavg_cycle_cemp4_dev")
+        return 1e3 * dt
+
+    def quad_call():
+        t = time.perf_counter()
+        rc = L.irotavg_cycle_check4_dev(m, n, p(ei), p(qq), 4, 1, args.threshold, ne, p(sub), *[p(x) for x in quad], qs, stream)
+        dt = time.perf_counter() - t
+        capi.check(rc, "irotavg_cycle_check4_dev")
+        return 1e3 * dt
+
+    t6, t0, tq = [], [], []
+    for rep in range(args.warmup + args.reps):
+        b, c, a = cemp4_call(0), quad_call(), cemp4_call(6)
+        if rep >= args.warmup:
+            t6.append(a), t0.append(b), tq.append(c)
+    h = capi.cycle_cemp4(I, QQ, n, s.cpu().numpy(), sub.cpu().numpy(), beta)
+    equal = bool(h["s"].tobytes() == s4.cpu().numpy().tobytes() and h["quad_used"].tobytes() == used.cpu().numpy().tobytes()
+                 and list(h["summary"].values()) == list(hs))
+    row = dict(case="paired", views=n, edges=m, listed=ne, cemp4_iters6=stats(t6), cemp4_iters0=stats(t0),
+               per_iteration=stats([(a - b) / 6 for a, b in zip(t6, t0)]), cycle_check4=stats(tq), bitwise_equal=equal,
+               summary=dict(zip(capi.CEMP_SUMMARY_FIELDS, (int(v) for v in hs))))
+    row["table_bytes"] = 32 * row["summary"]["records"]
+    row["iters6_over_cycle_check4_median"] = round(row["cemp4_iters6"]["median_ms"] / row["cycle_check4"]["median_ms"], 4)
+    row["iteration_over_iters6_median"] = round(row["per_iteration"]["median_ms"] / row["cemp4_iters6"]["median_ms"], 4)
+    print(json.dumps(dict(tool="time_cycle_check --cemp4", device=torch.cuda.get_device_name(dev), cases=[row])))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cemp4", default=None, help="time the corruption estimates over four-cycles instead: paired")
     ap.add_argument("--cemp", nargs="?", const="band,loops", default=None,
                     help="time the corruption estimates instead: comma-separated names of band, loops (default both)")
     ap.add_argument("--quads", nargs="?", const="paired,band", default=None,
@@ -196,6 +254,8 @@ def main():
     args = ap.parse_args()
     if args.reps < 7:
         ap.error("--reps must be at least 7")
+    if args.cemp4:
+        return cemp4(args)
     if args.quads:
         return quads(args)
     if args.cemp:
