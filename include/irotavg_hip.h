@@ -650,6 +650,43 @@ int irotavg_init_tree_dev(int64_t m, int64_t n_total, int f, const int32_t *I_de
  * the kernels and fills it put on the stream, out[1] = the most pointer-jumping passes of one round that moved a pointer. */
 void irotavg_init_tree_counters(int64_t out[2]);
 
+/* The connected components of the usable edges, and the one to solve as a compact, relabelled problem
+ * (docs/components.md): what a caller needs after a screening step has cut the graph and irotavg_init_tree answers
+ * IROTAVG_ERR_NOT_SPANNING. Everything is an integer; a lock-free union-find in one launch over the edges, eight launches in
+ * all whatever the graph's diameter, no rounds and no host decision in between.
+ *   m, n_total, f, I, rank   as irotavg_init_tree: an edge is usable when rank is NULL or rank[k] >= 0, and a_k != b_k
+ *   which       0: the component of view 0 (irotavg_init_tree's anchor); 1: the component with the most views, ties to the
+ *               smaller label
+ *   label       n_total int32 or NULL: the least view id of the component of v; an isolated view is its own component
+ *   view_map    n_total int32 or NULL: the new id of v when label[v] is the selected label, -1 otherwise. New ids ascend with
+ *               old ids, so the selected fixed views come first: f' = the number of v < f selected
+ *   edge_map    m int32 or NULL: the new index of edge k when it is usable and label[a_k] is selected, in ascending k, -1
+ *               otherwise
+ *   views_out   n_total int32 or NULL: [0, n') = the old ids of the selected views, ascending
+ *   edges_out   m int32 or NULL: [0, m') = the old ids of the kept edges, ascending
+ *   I_out       m pairs or NULL: [0, m') = (view_map[a_k], view_map[b_k]) of the kept edges, in the stored direction
+ *   info        6 int64 on the HOST or NULL: components; n'; m'; f'; the selected label; the size of the largest component
+ * Entries past n' / m' are never written. (n', f', I_out, m') is a problem irotavg_init_tree, irotavg_weiszfeld and
+ * irotavg_graph_create take as it is once the caller has gathered its rows of QQ and Q with edges_out and views_out.
+ * which = 1 may give f' = 0: a success; the caller decides. With every output NULL the call is the id check.
+ * Errors and write rules are those of irotavg_init_tree: IROTAVG_ERR_BAD_ARG before any device work for NULL I, m <= 0 or
+ * above 0x7fffffff, n_total <= 0 or above 0x7fffffff, f < 1 or f > n_total, which not 0 or 1; IROTAVG_ERR_NO_DEVICE without a
+ * device; an id outside [0, n_total) is found on the device before anything is indexed with it: IROTAVG_ERR_BAD_ARG, every
+ * output byte untouched. Outputs are written on success alone. Memory is O(n_total) from the device pool, nothing per
+ * edge. IROTAVG_ERR_SOLVER: the step bound of a find was passed (an internal error that no input should reach).
+ * Deterministic: labels are canonical, sizes exact integer sums, the selection a total order, the compaction
+ * order-preserving -- two calls give the same bytes. */
+int irotavg_components(int64_t m, int64_t n_total, int f, const int32_t *I, const int32_t *rank, int which, int32_t *label,
+                       int32_t *view_map, int32_t *edge_map, int32_t *views_out, int32_t *edges_out, int32_t *I_out,
+                       int64_t info[6]);
+/* The same on arrays that live on the device: I_dev and I_out_dev 8-byte, every other array 4-byte aligned, the lowest and
+ * highest element of every array device memory of the current device (else IROTAVG_ERR_BAD_ARG, before any kernel). The
+ * kernels go on `stream` itself: inputs may still be in flight there, the outputs are ready for whatever is enqueued on it
+ * next. The call blocks until the status and info are back. The outputs are bitwise the host call's. */
+int irotavg_components_dev(int64_t m, int64_t n_total, int f, const int32_t *I_dev, const int32_t *rank_dev, int which,
+                           int32_t *label_dev, int32_t *view_map_dev, int32_t *edge_map_dev, int32_t *views_out_dev,
+                           int32_t *edges_out_dev, int32_t *I_out_dev, int64_t *info /* HOST */, void *stream);
+
 /* Weiszfeld sweeps (docs/local_sweeps.md): solver-free refinement of rotations; every free view is moved to the geodesic
  * median (IROTAVG_L1) or mean (IROTAVG_L2) of what its neighbours predict for it, all views at once (Jacobi). No fixed
  * structure, no band, no solver, no tolerance; any topology.

@@ -56,6 +56,7 @@ SYMBOLS = [
     "irotavg_init_tree", "irotavg_init_tree_dev", "irotavg_init_tree_counters",
     "irotavg_cycle_cemp", "irotavg_cycle_cemp_dev", "irotavg_cycle_cemp4", "irotavg_cycle_cemp4_dev",
     "irotavg_weiszfeld", "irotavg_weiszfeld_dev",
+    "irotavg_components", "irotavg_components_dev",
 ]
 
 
@@ -208,6 +209,8 @@ def lib():
                                         C.c_int64, vp, _i64p, vp]
     L.irotavg_init_tree_counters.argtypes = [_i64p]
     L.irotavg_init_tree_counters.restype = None
+    L.irotavg_components.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _ip, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _i64p]
+    L.irotavg_components_dev.argtypes = [C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, _i64p, vp]
     L.irotavg_weiszfeld.argtypes = [C.c_int64, C.c_int64, C.c_int, _ip, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_int, C.c_int,
                                     C.c_int, C.c_double, _dp, _i64p]
     L.irotavg_weiszfeld_dev.argtypes = [C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64,
@@ -878,6 +881,46 @@ def init_tree_counters():
     out = (C.c_int64 * 2)(0, 0)
     lib().irotavg_init_tree_counters(out)
     return int(out[0]), int(out[1])
+
+
+COMP_INFO_FIELDS = ("components", "n_total", "m", "f", "label", "largest")
+COMP_WHICH = {"anchor": 0, "largest": 1}
+
+
+def components_which(which):
+    """which of components as an int, or ValueError: "anchor" / "largest" (or 0 / 1)."""
+    if which not in COMP_WHICH and which not in COMP_WHICH.values():
+        raise ValueError("which must be 'anchor' or 'largest', got %r" % (which,))
+    return int(COMP_WHICH.get(which, which))
+
+
+def components(I, n_total, f=1, rank=None, which="anchor", allow_rc=()):
+    """irotavg_components (docs/components.md): the connected components of the usable edges (rank None or rank[k] >= 0, no
+    self loops) and the one to solve -- "anchor": that of view 0, "largest": the one with the most views, ties to the
+    smaller label -- as a compact problem. Returns dict(rc, label, view_map (n_total), edge_map (m), views (n'), edges
+    (m'), I (m', 2), info (dict of COMP_INFO_FIELDS: the components, n', m', f', the selected label, the largest size));
+    with another rc than OK every array and info are None. Anything but OK raises unless listed in allow_rc."""
+    I = edges(I)
+    m, n_total = len(I), int(n_total)
+    rk = None
+    if rank is not None:
+        rk = np.ascontiguousarray(rank, dtype=np.int32)
+        if rk.shape != (m,):
+            raise ValueError("rank must be (%d,)" % m)
+    which = components_which(which)
+    per_view = [np.full(max(n_total, 0), -2, dtype=np.int32) for _ in range(3)]  # label, view_map, views_out
+    per_edge = [np.full(m, -2, dtype=np.int32) for _ in range(2)]                # edge_map, edges_out
+    I_out = np.full((m, 2), -2, dtype=np.int32)
+    s = (C.c_int64 * 6)(*([-1] * 6))
+    rc = lib().irotavg_components(m, n_total, int(f), _i(I), None if rk is None else _i(rk), which, _i(per_view[0]),
+                                  _i(per_view[1]), _i(per_edge[0]), _i(per_view[2]), _i(per_edge[1]), _i(I_out), s)
+    if rc != OK and rc not in allow_rc:
+        raise IrotavgError(rc, "irotavg_components")
+    if rc != OK:
+        return dict(rc=rc, label=None, view_map=None, edge_map=None, views=None, edges=None, I=None, info=None)
+    info = dict(zip(COMP_INFO_FIELDS, (int(v) for v in s)))
+    return dict(rc=rc, label=per_view[0], view_map=per_view[1], edge_map=per_edge[0], views=per_view[2][:info["n_total"]],
+                edges=per_edge[1][:info["m"]], I=I_out[:info["m"]], info=info)
 
 
 SWEEP_INFO_FIELDS = ("half_edges", "empty_rows")

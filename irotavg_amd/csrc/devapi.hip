@@ -702,6 +702,42 @@ void irotavg_init_tree_counters(int64_t out[2]) {
     if (out) init_tree_counters(out);
 }
 
+// The connected components of the usable edges and the one to solve as a compact problem (docs/components.md; the kernels:
+// components.hip). Handle-free; the device form runs on the caller's stream itself: init_tree's size checks, and `which`.
+int irotavg_components(int64_t m, int64_t n_total, int f, const int32_t *I, const int32_t *rank, int which, int32_t *label,
+                       int32_t *view_map, int32_t *edge_map, int32_t *views_out, int32_t *edges_out, int32_t *I_out,
+                       int64_t info[6]) {
+    if (!I || !tree_sizes_ok(m, n_total, f) || (which != 0 && which != 1)) return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        const CompArrays A{I, rank, label, view_map, edge_map, views_out, edges_out, I_out};
+        return components_host(m, n_total, f, which, A, info);
+    });
+}
+
+int irotavg_components_dev(int64_t m, int64_t n_total, int f, const int32_t *I_dev, const int32_t *rank_dev, int which,
+                           int32_t *label_dev, int32_t *view_map_dev, int32_t *edge_map_dev, int32_t *views_out_dev,
+                           int32_t *edges_out_dev, int32_t *I_out_dev, int64_t *info, void *stream) {
+    if (!I_dev || !tree_sizes_ok(m, n_total, f) || (which != 0 && which != 1)) return IROTAVG_ERR_BAD_ARG;
+    if (!aligned8(I_dev) || !aligned8(I_out_dev) || !aligned4(rank_dev) || !aligned4(label_dev) || !aligned4(view_map_dev) ||
+        !aligned4(edge_map_dev) || !aligned4(views_out_dev) || !aligned4(edges_out_dev))
+        return IROTAVG_ERR_BAD_ARG;
+    if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
+    return guarded([&]() -> int {
+        int device = 0;
+        IRH_CHECK(hipGetDevice(&device));
+        if (!dev_index_ok(I_dev, m, device) || (I_out_dev && !dev_index_ok(I_out_dev, m, device))) return IROTAVG_ERR_BAD_ARG;
+        const int32_t *const per_edge[3] = {rank_dev, edge_map_dev, edges_out_dev};
+        for (const int32_t *p : per_edge)
+            if (p && !dev_span_ok(p, p + m - 1, device)) return IROTAVG_ERR_BAD_ARG;
+        const int32_t *const per_view[3] = {label_dev, view_map_dev, views_out_dev};
+        for (const int32_t *p : per_view)
+            if (p && !dev_span_ok(p, p + n_total - 1, device)) return IROTAVG_ERR_BAD_ARG;
+        const CompArrays A{I_dev, rank_dev, label_dev, view_map_dev, edge_map_dev, views_out_dev, edges_out_dev, I_out_dev};
+        return components_dev(m, n_total, f, which, A, info, static_cast<hipStream_t>(stream));
+    });
+}
+
 // Weiszfeld sweeps (docs/local_sweeps.md; the kernels: sweep.hip). Handle-free; the device form runs on the caller's stream
 // itself, as the cycle check does: its size checks, and those of the sweep.
 static bool sweep_args_ok(int64_t m, int64_t n_total, int f, int cost, int sweeps, int inner, double floor) {

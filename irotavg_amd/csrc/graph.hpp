@@ -445,6 +445,21 @@ int init_tree_dev(int64_t m, int64_t n_total, int f, const TreeArrays &A, int64_
 int init_tree_host(int64_t m, int64_t n_total, int f, const int32_t *I, const double *QQ, int64_t ldqq, const int32_t *rank, double *Q,
                    int64_t ldq, int32_t *in_tree, int64_t *info);
 void init_tree_counters(int64_t out[2]);  // irotavg_init_tree_counters
+// components.hip: the connected components of the usable edges and the selected one as a compact problem
+// (irotavg_components[_dev]; docs/components.md). The arguments have been checked. The device form runs on `stream`, the
+// host form uploads, runs the same kernels and copies back what was written. Both block until the status and info are
+// back; rank, every output and info may each be nullptr. Outputs are written on success alone.
+struct CompArrays {
+    const int32_t *I;     // m pairs
+    const int32_t *rank;  // m, or nullptr: all zero
+    int32_t *label, *view_map;  // n_total each
+    int32_t *edge_map;          // m
+    int32_t *views_out;         // n_total, the first n' written
+    int32_t *edges_out;         // m, the first m' written
+    int32_t *I_out;             // m pairs, the first m' written
+};
+int components_dev(int64_t m, int64_t n_total, int f, int which, const CompArrays &A, int64_t *info /* host */, hipStream_t stream);
+int components_host(int64_t m, int64_t n_total, int f, int which, const CompArrays &A, int64_t *info);
 // wincov.hip: the uncertainty queries of a window-size problem in one kernel launch (docs/viewgraph_uncertainty.md)
 struct WinCov;
 WinCov *wincov_new();

@@ -197,6 +197,11 @@ class TorchGraph(capi.Graph):
             self.set_rotations(Q)
         return out
 
+    def components(self, edge_index, **kw):
+        """components (below) of the tensor passed, with the handle's n_total and f."""
+        _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), self.device)
+        return components(edge_index, self.n_total, self.f, **kw)
+
     def weiszfeld(self, edge_index, QQ, Q, **kw):
         """weiszfeld (below) of the tensors passed, with the handle's n_total and f. Q is updated in place; the handle's
         own rotations are not touched (set_rotations(Q) hands them over)."""
@@ -702,6 +707,82 @@ def init_tree(edge_index, QQ, n_total, Q, f=1, rank=None, in_tree=False, allow_r
     _allowed(rc, "irotavg_init_tree_dev", allow_rc)
     return dict(rc=rc, Q=Q, in_tree=tree,
                 info=dict(zip(capi.INFO_FIELDS, (int(v) for v in s))) if rc in (capi.OK, capi.ERR_NOT_SPANNING) else None)
+
+
+# ---- connected components and the sub-problem to solve (irotavg_components_dev, docs/components.md) -----------------------
+def components(edge_index, n_total, f=1, rank=None, which="anchor", allow_rc=()):
+    """The connected components of the usable edges and the one to solve as a compact, relabelled problem, on torch's
+    current stream: what to do when a screening step has cut the graph and init_tree answers ERR_NOT_SPANNING. Eight
+    launches whatever the graph, no host decision in between.
+
+    edge_index: (m, 2) int32 or int64 (narrowed on the device: a value outside int32 range becomes an id the device check
+    refuses). rank: None or a contiguous int32 tensor of m entries; edge k is usable when rank[k] >= 0 and its ends differ.
+    which: "anchor" (the component of view 0) or "largest" (the most views, ties to the smaller label; f may come out 0).
+    Returns dict(rc, label (n_total: the least id of the view's component), view_map (n_total) and edge_map (m): new ids,
+    -1 outside the selection, views (n') and edges (m'): the old ids in ascending order, edge_index (m', 2): the kept edges
+    in new ids, n_total, m, f: n', m', f' -- what init_tree, weiszfeld and TorchGraph take --, info: a host dict of
+    capi.COMP_INFO_FIELDS). extract_component gathers the caller's rows, scatter_component puts an answer back. An id
+    outside [0, n_total) gives ERR_BAD_ARG; with another rc than OK the tensors and info are None; anything but OK raises
+    unless listed in allow_rc. The call blocks until the status is back."""
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2), placed=False)
+    m = int(edge_index.shape[0])
+    if rank is not None:
+        _check(rank, "rank", (torch.int32,), (m,), placed=False)
+    n_total, f = int(n_total), int(f)
+    if m < 1:
+        raise ValueError("edge_index must have at least one row")
+    if not 0 < n_total <= INT32_MAX:
+        raise ValueError("n_total must lie in [1, 2^31 - 1], got %d" % n_total)
+    if not 1 <= f <= n_total:
+        raise ValueError("f must lie in [1, n_total], got %d" % f)
+    which = capi.components_which(which)
+    _check(edge_index, "edge_index", (torch.int32, torch.int64), (None, 2))
+    device = edge_index.device
+    rk = None if rank is None else _vector(rank, "rank", m, device, torch.int32)
+    label, view_map, views = (torch.empty(n_total, dtype=torch.int32, device=device) for _ in range(3))
+    edge_map, edges = (torch.empty(m, dtype=torch.int32, device=device) for _ in range(2))
+    ei_out = torch.empty((m, 2), dtype=torch.int32, device=device)
+    s = (C.c_int64 * 6)(*([-1] * 6))
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        rc = capi.lib().irotavg_components_dev(m, n_total, f, _ptr(ei), None if rk is None else _ptr(rk), which, _ptr(label),
+                                               _ptr(view_map), _ptr(edge_map), _ptr(views), _ptr(edges), _ptr(ei_out), s,
+                                               _stream(device))
+    _allowed(rc, "irotavg_components_dev", allow_rc)
+    if rc != capi.OK:
+        return dict(rc=rc, label=None, view_map=None, edge_map=None, views=None, edges=None, edge_index=None, n_total=None,
+                    m=None, f=None, info=None)
+    info = dict(zip(capi.COMP_INFO_FIELDS, (int(v) for v in s)))
+    n1, m1 = info["n_total"], info["m"]
+    return dict(rc=rc, label=label, view_map=view_map, edge_map=edge_map, views=views[:n1], edges=edges[:m1],
+                edge_index=ei_out[:m1], n_total=n1, m=m1, f=info["f"], info=info)
+
+
+def extract_component(c, QQ, Q=None, rank=None, w=None):
+    """The caller's rows of the component `c` (a dict of components): QQ, rank and w by c["edges"], Q by c["views"], with
+    index_select on their own device. Returns dict(edge_index, QQ, Q, rank, w, n_total, m, f); what was not passed is None."""
+    m, n = int(c["edge_map"].shape[0]), int(c["view_map"].shape[0])
+    _check(QQ, "QQ", (torch.float64,), (m, 4), placed=False)
+    if Q is not None:
+        _check(Q, "Q", (torch.float64,), (n, 4), placed=False)
+    if rank is not None:
+        _check(rank, "rank", (torch.int32,), (m,), placed=False)
+    if w is not None:
+        _check(w, "w", (torch.float64,), (m,), placed=False)
+    edges, views = c["edges"].long(), c["views"].long()
+    return dict(edge_index=c["edge_index"], QQ=QQ.index_select(0, edges), Q=None if Q is None else Q.index_select(0, views),
+                rank=None if rank is None else rank.index_select(0, edges), w=None if w is None else w.index_select(0, edges),
+                n_total=c["n_total"], m=c["m"], f=c["f"])
+
+
+def scatter_component(c, Q_full, Q_sub):
+    """Q_full[c["views"]] = Q_sub, in place: the rows of a solved component back into the full problem. Every other row of
+    Q_full stays as it is. Returns Q_full."""
+    n, n1 = int(c["view_map"].shape[0]), int(c["views"].shape[0])
+    _check(Q_full, "Q_full", (torch.float64,), (n, 4), placed=False)
+    _check(Q_sub, "Q_sub", (torch.float64,), (n1, 4), placed=False)
+    Q_full.index_copy_(0, c["views"].long(), Q_sub)
+    return Q_full
 
 
 # ---- Weiszfeld sweeps: solver-free L1 / L2 refinement (irotavg_weiszfeld_dev, docs/local_sweeps.md) ----------------------
