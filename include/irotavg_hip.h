@@ -488,6 +488,29 @@ int irotavg_window_init_mst_batch_dev(int64_t nb, const int32_t *sizes, const in
                                       int64_t qq_rs, int64_t qq_cs, double *Q_dev, int64_t q_rs, int64_t q_cs,
                                       int32_t *results, void *stream);
 
+/* The corruption estimates of irotavg_cycle_cemp (below) for many small problems in one call, on arrays that live on the
+ * device (docs/window_cemp_batch.md): the screening in front of init -> solve -> gate, one workgroup per problem, ONE
+ * launch, the start vector and every iteration inside it. sizes, packing, limits, the stride rule, alignment and the
+ * lowest / highest-element check are those of irotavg_window_solve_batch_dev, so the same arrays pass down the chain; f
+ * is held to the limits and otherwise unused (fixed and free views are alike here).
+ *   iters, beta   as irotavg_cycle_cemp: iters in [0, 64], beta HOST, iters finite doubles >= 0 (NULL with iters == 0)
+ *   s_dev         sum(m) contiguous doubles, 8-byte aligned, or NULL: the estimate of every edge, NaN without a used triangle
+ *   tri_used_dev  sum(m) int32 or NULL: the used (finite) triangles of every edge
+ *   results       HOST, 3 nb int32 or NULL: per problem its status, the sum of tri_used, the edges with no used triangle
+ * Per problem the definition is that of irotavg_cycle_cemp, to the order of its floating-point sums, which is this
+ * kernel's own (the doc states it): s is close to irotavg_cycle_cemp's, not bitwise equal. IROTAVG_ERR_BAD_ARG before any
+ * device work: what irotavg_window_solve_batch_dev refuses of nb, sizes, pointers, strides and alignment, iters outside
+ * [0, 64], beta NULL with iters > 0, a beta[t] that is NaN, infinite or negative; no HIP device: IROTAVG_ERR_NO_DEVICE.
+ * The edge ids are read on the device alone: the workgroup of a problem with an id outside [0, n_total) reports
+ * IROTAVG_ERR_BAD_ARG, indexes nothing with it and leaves its rows of s_dev and tri_used_dev exactly as they were (its
+ * two counts are 0); the other problems are computed. With both outputs NULL the call is the id check and `results`. The
+ * launch goes on `stream` itself: inputs may still be in flight there, the outputs are ready for whatever is enqueued on
+ * it next. The call blocks until every result record has arrived and returns the first non-zero status in problem order.
+ * Deterministic: two calls give the same bytes, and a problem gives the same bytes wherever it stands in a batch. */
+int irotavg_window_cemp_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                  int64_t qq_rs, int64_t qq_cs, int iters, const double *beta, double *s_dev,
+                                  int32_t *tri_used_dev, int32_t *results, void *stream);
+
 /* Cycle-consistency screening of relative rotations before any solve (docs/cycle_check.md): for every edge k = (a, b) the
  * triangles it closes with two other edges, (k1, k2) with k1 joining b and c, k2 joining c and a, c outside {a, b}, no
  * self loop among the three; parallel edges are distinct, every pair counts. The error of a triangle is the angle of

@@ -189,16 +189,18 @@ bool dev_index_ok(const int32_t *p, int64_t rows, int device) { return dev_span_
 // The checks every batched window call makes of its packed problem arrays (A: WinBatchArrays or WinCovArrays), in the
 // order the calls have always had: before any device work alignment and the stride rule (BAD_ARG), then a device at all
 // (NO_DEVICE), then the calling thread's current one -> `device`, then the lowest and the highest element of each array
-// (BAD_ARG). A call's own host checks go in front of this, its own pointer checks behind it.
+// (BAD_ARG). A call's own host checks go in front of this, its own pointer checks behind it. A call that has rotations
+// refuses a NULL Q itself; one that has none (the screening) passes NULL and nothing of Q is looked at.
 template <class Arrays>
 int win_arrays_check(const Arrays &A, int64_t sum_m, int64_t sum_n, int &device) {
     if (!aligned8(A.I) || !aligned8(A.QQ) || !aligned8(A.Q) || !aligned8(A.weights) || !strides_ok(sum_m, 4, A.qq_rs, A.qq_cs) ||
-        !strides_ok(sum_n, 4, A.q_rs, A.q_cs))
+        (A.Q && !strides_ok(sum_n, 4, A.q_rs, A.q_cs)))
         return IROTAVG_ERR_BAD_ARG;
     if (irotavg_device_count() <= 0) return IROTAVG_ERR_NO_DEVICE;
     IRH_CHECK(hipGetDevice(&device));
     const bool ok = dev_index_ok(A.I, sum_m, device) && dev_matrix_ok(A.QQ, sum_m, 4, A.qq_rs, A.qq_cs, device) &&
-                    dev_matrix_ok(A.Q, sum_n, 4, A.q_rs, A.q_cs, device) && (!A.weights || dev_vector_ok(A.weights, sum_m, device));
+                    (!A.Q || dev_matrix_ok(A.Q, sum_n, 4, A.q_rs, A.q_cs, device)) &&
+                    (!A.weights || dev_vector_ok(A.weights, sum_m, device));
     return ok ? IROTAVG_OK : IROTAVG_ERR_BAD_ARG;
 }
 
@@ -427,6 +429,28 @@ int irotavg_window_init_mst_batch_dev(int64_t nb, const int32_t *sizes, const in
         int device = 0;
         if (const int rc = win_arrays_check(A, plan.sum_m, plan.sum_n, device); rc != IROTAVG_OK) return rc;
         return window_init_mst_batch_dev(plan, device, A, results, static_cast<hipStream_t>(stream));
+    });
+}
+
+// irotavg_cycle_cemp's corruption estimates on many small problems on packed device arrays, one workgroup each, one
+// launch (docs/window_cemp_batch.md): the link in front of the call above. The plan and the array checks of the batched
+// calls (there is no Q), the schedule checks of irotavg_cycle_cemp (below: cemp_args_ok).
+static bool aligned4(const void *p);
+static bool cemp_args_ok(int iters, const double *beta, int64_t max_records);
+int irotavg_window_cemp_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
+                                  int64_t qq_cs, int iters, const double *beta, double *s_dev, int32_t *tri_used_dev,
+                                  int32_t *results, void *stream) {
+    if (!I_dev || !QQ_dev || !cemp_args_ok(iters, beta, 0) || !aligned8(s_dev) || !aligned4(tri_used_dev)) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        WinBatchPlan plan;
+        if (!winbatch_plan(nb, sizes, 1, plan)) return IROTAVG_ERR_BAD_ARG;  // kernel 1: one list, in the caller's order
+        const WinBatchArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, nullptr, 0, 0, nullptr};
+        int device = 0;
+        if (const int rc = win_arrays_check(A, plan.sum_m, plan.sum_n, device); rc != IROTAVG_OK) return rc;
+        if (s_dev && !dev_vector_ok(s_dev, plan.sum_m, device)) return IROTAVG_ERR_BAD_ARG;
+        if (tri_used_dev && !dev_span_ok(tri_used_dev, tri_used_dev + plan.sum_m - 1, device)) return IROTAVG_ERR_BAD_ARG;
+        const WinCempArrays C{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, s_dev, tri_used_dev};
+        return window_cemp_batch_dev(plan, C, iters, beta, results, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -328,6 +328,18 @@ int window_solve_batch_dev(const WinBatchPlan &plan, int device, const WinBatchA
 // A.Q are written and never read, fixed rows read and never written.
 int window_init_mst_batch_dev(const WinBatchPlan &plan, int device, const WinBatchArrays &A, int32_t *results /* host */,
                               hipStream_t stream);
+// wincemp.hip: irotavg_cycle_cemp's definition on every problem of such a batch in one launch
+// (irotavg_window_cemp_batch_dev; docs/window_cemp_batch.md). plan: winbatch_plan(..., kernel = 1, ...); s (sum(m)
+// doubles) and tri_used (sum(m) int32) may each be nullptr; results: 3 nb int32 on the host or nullptr.
+struct WinCempArrays {
+    const int32_t *I;
+    const double *QQ;
+    long long qq_rs, qq_cs;
+    double *s;
+    int32_t *tri_used;
+};
+int window_cemp_batch_dev(const WinBatchPlan &plan, const WinCempArrays &A, int iters, const double *beta /* host */,
+                          int32_t *results /* host */, hipStream_t stream);
 // cycles.hip: the triangle test of every edge (irotavg_cycle_check[_dev]; docs/cycle_check.md). The arguments have been
 // checked. The device form runs on `stream` and writes the caller's device arrays; the host form uploads, runs the same
 // kernels and copies back. Both block until the error word and the summary are back; outputs may each be nullptr.

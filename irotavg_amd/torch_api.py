@@ -626,6 +626,39 @@ def cycle_cemp4(edge_index, QQ, n_total, s, edges=None, beta=None, max_records=0
                 summary=dict(zip(capi.CEMP_SUMMARY_FIELDS, (int(v) for v in h))) if summary and h[0] >= 0 else None)
 
 
+# ---- ... for many small problems in one call (irotavg_window_cemp_batch_dev, docs/window_cemp_batch.md) --------------------
+def window_cemp_batch(sizes, edge_index, QQ, beta=None, s=True, used=True, allow_rc=()):
+    """cycle_cemp on nb independent window-size problems, one workgroup per problem, in one launch on torch's current
+    stream: the screening in front of window_init_mst_batch. sizes, edge_index, QQ: as window_solve_batch takes them (f is
+    held to the limits and otherwise unused). beta: as cycle_cemp (None: cemp_beta(); empty: the plain mean).
+
+    s / used: True (a new tensor, s preset to NaN and used to 0), False / None (not computed), or a contiguous tensor of
+    sum m entries to fill (float64 / int32). Returns dict(rc, s, tri_used, results); results is a host numpy array of
+    (nb, 3) int32: status, sum of tri_used, edges with no used triangle. rc is the first non-zero status in problem order
+    (ERR_BAD_ARG: an edge id outside the problem); anything but OK raises unless listed in allow_rc. A problem that fails
+    keeps its rows of s and tri_used as they were. rank_from_cemp and weights_from_cemp take the packed s as it is."""
+    import numpy as np
+    s32, _, _, sum_m, _ = batch_offsets(sizes)
+    specs = _shapes([(edge_index, "edge_index", _IDS, (sum_m, 2)), (QQ, "QQ", _F64, (sum_m, 4))])
+    wants = (("s", s, torch.float64, float("nan")), ("used", used, torch.int32, 0))
+    for name, want, dt, _ in wants:
+        if not (want is True or want is False or want is None):
+            _check(want, name, (dt,), (sum_m,), placed=False)
+    b = capi.cemp_schedule(cemp_beta() if beta is None else beta)
+    device = _placed(specs)
+    outs = [_output(want, name, sum_m, device, dt, fill) for name, want, dt, fill in wants]
+    nb = len(s32)
+    results = np.zeros((nb, 3), dtype=np.int32)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        rc = capi.lib().irotavg_window_cemp_batch_dev(
+            nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ), len(b),
+            capi._d(b) if len(b) else None, *[None if t is None else _ptr(t) for t in outs],
+            results.ctypes.data_as(C.POINTER(C.c_int32)), _stream(device))
+    _allowed(rc, "irotavg_window_cemp_batch_dev", allow_rc)
+    return dict(rc=rc, s=outs[0], tri_used=outs[1], results=results)
+
+
 def rank_from_cemp(s, threshold):
     """The rank init_tree takes, from the estimates of cycle_cemp, in plain torch on the device: 0 for s <= threshold, 1
     for NaN (no used triangle), 2 otherwise. Returns an int32 tensor of m entries."""
