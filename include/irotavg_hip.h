@@ -488,6 +488,33 @@ int irotavg_window_init_mst_batch_dev(int64_t nb, const int32_t *sizes, const in
                                       int64_t qq_rs, int64_t qq_cs, double *Q_dev, int64_t q_rs, int64_t q_cs,
                                       int32_t *results, void *stream);
 
+/* The rank-aware tree initialisation for many small problems in one call, on arrays that live on the device
+ * (docs/window_init_tree_batch.md): the link between irotavg_window_cemp_batch_dev and the solve, one workgroup per
+ * problem, ONE launch. sizes, packing, limits, the stride rule, alignment and the lowest / highest-element check are
+ * those of irotavg_window_solve_batch_dev. Per problem the fixed views [0, f) together are one root; an edge k is usable
+ * when rank[k] >= 0 and its ends are not both fixed and not the same view; the tree is the minimum spanning forest of
+ * {root} + free views under the keys (rank[k], k), k the position inside the problem -- irotavg_init_tree's tree when
+ * f = 1. T(u) = Q[u] for a fixed u, T(b) = QQ_k (x) T(a) along a tree edge k = (a, b) walked from a, T(a) = QQ_k* (x) T(b)
+ * walked from b (QQ_k*: w negated); a free view v gets +-T(v) up to rounding (sign and association are not specified).
+ *   rank_dev     sum(m) int32, 4-byte aligned, or NULL (all zero); rank[k] < 0: edge k is never used
+ *   Q_dev        the rows of fixed views are read where a tree edge enters them and never written; the rows of free views
+ *                are written and never read, so they may be uninitialised (NaN included); nothing is normalised
+ *   in_tree_dev  sum(m) int32 or NULL: 1 for a tree edge, 0 for every other edge of the problem (n_total - f ones)
+ *   results      HOST, 4 nb int32 or NULL: per problem its status, the free views not joined to the root, the tree edges
+ *                with rank > 0, the largest rank in the tree (the last two 0 unless the status is IROTAVG_OK)
+ * IROTAVG_ERR_BAD_ARG before any device work: what irotavg_window_solve_batch_dev refuses of nb, sizes, pointers, strides
+ * and alignment, and a problem with f < 1; no HIP device: IROTAVG_ERR_NO_DEVICE. The edge ids are read on the device
+ * alone: the workgroup of a problem with an id outside [0, n_total) reports IROTAVG_ERR_BAD_ARG and indexes nothing with
+ * it; a problem with a free view that no chain of usable edges joins to a fixed view reports IROTAVG_ERR_NOT_SPANNING and
+ * their count (a fixed view no edge touches does not matter). A problem that fails keeps every byte of its rows of Q_dev
+ * and in_tree_dev; the other problems are computed. The launch goes on `stream` itself: inputs may still be in flight
+ * there, the outputs are ready for whatever is enqueued on it next. The call blocks until every result record has
+ * arrived and returns the first non-zero status in problem order. Deterministic: two calls give the same bytes, and a
+ * problem gives the same bytes wherever it stands in a batch. */
+int irotavg_window_init_tree_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                       int64_t qq_rs, int64_t qq_cs, const int32_t *rank_dev, double *Q_dev, int64_t q_rs,
+                                       int64_t q_cs, int32_t *in_tree_dev, int32_t *results, void *stream);
+
 /* The corruption estimates of irotavg_cycle_cemp (below) for many small problems in one call, on arrays that live on the
  * device (docs/window_cemp_batch.md): the screening in front of init -> solve -> gate, one workgroup per problem, ONE
  * launch, the start vector and every iteration inside it. sizes, packing, limits, the stride rule, alignment and the

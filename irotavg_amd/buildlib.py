@@ -7,11 +7,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 CLI = os.path.join(HERE, "bin", "l1_irls")
 LIB = os.path.join(HERE, "libirotavg_hip.so")
-SOURCES = ["build.cpp", "gbuild.hip", "solver.hip", "cgcg.hip", "dense.hip", "bcr.hip", "l1pd.hip", "capi.cpp", "viewgraph.cpp", "dist.hip", "window.hip", "resident.hip", "marginals.hip", "edgediag.hip", "wincov.hip", "winmst.hip", "wincemp.hip", "cycles.hip", "cycles4.hip", "treeinit.hip", "components.hip", "cemp.hip", "cemp4.hip", "sweep.hip", "devapi.hip"]
-# flags of single sources: cemp.hip, cemp4.hip, sweep.hip and wincemp.hip are compiled without the packed fp32 instructions (everything in them is fp64)
+SOURCES = ["build.cpp", "gbuild.hip", "solver.hip", "cgcg.hip", "dense.hip", "bcr.hip", "l1pd.hip", "capi.cpp", "viewgraph.cpp", "dist.hip", "window.hip", "resident.hip", "marginals.hip", "edgediag.hip", "wincov.hip", "winmst.hip", "wincemp.hip", "wintree.hip", "cycles.hip", "cycles4.hip", "treeinit.hip", "components.hip", "cemp.hip", "cemp4.hip", "sweep.hip", "devapi.hip"]
+# flags of single sources: cemp.hip, cemp4.hip, sweep.hip, wincemp.hip and wintree.hip are compiled without the packed fp32 instructions (everything in them is fp64)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-FLAGS = {"cemp.hip": NO_PACKED_FP32, "cemp4.hip": NO_PACKED_FP32, "sweep.hip": NO_PACKED_FP32, "wincemp.hip": NO_PACKED_FP32}
-HEADERS = ["common.hpp", "graph.hpp", "kernels.hpp", "asm0w.hpp", "bcr_route.hpp", "switches.hpp", "marginals.hpp", "winbatch.hpp", "winio.hpp", "winmst.hpp", "wincemp.hpp", "cycles.hpp", "cycles4.hpp", "cycload.hpp", "cemp.hpp", "cemp4.hpp", "sweep.hpp", "treeinit.hpp", "components.hpp", "hostwait.hpp", "batchdev.hpp", "../../include/irotavg_hip.h"]
+FLAGS = {"cemp.hip": NO_PACKED_FP32, "cemp4.hip": NO_PACKED_FP32, "sweep.hip": NO_PACKED_FP32, "wincemp.hip": NO_PACKED_FP32, "wintree.hip": NO_PACKED_FP32}
+HEADERS = ["common.hpp", "graph.hpp", "kernels.hpp", "asm0w.hpp", "bcr_route.hpp", "switches.hpp", "marginals.hpp", "winbatch.hpp", "winio.hpp", "winmst.hpp", "wincemp.hpp", "wintree.hpp", "cycles.hpp", "cycles4.hpp", "cycload.hpp", "cemp.hpp", "cemp4.hpp", "sweep.hpp", "treeinit.hpp", "components.hpp", "hostwait.hpp", "batchdev.hpp", "../../include/irotavg_hip.h"]
 
 
 def hipcc():

@@ -50,7 +50,7 @@ SYMBOLS = [
     "irotavg_graph_rotation_variance_dev", "irotavg_graph_edge_diagnostics_dev", "irotavg_window_solve_batch_dev",
     "irotavg_window_uncertainty", "irotavg_window_uncertainty_batch_dev",
     "irotavg_window_gate", "irotavg_window_gate_batch_dev",
-    "irotavg_window_init_mst_batch_dev", "irotavg_window_cemp_batch_dev",
+    "irotavg_window_init_mst_batch_dev", "irotavg_window_cemp_batch_dev", "irotavg_window_init_tree_batch_dev",
     "irotavg_cycle_check","irotavg_cycle_check_dev", "irotavg_cycle_check_group",
     "irotavg_cycle_check4", "irotavg_cycle_check4_dev", "irotavg_cycle_check4_group",
     "irotavg_init_tree", "irotavg_init_tree_dev", "irotavg_init_tree_counters",
@@ -190,6 +190,8 @@ def lib():
                                                     C.c_int64, C.c_int64, C.POINTER(C.c_int32), vp]
     L.irotavg_window_cemp_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, C.c_int, _dp,
                                                 vp, vp, C.POINTER(C.c_int32), vp]
+    L.irotavg_window_init_tree_batch_dev.argtypes = [C.c_int64, C.POINTER(C.c_int32), vp, vp, C.c_int64, C.c_int64, vp, vp,
+                                                     C.c_int64, C.c_int64, vp, C.POINTER(C.c_int32), vp]
     L.irotavg_cycle_check.argtypes = [C.c_int64, C.c_int64, _ip, _dp, C.c_int64, C.c_double, _ip, _ip, _dp, _i64p]
     L.irotavg_cycle_check_dev.argtypes = [C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int64, C.c_double, vp, vp, vp, _i64p,
                                           vp]

@@ -432,10 +432,34 @@ int irotavg_window_init_mst_batch_dev(int64_t nb, const int32_t *sizes, const in
     });
 }
 
-// irotavg_cycle_cemp's corruption estimates on many small problems on packed device arrays, one workgroup each, one
-// launch (docs/window_cemp_batch.md): the link in front of the call above. The plan and the array checks of the batched
-// calls (there is no Q), the schedule checks of irotavg_cycle_cemp (below: cemp_args_ok).
+// The rank-aware tree initialisation of many small problems on packed device arrays, one workgroup each, one launch
+// (docs/window_init_tree_batch.md): the arrays, the plan and the checks of the call above, then rank_dev and in_tree_dev
+// by their lowest and highest element.
 static bool aligned4(const void *p);
+int irotavg_window_init_tree_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev,
+                                       int64_t qq_rs, int64_t qq_cs, const int32_t *rank_dev, double *Q_dev, int64_t q_rs,
+                                       int64_t q_cs, int32_t *in_tree_dev, int32_t *results, void *stream) {
+    if (!I_dev || !QQ_dev || !Q_dev || !aligned4(rank_dev) || !aligned4(in_tree_dev)) return IROTAVG_ERR_BAD_ARG;
+    return guarded([&]() -> int {
+        WinBatchPlan plan;
+        if (!winbatch_plan(nb, sizes, 1, plan)) return IROTAVG_ERR_BAD_ARG;  // kernel 1: one list, in the caller's order
+        for (const WinDesc &d : plan.desc)
+            if (d.f < 1) return IROTAVG_ERR_BAD_ARG;  // the root is the fixed views: there must be one
+        const WinBatchArrays A{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
+                               nullptr};
+        int device = 0;
+        if (const int rc = win_arrays_check(A, plan.sum_m, plan.sum_n, device); rc != IROTAVG_OK) return rc;
+        for (const int32_t *p : {rank_dev, static_cast<const int32_t *>(in_tree_dev)})
+            if (p && !dev_span_ok(p, p + plan.sum_m - 1, device)) return IROTAVG_ERR_BAD_ARG;
+        const WinTreeArrays T{I_dev, QQ_dev, (long long)qq_rs, (long long)qq_cs, Q_dev, (long long)q_rs, (long long)q_cs,
+                              rank_dev, in_tree_dev};
+        return window_init_tree_batch_dev(plan, T, results, static_cast<hipStream_t>(stream));
+    });
+}
+
+// irotavg_cycle_cemp's corruption estimates on many small problems on packed device arrays, one workgroup each, one
+// launch (docs/window_cemp_batch.md): the link in front of the two calls above. The plan and the array checks of the batched
+// calls (there is no Q), the schedule checks of irotavg_cycle_cemp (below: cemp_args_ok).
 static bool cemp_args_ok(int iters, const double *beta, int64_t max_records);
 int irotavg_window_cemp_batch_dev(int64_t nb, const int32_t *sizes, const int32_t *I_dev, const double *QQ_dev, int64_t qq_rs,
                                   int64_t qq_cs, int iters, const double *beta, double *s_dev, int32_t *tri_used_dev,

@@ -340,6 +340,21 @@ struct WinCempArrays {
 };
 int window_cemp_batch_dev(const WinBatchPlan &plan, const WinCempArrays &A, int iters, const double *beta /* host */,
                           int32_t *results /* host */, hipStream_t stream);
+// wintree.hip: the minimum spanning forest under the keys (rank[k], k), grown from the fixed views, and the free views'
+// rotations along it, on every problem of such a batch in one launch (irotavg_window_init_tree_batch_dev;
+// docs/window_init_tree_batch.md). plan: winbatch_plan(..., kernel = 1, ...), every f >= 1; rank and in_tree (sum(m) int32)
+// may each be nullptr; results: 4 nb int32 on the host or nullptr. Free rows of Q are written and never read, fixed rows
+// read and never written.
+struct WinTreeArrays {
+    const int32_t *I;
+    const double *QQ;
+    long long qq_rs, qq_cs;
+    double *Q;
+    long long q_rs, q_cs;
+    const int32_t *rank;
+    int32_t *in_tree;
+};
+int window_init_tree_batch_dev(const WinBatchPlan &plan, const WinTreeArrays &A, int32_t *results /* host */, hipStream_t stream);
 // cycles.hip: the triangle test of every edge (irotavg_cycle_check[_dev]; docs/cycle_check.md). The arguments have been
 // checked. The device form runs on `stream` and writes the caller's device arrays; the host form uploads, runs the same
 // kernels and copies back. Both block until the error word and the summary are back; outputs may each be nullptr.

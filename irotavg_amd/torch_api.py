@@ -659,6 +659,48 @@ def window_cemp_batch(sizes, edge_index, QQ, beta=None, s=True, used=True, allow
     return dict(rc=rc, s=outs[0], tri_used=outs[1], results=results)
 
 
+# ---- the rank-aware initialisation behind it (irotavg_window_init_tree_batch_dev, docs/window_init_tree_batch.md) ----------
+def window_init_tree_batch(sizes, edge_index, QQ, Q, rank=None, in_tree=False, allow_rc=()):
+    """Initial rotations of nb independent window-size problems along the minimum spanning forest under the keys
+    (rank[k], k), grown from the fixed views, one workgroup per problem, in one launch on torch's current stream: the link
+    between window_cemp_batch / rank_from_cemp and window_solve_batch. sizes, edge_index, QQ, Q: as window_solve_batch
+    takes them, every problem with f >= 1. With f = 1 the tree is init_tree's.
+
+    rank: None (all zero) or a contiguous int32 or int64 tensor of sum m entries (int64 is narrowed; a value outside int32
+    range raises ValueError); rank[k] < 0: edge k is never used. in_tree: True (a new int32 tensor, preset to 0), False /
+    None, or a contiguous int32 tensor of sum m entries to fill. Q is updated in place: the rows of free views are written
+    (they are never read and may hold NaN), the rows of fixed views are read and never written. Returns dict(rc, Q,
+    in_tree, results); results is a host numpy array of (nb, 4) int32: status, free views not joined to a fixed view, tree
+    edges with rank > 0, the largest rank in the tree. rc is the first non-zero status in problem order (ERR_BAD_ARG: an
+    edge id outside the problem, ERR_NOT_SPANNING: a free view the usable edges do not join to a fixed view); anything
+    but OK raises unless listed in allow_rc. A problem that fails keeps its rows of Q and in_tree as they were."""
+    import numpy as np
+    s32, sum_m, _, specs = _batch_tensors(sizes, edge_index, QQ, Q)
+    if rank is not None:
+        specs += _shapes([(rank, "rank", _IDS, (sum_m,))])
+    if not (in_tree is True or in_tree is False or in_tree is None):
+        _check(in_tree, "in_tree", (torch.int32,), (sum_m,), placed=False)
+    device = _placed(specs)
+    rk = None
+    if rank is not None:
+        rk = _vector(rank, "rank", sum_m, device, rank.dtype)
+        if rk.dtype == torch.int64:
+            if sum_m and (int(rk.min()) < -INT32_MAX - 1 or int(rk.max()) > INT32_MAX):
+                raise ValueError("rank must lie in int32 range")
+            rk = rk.to(torch.int32)
+    tree = _output(in_tree, "in_tree", sum_m, device, torch.int32, 0)
+    nb = len(s32)
+    results = np.zeros((nb, 4), dtype=np.int32)
+    with torch.cuda.device(device):
+        ei = _narrow(edge_index)
+        rc = capi.lib().irotavg_window_init_tree_batch_dev(
+            nb, s32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(ei), _ptr(QQ), *matrix_strides(QQ),
+            None if rk is None else _ptr(rk), _ptr(Q), *matrix_strides(Q), None if tree is None else _ptr(tree),
+            results.ctypes.data_as(C.POINTER(C.c_int32)), _stream(device))
+    _allowed(rc, "irotavg_window_init_tree_batch_dev", allow_rc)
+    return dict(rc=rc, Q=Q, in_tree=tree, results=results)
+
+
 def rank_from_cemp(s, threshold):
     """The rank init_tree takes, from the estimates of cycle_cemp, in plain torch on the device: 0 for s <= threshold, 1
     for NaN (no used triangle), 2 otherwise. Returns an int32 tensor of m entries."""
